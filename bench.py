@@ -2,7 +2,8 @@
 """Benchmark of the ALD reconstruction hot path (BASELINE.json metric: ALD reconstructions/sec, 128x128 complex,
 R=40, 4 coils) on N MI355X of one node.
 
-    python bench.py                       # N=1
+    python bench.py                       # N=1, the headline line only
+    python bench.py --full                # + roofline, the other kernel families, upfirdn2d, 105 samples, CPU baseline
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
 
@@ -17,15 +18,22 @@ One "step" = one Langevin iteration of a rank's whole sample batch: the score ne
 reconstruction is 2311*3 = 6933 such iterations plus one denoising score evaluation (counted as a 6934th
 iteration); the iteration cost does not depend on the noise level (same launches, same shapes), so
     value = total samples / (ms_per_step * 6934)
-with the timed steps strided evenly over the 6933-iteration schedule.  `--full` runs the entire schedule instead
-and reports the directly measured rate (takes ~6934/steps times longer).
+with the timed steps strided evenly over the 6933-iteration schedule.  `--whole-schedule` runs the entire schedule
+instead and reports the directly measured rate (takes ~6934/steps times longer).
 
-The JSON line also carries
+`--dump-outputs DIR` writes the sample state after the last timed step (what a caller of the iteration receives) as
+float32 .npy files: samples_real.npy / samples_imag.npy, shape (B, 1, 128, 128), with a `_rank<r>` suffix when N > 1.
+Inputs (phantom, coils, mask, weights, noise stream, strided levels) are seeded, so equal arguments give equal inputs.
+
+A plain run prints only the headline line.  With `--full` the JSON line also carries
   roofline      fp32 MFMA roofline of the dominant kernel family (conv_mfma_kernel<...>, the dense 3x3/1x1
                 convolutions): algorithmic FLOPs of the 113 conv launches of one score evaluation divided by
                 their summed durations, measured with HIP events around every conv launch on the launch stream.
   cpu_baseline  the CPU oracle (oracle/, a torch-CPU restatement pinned to the reference) timed on this host's
                 cores on a bounded slice of the same workload (1 sample, a few iterations), rank 0 / N=1 only.
+  alt_*, upfirdn2d, config3_on_one_gpu   (N=1, not with --whole-schedule) the other convolution families on the same
+                iteration, upfirdn2d's HBM rate, and all 105 samples of config 3 as one batch on this GPU.
+  config.posterior_mag_mean   from the one collective of the path (posterior moments of the current samples).
 """
 import argparse
 import json
@@ -51,7 +59,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=60)
     ap.add_argument("--warmup", type=int, default=6)
-    ap.add_argument("--full", action="store_true", help="run the whole 6933-iteration schedule + denoise")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the extra measurements: roofline census, other kernel families, upfirdn2d, 105 samples, "
+                         "CPU baseline (each can be dropped with its --no-* switch)")
+    ap.add_argument("--whole-schedule", action="store_true", help="time the whole 6933-iteration schedule + denoise")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the sample state after the last timed step as float32 .npy files into DIR")
     ap.add_argument("--samples-rank0", type=int, default=14)
     ap.add_argument("--samples-other", type=int, default=13)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -61,7 +74,10 @@ def parse():
     ap.add_argument("--no-cpu-mnist", action="store_true", help="skip the end-to-end MNIST-shaped CPU anchor")
     ap.add_argument("--no-full-batch", action="store_true", help="N=1: skip the extra 105-sample measurement")
     ap.add_argument("--no-graph", action="store_true")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.whole_schedule and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def log(msg):
@@ -204,6 +220,22 @@ def upfirdn2d_hbm(dev):
     return res
 
 
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(out_dir, x, B, world, rank):
+    """the (2B, 1, H, W) [real | imaginary] state of the timed iteration -> <out_dir>/samples_{real,imag}[_rank<r>].npy
+    (float32).  Over the byte budget (all ranks together) a fixed, seeded subset of the samples is written."""
+    keep = max(1, min(B, DUMP_BYTES_MAX // (world * 2 * x[0].numel() * 4)))
+    idx = np.arange(B) if keep == B else np.sort(np.random.default_rng(0).choice(B, keep, replace=False))
+    host = x.detach().float().cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for part, block in (("real", host[:B]), ("imag", host[B:2 * B])):
+        np.save(os.path.join(out_dir, f"samples_{part}{suffix}.npy"), np.ascontiguousarray(block[idx]))
+    log(f"rank {rank}: wrote {keep} of {B} samples to {out_dir}")
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -240,7 +272,7 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    if args.full:
+    if args.whole_schedule:
         steps, warm = n_sched, 0
         order = np.arange(n_sched)
     else:
@@ -254,7 +286,7 @@ def main():
     t0 = time.perf_counter()
     for k in order[warm:warm + steps]:
         runner.run(int(k))
-    if args.full:                                                    # denoise: one more score evaluation
+    if args.whole_schedule:                                          # denoise: one more score evaluation
         with torch.no_grad():
             runner.st["labels"].fill_(L_LEVELS - 1)
             prob.scorenet(runner.x, runner.st["labels"])
@@ -266,11 +298,11 @@ def main():
     elapsed = float(t.item())
     log(f"rank {rank}: {steps} steps in {elapsed:.3f} s")
     finite = bool(torch.isfinite(runner.x).all())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, runner.x, runner.B, world, rank)
 
-    # the one collective of the path: posterior moments of the current samples
-    post = sharding.all_reduce_posterior(runner.current(), total)
     ms_per_step = elapsed * 1e3 / steps
-    if args.full:
+    if args.whole_schedule:
         value = total / elapsed
     else:
         value = total / (ms_per_step * 1e-3 * ITER_PER_RECON)
@@ -295,15 +327,18 @@ def main():
             "step": "one Langevin iteration of a rank's sample batch: score net on (2B,1,128,128) + fused "
                     "Langevin/SENSE-proximal kernel, one hipGraph replay",
             "iterations_per_reconstruction": ITER_PER_RECON,
-            "value_formula": "total_samples / elapsed" if args.full else
+            "value_formula": "total_samples / elapsed" if args.whole_schedule else
                              "total_samples / (ms_per_step * iterations_per_reconstruction)",
             "samples_total": total, "samples_this_rank": n_local, "parallelism": f"sample-sharded x{world}",
             "hip_graph": not args.no_graph, "state_finite": finite,
-            "posterior_mag_mean": float(post["mag_mean"].mean()),
         },
     }
+    if args.full:
+        # the one collective of the path: posterior moments of the current samples
+        post = sharding.all_reduce_posterior(runner.current(), total)
+        out["config"]["posterior_mag_mean"] = float(post["mag_mean"].mean())
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- roofline of the dominant kernel family: per-launch HIP events around every conv of one forward
         x = runner.x.clone()
         labels = runner.st["labels"].clone()
@@ -383,7 +418,7 @@ def main():
                 "winograd_launches": n_wino, "executed_mfma_tflops": executed / (conv_ms * 1e-3) / 1e12,
                 "executed_mfma_frac": executed / (conv_ms * 1e-3) / 1e12 / PEAK_FP32_MFMA_TFLOPS,
             }, **common)
-        if world == 1 and not args.full and not args.no_alt and ops.split_impl():
+        if world == 1 and not args.whole_schedule and not args.no_alt and ops.split_impl():
             # the same iteration through the other kernel families, reported beside the headline so that the split result can
             # be judged against them: the exact-fp32-MFMA kernels (conv_mfma_kernel + fp32 Winograd) and the other split
             headline_impl = ops.CONV_IMPL
@@ -412,9 +447,9 @@ def main():
                     del alt
                 finally:
                     ops.CONV_IMPL = headline_impl
-        if world == 1 and not args.full and not args.no_alt:
+        if world == 1 and not args.whole_schedule and not args.no_alt:
             out["upfirdn2d"] = upfirdn2d_hbm(dev)
-        if world == 1 and not args.full and not args.no_full_batch and total != 105:
+        if world == 1 and not args.whole_schedule and not args.no_full_batch and total != 105:
             # the WHOLE of BASELINE config 3 (105 posterior samples) on this one GPU: with the driver's N = 2, 4, 8 runs this
             # is the strong-scaling reference point of the 1 -> 8 curve (the headline `value` keeps the per-GPU share).
             # Same kernels, same dispatch (the rule is batch-independent), one hipGraph of the (210, 1, 128, 128) iteration.
@@ -446,6 +481,7 @@ def main():
                 out["config3_on_one_gpu"] = {"error": repr(e)[:300]}
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(prob, args.cpu_steps_b1, args.cpu_steps_b8, not args.no_cpu_mnist)
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

@@ -11,7 +11,7 @@ for r in $(seq 1 $ROUNDS); do
     (
       if [[ "$v" == *=* ]]; then IFS=',' read -ra KV <<< "$v"; for kv in "${KV[@]}"; do export "$kv"; done
       elif [ "$v" != "prod" ]; then export IPDM_LIB=$ROOT/_variants/libipdm_$v.so; fi
-      timeout -k 10 300 python bench.py --steps 40 --warmup 6 --no-cpu-baseline --no-alt --no-full-batch 2>/dev/null | python -c "
+      timeout -k 10 300 python bench.py --steps 40 --warmup 6 --full --no-cpu-baseline --no-alt --no-full-batch 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('$v', round(d['ms_per_step'],3), round(d['roofline']['conv_ms_per_step'],3))"
     )
   done
