@@ -459,6 +459,15 @@ int ipdm_conv_wino_hx2_pack_weight(const float* w /* [Cout][Cin][3][3] */, void*
 int ipdm_conv2d_wino_hx2_f32(const float* x, const void* U, const float* bias, const float* residual, float* out,
                              float* out_act, int act_out, int B, int Cin, int Cout, int H, int W, int dilation,
                              int pool2, const ipdm_conv_ext_t* ext, void* stream);
+/* Which instantiation of the persistent 2-D Winograd kernel ipdm_conv2d_wino_hx2_f32 runs for a layer shape (a function of the
+ * shape and of the IPDM_WBX3_* environment switches, never of the batch); IPDM_EUNSUPPORTED where the kernel does not apply.
+ * CO32: (image, 32 output channels) workgroups; HALF: (image, upper / lower eight rows, 64 channels) workgroups -- both for
+ * undilated <= 16-pixel layers with fewer than 512 output channels, HALF for the 16 x 16 ones; POLY: dilated 16 x 16 layers. */
+#define IPDM_WINO_FORM_OTHER 0
+#define IPDM_WINO_FORM_CO32 1
+#define IPDM_WINO_FORM_HALF 2
+#define IPDM_WINO_FORM_POLY 3
+int ipdm_conv2d_wino_hx2_form(int Cin, int Cout, int H, int W, int dilation);
 /* 1-D Winograd form of the same 3x3 convolution on f16x2 operands (conv_wino1d.hip): F(2,3) along x, the filter's three rows as
  * K -- 4 positions instead of 16, 128 output channels per workgroup, 12 instead of 16 weight values per (co, ci) and 1.5x the
  * matrix instructions.  Same arguments as ipdm_conv2d_wino_hx2_f32 without the dilation (undilated launches; Cin % 32 == 0,

@@ -618,19 +618,27 @@ __global__ __launch_bounds__(512) void conv_wino_bx3_kernel(ConvArgs a) {
 // CO32: 32 output channels per workgroup (one channel tile per wave instead of two: half the accumulators) -- for 16-pixel layers with
 // fewer than 512 output channels, whose (image, 64-channel tile) pairs fill under half of the chip: twice the workgroups, the whole K
 // loop in each, instead of two K halves + a reduction launch
+// HALF (TX x TY = 8 x 4): 64 output channels of the upper or the lower eight rows of a 16 x 16 image per workgroup -- the same
+// layers and the same number of workgroups as CO32, split by PIXELS instead of channels: a thread holds ONE patch per chunk
+// (lane = tile, half-wave = channel of the wave's pair; the halves trade eight transformed values by v_permlane32_swap and
+// each splits and stores eight positions), a B fragment feeds six MFMAs, and only tile group 0 of a V stage is used.  Chunk
+// order along K and the three MFMAs of a product are those of every other form: the same bits.
 template <bool HX, int TX, int TY, bool CO_MAJOR, bool DMA4, bool POOL = false, bool STATS = false, bool KSP = false, bool POLY = false,
-          bool CO32 = false>
+          bool CO32 = false, bool HALF = false>
 __global__ __launch_bounds__(512) void conv_wino_bx3_wide_kernel(ConvArgs a, int total_tiles) {
   constexpr int NPC = HX ? 2 : 3;                            // operand pieces; FRAG: 16-byte units per (chunk, channel tile)
   constexpr int FRAG = 64 * NPC;
   constexpr int NC = CO32 ? 1 : 2;                           // 32-channel tiles per workgroup
   static_assert(!CO32 || (HX && TX == 8 && TY == 8 && DMA4 && !POOL && !STATS && !KSP && !POLY), "CO32: the plain 8 x 8 form");
   static_assert(!POLY || (TX == 8 && TY == 8 && DMA4 && !POOL && !STATS && !KSP), "POLY: the 8 x 8 form, plain epilogue");
+  static_assert(!HALF || (HX && TX == 8 && TY == 4 && DMA4 && !POOL && !STATS && !KSP && !POLY && !CO32), "HALF: the plain 8 x 4 form");
+  constexpr int NTG = HALF ? 1 : 2;                           // 32-tile groups per workgroup
+  constexpr int NDMA = HALF ? 2 : 4;                          // (wave-private) DMA instructions per wave and chunk
   constexpr int PPW = 24, PPH = 17;                           // POLY: padded row pitch / rows per channel
   constexpr int QC = POLY ? PPW / 4 : TX / 2 + 2, RC4 = 4 * QC;   // quads / floats per raw row (x0-4 .. x0+2TX+3)
   constexpr int QN = POLY ? PPH * QC : (2 * TY + 2) * QC;     // quads per channel
   constexpr int NI = (X_KC * QN + 63) / 64;                   // wave-instructions per chunk
-  static_assert(NI >= 24 && NI <= 32 && NI * 256 <= X_R_ELEMS, "quad image fits the raw stage; pieces 0..23 exist");
+  static_assert(HALF || (NI >= 24 && NI <= 32 && NI * 256 <= X_R_ELEMS), "quad image fits the raw stage; pieces 0..23 exist");
   // f16x2 + 16-byte DMA: the raw stage is WAVE-PRIVATE -- wave w fetches exactly the two channels (2w, 2w+1) whose patches its
   // own threads transform, into its own 4 KiB block (2 * QN quads <= 256 = four wave-instructions).  No other wave ever reads
   // that block, so the raw data needs no barrier at all: a wave waits for ITS DMA with a counted vmcnt, reads its patches into
@@ -638,8 +646,8 @@ __global__ __launch_bounds__(512) void conv_wino_bx3_wide_kernel(ConvArgs a, int
   // the V stage's.  (Shared raw stage: barrier -> DMA -> landing -> barrier -> patch reads -> barrier was the critical path,
   // 4.1 k cycles per chunk against 1.5 k of matrix work.)
   constexpr bool WPRIV = HX && DMA4;
-  static_assert(!WPRIV || 2 * QN <= 256, "a wave's two channels fit four DMA instructions");
-  static_assert(TX * TY == X_TILES, "64 tiles per workgroup");
+  static_assert(!WPRIV || 2 * QN <= 64 * NDMA, "a wave's two channels fit its DMA instructions");
+  static_assert(TX * TY * 2 == X_TILES * NTG, "32 tiles per tile group");
   constexpr int RC = 2 * TX + 2, RR = 2 * TY + 2;            // raw region: 34 x 10 or 18 x 18 pixels (<= X_RCH)
   static_assert(RC * RR <= X_RCH, "raw region fits its LDS slot");
   extern __shared__ __align__(16) float lds[];
@@ -698,7 +706,7 @@ __global__ __launch_bounds__(512) void conv_wino_bx3_wide_kernel(ConvArgs a, int
   const __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float*>(a.x), 0, (int)((size_t)a.B * a.Cin * HW * 4), 0x00020000);
   float* const rs = lds + 2 * X_V_ELEMS;
-  const int mytile = tid & 63;
+  const int mytile = HALF ? tid & 31 : tid & 63;
 
   // raw stage by LDS-DMA.  dword form: wave w brings in channels 2w, 2w+1 (6 x 64 floats each); quad form: the
   // chunk's 16 channels are one packed image of NI x 64 quads, wave w issues pieces w, w+8, w+16, w+24
@@ -714,7 +722,7 @@ __global__ __launch_bounds__(512) void conv_wino_bx3_wide_kernel(ConvArgs a, int
     if constexpr (KSP) dma_c0 = g.c0;
     if constexpr (DMA4) {
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
+      for (int k = 0; k < NDMA; ++k) {
         const int e = (WPRIV ? k : dma_piece(k)) * 64 + lane;
         const int cl = e / QN, qq = e - cl * QN;                // WPRIV: cl = channel of the wave's pair (>= 2: padding lanes,
         const int cin = WPRIV ? 2 * wave + cl : cl;             //        which write zeros into the tail of the wave's own block)
@@ -739,7 +747,7 @@ __global__ __launch_bounds__(512) void conv_wino_bx3_wide_kernel(ConvArgs a, int
     if constexpr (DMA4) {
       [[maybe_unused]] const int soff = (int)(((size_t)dma_b * a.Cin + chunk * X_KC) * HW * 4);
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
+      for (int k = 0; k < NDMA; ++k) {
 #if defined(__HIP_DEVICE_COMPILE__)   // the 16-byte form only exists for gfx950: keep it out of the host pass
         __builtin_amdgcn_raw_ptr_buffer_load_lds(
             x_rsrc, (__attribute__((address_space(3))) void*)(rs + (WPRIV ? wave * 4 + k : dma_piece(k)) * 256), 16, dma_off[k],
@@ -761,14 +769,13 @@ __global__ __launch_bounds__(512) void conv_wino_bx3_wide_kernel(ConvArgs a, int
   float dreg[16];
   // POLY: this thread's tile in the polyphase tile space, and the padded-image offsets of its patch rows / columns
   const int pd = POLY ? a.dil : 1;
+  // (16 x 16 images, d = 2 or 4: 8 / d tiles per row and column of a sub-image, all powers of two -- shifts and masks instead of
+  // quotients by run-time values.  Cheap enough for hipcc to hoist out of every loop: see etile_p in the epilogue)
+  const int pls = pd == 4 ? 1 : pd == 2 ? 2 : 3;              // log2 of the tiles per sub-image row; log2(d) = 3 - pls
   auto tile_origin = [&](int tl, int& py, int& px) {
-    const int tws = a.W / (2 * pd), ths = a.H / (2 * pd);
-    const int txx = tl % tws;
-    int r = tl / tws;
-    const int tyy = r % ths;
-    r /= ths;
-    py = pd * (2 * tyy) + r / pd;
-    px = pd * (2 * txx) + r % pd;
+    const int txx = tl & ((1 << pls) - 1), tyy = (tl >> pls) & ((1 << pls) - 1), r = tl >> (2 * pls);
+    py = pd * (2 * tyy) + (r >> (3 - pls));
+    px = pd * (2 * txx) + (r & (pd - 1));
   };
   [[maybe_unused]] int prow[4], pcol[4];
   if constexpr (POLY) {
@@ -888,9 +895,37 @@ __global__ __launch_bounds__(512) void conv_wino_bx3_wide_kernel(ConvArgs a, int
       vs[(p * 2 + 1) * (8 * X_TILES)] = lp;
     }
   };
+  // HALF: this thread holds B^T d B of channel 2w + h of its tile in v.  The half-waves trade eight values each, so that a
+  // thread has BOTH channels of positions 8h .. 8h+7: vp[p][0] / vp[p][1] = channel 2w / 2w+1 of position 8h + p
+  [[maybe_unused]] auto trade_halves = [&](const float (&v)[16], float (&vp)[8][2]) {
+#pragma unroll
+    for (int p = 0; p < 8; ++p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+      const auto r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, v[p]), __builtin_bit_cast(unsigned, v[p + 8]), false, false);
+      vp[p][0] = __builtin_bit_cast(float, (unsigned)r[0]);
+      vp[p][1] = __builtin_bit_cast(float, (unsigned)r[1]);
+#endif
+    }
+  };
+  [[maybe_unused]] auto store_half = [&](float* st, const float (&vp)[8][2]) {
+    unsigned* vs = reinterpret_cast<unsigned*>(st) + wave * X_TILES + mytile + (8 * h) * 2 * (8 * X_TILES);
+#pragma unroll
+    for (int p = 0; p < 8; ++p) {
+      unsigned hp, lp;
+      split2_pk_scaled(vp[p][0], vp[p][1], hx_in, hp, lp);
+      vs[(p * 2 + 0) * (8 * X_TILES)] = hp;
+      vs[(p * 2 + 1) * (8 * X_TILES)] = lp;
+    }
+  };
   // stage the chunk held in the raw stage into V stage `st` (this thread: its tile, channels 2w and 2w+1)
   auto stage_chunk = [&](float* st) {
-    if constexpr (HX) {
+    if constexpr (HALF) {
+      float va[16], vp[8][2];
+      read_patch_to(va, h);
+      transform(va);
+      trade_halves(va, vp);
+      store_half(st, vp);
+    } else if constexpr (HX) {
       float va[16], vb[16];
       read_patch_to(va, 2 * wave);
       transform(va);
@@ -927,12 +962,12 @@ __global__ __launch_bounds__(512) void conv_wino_bx3_wide_kernel(ConvArgs a, int
       fr[s] = make_uint4(bp[s * 8 * X_TILES], bp[(s * 8 + 1) * X_TILES], bp[(s * 8 + 2) * X_TILES], bp[(s * 8 + 3) * X_TILES]);
   };
 
-  f32x16 acc[2][NC][2];
+  f32x16 acc[2][NC][NTG];
   auto zero_acc = [&]() {
 #pragma unroll
-    for (int i = 0; i < 4 * NC; ++i)
+    for (int i = 0; i < 2 * NC * NTG; ++i)
 #pragma unroll
-      for (int rr = 0; rr < 16; ++rr) acc[i / (2 * NC)][(i >> 1) % NC][i & 1][rr] = 0.f;
+      for (int rr = 0; rr < 16; ++rr) acc[i / (NTG * NC)][(i / NTG) % NC][i % NTG][rr] = 0.f;
   };
   zero_acc();
 
@@ -1006,7 +1041,51 @@ __global__ __launch_bounds__(512) void conv_wino_bx3_wide_kernel(ConvArgs a, int
         [[maybe_unused]] float unused_out;
         if (a_next && next_g.b != cur_g.b) hx_scales_of(next_g.b, hx_in, unused_out);   // this chunk stages chunk 0 of the NEXT tile (its image's scale)
       }
-      if constexpr (WPRIV) {
+      if constexpr (HALF) {
+        // the WPRIV chunk below with one patch per thread and two MFMA steps (positions p0, p0+1; six MFMAs each): the patch's
+        // transform and the trade between the half-waves lie under step 0, the split and the packed stores under step 1
+        uint4 bsh[2][2];
+        float va[16], vp[8][2];
+        __builtin_amdgcn_s_waitcnt(0x0F74);                     // vmcnt(4): everything but position p0+1's fragments
+        read_patch_to(va, h);
+        load_Bh(bsh[0], cur, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_waitcnt(0xC07F);                     // lgkmcnt(0): the patch is in registers
+        IPDM_TR(5);
+        issue_dma(dma_chunk);
+        __builtin_amdgcn_sched_barrier(0);
+        static_for<2>([&](auto sc) {
+          constexpr int pi = decltype(sc)::value;
+          if constexpr (pi == 0) {
+            load_Bh(bsh[1], cur, 1, 0);
+            transform(va);
+            trade_halves(va, vp);
+          } else {
+            store_half(nxt, vp);
+            load_A(afr[0], p0, a_chunk, a_cot);
+          }
+          const f16x8 bh = __builtin_bit_cast(f16x8, bsh[pi][0]), bl = __builtin_bit_cast(f16x8, bsh[pi][1]);
+#pragma unroll
+          for (int c = 0; c < NC; ++c) {
+            f32x16 v = acc[pi][c][0];
+            v = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, afr[pi][c][1]), bh, v, 0, 0, 0);
+            v = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, afr[pi][c][0]), bl, v, 0, 0, 0);
+            v = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, afr[pi][c][0]), bh, v, 0, 0, 0);
+            acc[pi][c][0] = v;
+          }
+          if constexpr (pi == 0) __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);    // next step's operand reads first
+          if constexpr (pi == 1) __builtin_amdgcn_sched_group_barrier(0x020, 4, 0);    // ... and the fragment requests
+#pragma unroll
+          for (int i = 0; i < 6; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x006, pi == 0 ? 10 : 8, 0);
+            if constexpr (pi == 1) __builtin_amdgcn_sched_group_barrier(0x200, 3, 0);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+          IPDM_TR(1 + pi);
+        });
+        load_A(afr[1], p0 + 1, a_chunk, a_cot);
+      } else if constexpr (WPRIV) {
         // this wave's DMA of chunk c+1 (issued a chunk ago) and the fragments of position p0 have landed: fragments of position
         // p0+1 first (older than the next DMA in the in-order vmcnt queue), the wave's own patches into registers, and at once
         // the DMA of chunk c+2 into the block just read -- no barrier: nobody else reads it.  Transform / split / packed stores
@@ -1226,10 +1305,16 @@ __global__ __launch_bounds__(512) void conv_wino_bx3_wide_kernel(ConvArgs a, int
     [[maybe_unused]] auto boff = [&](int c, int tg, int i, int ii) -> unsigned {
       return 4u * (unsigned)((c * 32 + i) * (oH * oW) + (rstep * (tg * 32 / TX) + ii) * oW) + eoff4;
     };
+    const size_t poly_base = ((size_t)cur_g.b * a.Cout + co0) * HW;    // (scalar) + a 32-bit per-thread element offset
+    // (opaque per tile pass, like eoff4 above: the output indices depend on the thread alone, so hipcc computed them once per launch
+    //  and carried them across the chunk loop in scratch -- 56 spilled registers, 76 with the cheaper tile_origin, 29 with this; the
+    //  epilogue 38.8 / 44.3 / 27.3 k cycles at d = 2, and every chunk ~6 % shorter)
+    [[maybe_unused]] int etile_p = etile;
+    if constexpr (POLY) asm volatile("" : "+v"(etile_p));
     auto out_index = [&](int c, int tg, int i, int ii) -> size_t {   // POLY only: element index of the row's first output; second: + d
       int py, px;
-      tile_origin(tg * 32 + etile, py, px);
-      return ((size_t)cur_g.b * a.Cout + co0 + c * 32 + ecg * 2 + i) * HW + (size_t)(py + pd * ii) * a.W + px;
+      tile_origin(tg * 32 + etile_p, py, px);
+      return poly_base + (unsigned)((c * 32 + ecg * 2 + i) * HW + (py + pd * ii) * a.W + px);
     };
     auto in_range = [&](int tg) {
       if constexpr (POLY) return true;                          // exactly 64 tiles per image
@@ -1246,7 +1331,7 @@ __global__ __launch_bounds__(512) void conv_wino_bx3_wide_kernel(ConvArgs a, int
     [[maybe_unused]] char* const act_b = reinterpret_cast<char*>(a.out_act) + tile_base;
     auto prefetch = [&](auto rc) {
       constexpr int rnd = decltype(rc)::value;
-      constexpr int c = rnd >> 1, tg = rnd & 1, bf = AHEAD ? rnd & 1 : 0;
+      constexpr int c = rnd / NTG, tg = rnd % NTG, bf = AHEAD ? rnd & 1 : 0;
       const bool res_ok = has_res && in_range(tg);
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
@@ -1278,9 +1363,9 @@ __global__ __launch_bounds__(512) void conv_wino_bx3_wide_kernel(ConvArgs a, int
     }
     if constexpr (AHEAD) prefetch(std::integral_constant<int, 0>{});
     [[maybe_unused]] float amx_o = 0.f, amx_a = 0.f;            // max |stored value| of this thread over the tile pass
-    static_for<2 * NC>([&](auto rc) {
+    static_for<NTG * NC>([&](auto rc) {
       constexpr int rnd = decltype(rc)::value;
-      constexpr int c = rnd >> 1, tg = rnd & 1, bf = AHEAD ? rnd & 1 : 0;
+      constexpr int c = rnd / NTG, tg = rnd % NTG, bf = AHEAD ? rnd & 1 : 0;
       if constexpr (!AHEAD) prefetch(rc);
 #pragma unroll
       for (int pi = 0; pi < 2; ++pi)
@@ -1293,7 +1378,7 @@ __global__ __launch_bounds__(512) void conv_wino_bx3_wide_kernel(ConvArgs a, int
       IPDM_TE(1 + 4 * rnd);
       __syncthreads();
       IPDM_TE(2 + 4 * rnd);
-      if constexpr (AHEAD && rnd < 2 * NC - 1) prefetch(std::integral_constant<int, rnd + 1>{});
+      if constexpr (AHEAD && rnd < NTG * NC - 1) prefetch(std::integral_constant<int, rnd + 1>{});
       constexpr int NSV = POOL ? 1 : 4;
       [[maybe_unused]] float sv[2][NSV];                      // STATS: this thread's stored values of the round
       if constexpr (STATS) {
@@ -1518,6 +1603,27 @@ bool x_co32(const ConvArgs& a) {
          a.Cout < 512 && !a.pool2 && !a.stats;
 }
 
+// ... and of those the 16 x 16 images as (image, upper / lower eight rows, 64 channels) workgroups (HALF): the same count of
+// workgroups, one patch per thread and chunk instead of two (IPDM_WBX3_HALF=0: off, i.e. CO32; a function of the layer shape only)
+bool x_half(const ConvArgs& a) {
+  static int enabled = -1;
+  if (enabled < 0) {
+    const char* e = getenv("IPDM_WBX3_HALF");
+    enabled = e ? atoi(e) : 1;
+  }
+  return enabled && x_co32(a) && a.W == 16 && a.H == 16;
+}
+
+// hipFuncAttributeMaxDynamicSharedMemorySize is a per-device attribute: set once per (kernel, device)
+template <typename K>
+void set_max_lds_once(K kernel, bool (&done)[64]) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+  if (done[dev]) return;
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, X_LDS_BYTES);
+  done[dev] = true;
+}
+
 int wino_persist() {                             // IPDM_WBX3_PERSIST=0: one workgroup per tile (tuning / fallback)
   static int persist = -1;
   if (persist < 0) {
@@ -1569,12 +1675,8 @@ static int conv_wino_bx3_launch_t(ConvArgs a, hipStream_t s) {
     a.tiles_x = a.tiles_y = 1;
     a.co_tiles = a.Cout / X_CO;
     const int64_t nblk = (int64_t)a.B * a.co_tiles;
-    static bool poly_attr = false;
-    if (!poly_attr) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wino_bx3_wide_kernel<HXV, 8, 8, true, true, false, false, false, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, X_LDS_BYTES);
-      poly_attr = true;
-    }
+    static bool poly_attr[64] = {};
+    set_max_lds_once(conv_wino_bx3_wide_kernel<HXV, 8, 8, true, true, false, false, false, true>, poly_attr);
     const int per_xcd = (int)((nblk + 7) / 8);
     const int S = per_xcd < cus_per_xcd() ? per_xcd : cus_per_xcd();
     hipLaunchKernelGGL((conv_wino_bx3_wide_kernel<HXV, 8, 8, true, true, false, false, false, true>), dim3((unsigned)(8 * S)),
@@ -1583,17 +1685,27 @@ static int conv_wino_bx3_launch_t(ConvArgs a, hipStream_t s) {
   }
   const bool small = x_small(a);
   if (HXV && small && wino_persist() && x_co32(a) && (reinterpret_cast<uintptr_t>(a.x) & 15) == 0) {
+    if (x_half(a)) {
+      a.tiles_x = 1;
+      a.tiles_y = 2;
+      a.co_tiles = a.Cout / X_CO;
+      const int64_t nblk = (int64_t)a.B * 2 * a.co_tiles;
+      if (nblk > 0x7fffffff) return IPDM_EUNSUPPORTED;
+      static bool half_attr[64] = {};
+      set_max_lds_once(conv_wino_bx3_wide_kernel<true, 8, 4, true, true, false, false, false, false, false, true>, half_attr);
+      const int per_xcd = (int)((nblk + 7) / 8);
+      const int S = per_xcd < cus_per_xcd() ? per_xcd : cus_per_xcd();
+      hipLaunchKernelGGL((conv_wino_bx3_wide_kernel<true, 8, 4, true, true, false, false, false, false, false, true>), dim3((unsigned)(8 * S)),
+                         dim3(512), X_LDS_BYTES, s, a, (int)nblk);
+      return ipdm_launch_status();
+    }
     a.tiles_x = (a.W + 15) / 16;
     a.tiles_y = (a.H + 15) / 16;
     a.co_tiles = a.Cout / 32;
     const int64_t nblk = (int64_t)a.B * a.tiles_x * a.tiles_y * a.co_tiles;
     if (nblk > 0x7fffffff) return IPDM_EUNSUPPORTED;
-    static bool co32_attr = false;
-    if (!co32_attr) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wino_bx3_wide_kernel<true, 8, 8, true, true, false, false, false, false, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, X_LDS_BYTES);
-      co32_attr = true;
-    }
+    static bool co32_attr[64] = {};
+    set_max_lds_once(conv_wino_bx3_wide_kernel<true, 8, 8, true, true, false, false, false, false, true>, co32_attr);
     const int per_xcd = (int)((nblk + 7) / 8);
     const int S = per_xcd < cus_per_xcd() ? per_xcd : cus_per_xcd();
     hipLaunchKernelGGL((conv_wino_bx3_wide_kernel<true, 8, 8, true, true, false, false, false, false, true>), dim3((unsigned)(8 * S)),
@@ -1816,6 +1928,18 @@ extern "C" int ipdm_conv2d_wino_bx3_splitk(int Cin, int Cout, int H, int W, int 
   a.coef = nullptr; a.act = IPDM_ACT_NONE; a.dil = dilation; a.D = 1; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W; a.B = 1;
   if (!wino_bx3_ok(a, 3)) return 1;
   return wino_bx3_ksplit_for(Cin, Cout, H, W, dilation);
+}
+
+/* the instantiation the f16x2 plain call runs for a layer shape (IPDM_WINO_FORM_*, include/ipdm.h; 16-byte aligned input, plain
+ * epilogue; a function of the layer shape and the IPDM_WBX3_* switches only) */
+extern "C" int ipdm_conv2d_wino_hx2_form(int Cin, int Cout, int H, int W, int dilation) {
+  ConvArgs a;
+  a.x = nullptr; a.coef = nullptr; a.act = IPDM_ACT_NONE; a.dil = dilation; a.D = 1; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W;
+  a.B = 1; a.hx = 1; a.pool2 = 0; a.stats = nullptr;
+  if (Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || dilation < 1 || !wino_bx3_ok(a, 3)) return IPDM_EUNSUPPORTED;
+  if (x_poly(a)) return IPDM_WINO_FORM_POLY;
+  if (x_small(a) && wino_persist() && x_co32(a)) return x_half(a) ? IPDM_WINO_FORM_HALF : IPDM_WINO_FORM_CO32;
+  return IPDM_WINO_FORM_OTHER;
 }
 
 static int wino_bx3_splitk_entry(const float* x, const void* U, const float* bias, const float* residual, float* out,

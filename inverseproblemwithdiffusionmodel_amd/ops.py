@@ -1465,7 +1465,8 @@ def conv2d_wino_bx3(x, U, bias=None, residual=None, act_out=ACT_NONE, raw=True, 
 
 
 # f16x2 family: the 16-pixel layers whose split-K rule says "two K halves" run as ONE launch of 32-channel workgroups instead
-# (conv_wino_bx3.hip: CO32; -0.35 % per iteration and 28 reduction launches fewer; 0: the split-K form)
+# (conv_wino_bx3.hip: CO32, and for 16 x 16 images HALF -- the native launcher's choice, ops.wino_hx2_form; -0.35 % per iteration and
+# 28 reduction launches fewer; 0: the split-K form)
 WBX3_CO32 = os.environ.get("IPDM_WBX3_CO32", "1") != "0"
 
 
@@ -1487,6 +1488,16 @@ def wino_bx3_pays(Cin, Cout, H, W, dilation=1, B=None):
 def wino_bx3_splitk(Cin, Cout, H, W, dilation=1):
     """K parts of the Winograd launch for this layer shape (1 = plain launch); never a function of the batch"""
     return int(_lib.lib.ipdm_conv2d_wino_bx3_splitk(int(Cin), int(Cout), int(H), int(W), int(dilation)))
+
+
+WINO_FORM_OTHER, WINO_FORM_CO32, WINO_FORM_HALF, WINO_FORM_POLY = 0, 1, 2, 3      # include/ipdm.h IPDM_WINO_FORM_*
+
+
+def wino_hx2_form(Cin, Cout, H, W, dilation=1):
+    """the instantiation the f16x2 family's plain Winograd call runs for this layer shape (WINO_FORM_*; the native rule, a
+    function of the shape only); None where the kernel does not apply"""
+    f = int(_lib.lib.ipdm_conv2d_wino_hx2_form(int(Cin), int(Cout), int(H), int(W), int(dilation)))
+    return None if f < 0 else f
 
 
 def wino_bx3_max_batch(Cin, H, W, dilation=1):
