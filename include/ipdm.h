@@ -13,6 +13,16 @@
  *
  * Layouts: images are NCHW planar, row-major, float32.  Complex data is interleaved (re, im)
  * float32 pairs ("c64"), the memory layout of torch.complex64 / numpy.complex64.
+ *
+ * Alignment: every tensor argument may be any contiguous buffer on its element's natural boundary (4 bytes for float32, 8 for
+ * c64 and int64 / double, 2 for half); 16-byte alignment only selects faster kernel forms, never a different result beyond
+ * rounding order.  No entry answers a misaligned tensor with IPDM_EINVAL.  Exceptions, answered with IPDM_EUNSUPPORTED (the
+ * caller takes its other path, as for an unsupported shape): ipdm_conv3x3_thin_f32 and the 1-D Winograd entries
+ * (ipdm_conv2d_wino1d_*, ipdm_conv3d_wino1d_f32) need `x` on 16 bytes; the Winograd entries whose epilogue moves pairs of columns
+ * (ipdm_conv2d_wino_f32, ipdm_conv2d_wino_{bx3,hx2}_f32 and _stats_f32 -- the pooled form included, for one rule per entry --
+ * and the 1-D ones) need `residual`, `out` and `out_act` on 8 bytes; the split-K entries (ipdm_conv2d_wino_*_splitk_f32) finish
+ * in a scalar reduction and take them at any alignment.  Packed weight blobs come from the pack functions into 16-byte aligned
+ * buffers and are not covered by the relaxation.
  */
 #ifndef IPDM_H
 #define IPDM_H

@@ -143,6 +143,6 @@ extern "C" int ipdm_conv2d_wino_f32(const float* x, const float* U, const float*
   a.x = x; a.wt = U; a.bias = bias; a.coef = nullptr; a.residual = residual; a.out = out; a.out_act = out_act;
   a.act_out = act_out; a.B = B; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W; a.dil = dilation; a.act = IPDM_ACT_NONE;
   a.D = 1; a.kd = 1; a.tiles_x = a.tiles_y = a.co_tiles = 0; a.dbg = g_wino_dbg; a.dbg = g_wino_dbg;
-  if (!wino_ok(a, 3)) return IPDM_EUNSUPPORTED;
+  if (!wino_ok(a, 3) || !wino_pairs_aligned(a)) return IPDM_EUNSUPPORTED;
   return conv_wino_launch(a, ipdm_stream(stream));
 }

@@ -546,6 +546,12 @@ int conv_cfg_128x128s(const ConvArgs& a, int ks, hipStream_t s);   // <2,2,2,2,1
 unsigned long long* conv_debug_stamps();   // conv.hip: buffer set by ipdm_debug_set_stamp_buffer (NULL = off)
 
 // Winograd F(2x2,3x3) path (conv_wino.hip)
+// the Winograd epilogues (2-D and 1-D) fetch the residual and store both outputs as pairs of columns: those three pointers must
+// sit on 8-byte boundaries (rows are even, so every pair then does).  A launcher answers anything else with "unsupported";
+// the host front end hands these kernels fresh (aligned) outputs and re-homes a misaligned residual.
+inline bool wino_pairs_aligned(const ConvArgs& a) {
+  return ((reinterpret_cast<uintptr_t>(a.residual) | reinterpret_cast<uintptr_t>(a.out) | reinterpret_cast<uintptr_t>(a.out_act)) & 7) == 0;
+}
 bool wino_ok(const ConvArgs& a, int ks);
 int conv_wino_launch(ConvArgs a, hipStream_t s);
 int conv_wino_weights(const float* w, float* U, int Cout, int Cin, hipStream_t s);

@@ -805,7 +805,7 @@ static int wino1d_entry(const float* x, const void* U, const float* bias, const 
   a.stats = stats;
   a.pool2 = pool2 ? 1 : 0;
   conv_apply_ext(a, ext, 1);
-  if (!wino1d_ok(a)) return IPDM_EUNSUPPORTED;
+  if (!wino1d_ok(a) || !wino_pairs_aligned(a)) return IPDM_EUNSUPPORTED;
   return conv_wino1d_launch(a, ipdm_stream(stream));
 }
 
@@ -923,6 +923,6 @@ extern "C" int ipdm_conv3d_wino1d_f32(const float* x, const void* U, const float
   a.D = D; a.kd = 3; a.tiles_x = a.tiles_y = a.co_tiles = 0; a.dbg = conv_debug_stamps();
   a.hx = 1;
   conv_apply_ext(a, ext, 1);
-  if (!wino1d_vol_ok(a)) return IPDM_EUNSUPPORTED;
+  if (!wino1d_vol_ok(a) || !wino_pairs_aligned(a)) return IPDM_EUNSUPPORTED;
   return conv_wino1d_vol_launch(a, ipdm_stream(stream));
 }

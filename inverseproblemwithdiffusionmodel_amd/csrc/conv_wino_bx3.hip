@@ -1910,7 +1910,7 @@ static int wino_bx3_entry(const float* x, const void* U, const float* bias, cons
   a.stats = stats;
   a.hx = hx;
   conv_apply_ext(a, ext, hx);
-  if (!wino_bx3_ok(a, 3)) return IPDM_EUNSUPPORTED;
+  if (!wino_bx3_ok(a, 3) || !wino_pairs_aligned(a)) return IPDM_EUNSUPPORTED;
   return conv_wino_bx3_launch(a, ipdm_stream(stream));
 }
 

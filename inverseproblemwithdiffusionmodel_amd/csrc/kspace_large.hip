@@ -270,16 +270,29 @@ __global__ __launch_bounds__(256) void langevin_planes_kernel(float* x_re, float
   }
   const int b = blockIdx.y;
   const int quads = HW / 4;                                    // HW is a multiple of 4 (power-of-two images)
+  // float4 access only where all the caller's planes sit on 16-byte boundaries; otherwise element by element (same
+  // arithmetic, same Philox quad per four elements)
+  const bool aligned = ((reinterpret_cast<uintptr_t>(x_re) | reinterpret_cast<uintptr_t>(x_im) | reinterpret_cast<uintptr_t>(g_re) |
+                         reinterpret_cast<uintptr_t>(g_im) | reinterpret_cast<uintptr_t>(n_re) | reinterpret_cast<uintptr_t>(n_im)) & 15) == 0;
   for (int q = blockIdx.x * 256 + threadIdx.x; q < quads; q += gridDim.x * 256) {
     const size_t gi = (size_t)b * HW + 4 * (size_t)q;
     float nr[4], ni[4];
+    if (!n_re) {
+      ipdm_philox_normal4(seed, sample_offset + b, step_id, 0, (uint32_t)q, nr);
+      ipdm_philox_normal4(seed, sample_offset + b, step_id, 1, (uint32_t)q, ni);
+    }
+    if (!aligned) {
+      for (int j = 0; j < 4; ++j) {
+        const float a = n_re ? n_re[gi + j] : nr[j], c = n_re ? n_im[gi + j] : ni[j];
+        x_re[gi + j] = x_re[gi + j] + step * g_re[gi + j] + a * noise_scale;
+        x_im[gi + j] = x_im[gi + j] + step * g_im[gi + j] + c * noise_scale;
+      }
+      continue;
+    }
     if (n_re) {
       const float4 a = *reinterpret_cast<const float4*>(n_re + gi), c = *reinterpret_cast<const float4*>(n_im + gi);
       nr[0] = a.x; nr[1] = a.y; nr[2] = a.z; nr[3] = a.w;
       ni[0] = c.x; ni[1] = c.y; ni[2] = c.z; ni[3] = c.w;
-    } else {
-      ipdm_philox_normal4(seed, sample_offset + b, step_id, 0, (uint32_t)q, nr);
-      ipdm_philox_normal4(seed, sample_offset + b, step_id, 1, (uint32_t)q, ni);
     }
     float4 xr = *reinterpret_cast<float4*>(x_re + gi), xi = *reinterpret_cast<float4*>(x_im + gi);
     const float4 gr = *reinterpret_cast<const float4*>(g_re + gi), gim = *reinterpret_cast<const float4*>(g_im + gi);

@@ -18,13 +18,17 @@ __global__ __launch_bounds__(256) void langevin_kernel(float* x, const float* __
   }
   // one thread per quad of elements inside a sample; samples on blockIdx.y
   const int64_t quads = (sample_elems + 3) / 4;
+  // the float4 form needs every pointer it touches on a 16-byte boundary (the caller's tensors are only known to be
+  // contiguous); otherwise the scalar form below, same arithmetic per element
+  const bool aligned = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(g) |
+                         (PHILOX ? uintptr_t(0) : reinterpret_cast<uintptr_t>(noise))) & 15) == 0;
   for (int64_t smp = blockIdx.y; smp < n_samples; smp += gridDim.y) {
     for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < quads; q += (int64_t)gridDim.x * blockDim.x) {
       float nz[4];
       const int64_t base = smp * sample_elems + q * 4;
       const int cnt = (int)((sample_elems - q * 4) < 4 ? (sample_elems - q * 4) : 4);
       if constexpr (PHILOX) ipdm_philox_normal4(seed, sample_offset + smp, step_id, 0, (uint32_t)q, nz);
-      const bool vec = cnt == 4 && ((base & 3) == 0);
+      const bool vec = aligned && cnt == 4 && ((base & 3) == 0);
       if (vec) {
         float4 xv = *reinterpret_cast<const float4*>(x + base);
         float4 gv = *reinterpret_cast<const float4*>(g + base);

@@ -233,7 +233,8 @@ __global__ __launch_bounds__(256) void affine_act_kernel(const float* x, const f
   const float mu = coef[plane * 3], sc = coef[plane * 3 + 1], sh = coef[plane * 3 + 2];
   const float* p = x + plane * HW;
   float* o = y + plane * HW;
-  if ((HW & 3) == 0) {
+  // float4 rows only on 16-byte boundaries (a contiguous view into a larger buffer need not start on one)
+  if ((HW & 3) == 0 && ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(o)) & 15) == 0) {
     for (int i = blockIdx.x * 256 + threadIdx.x; i < HW / 4; i += gridDim.x * 256) {
       float4 v = reinterpret_cast<const float4*>(p)[i];
       v.x = ipdm_act((v.x - mu) * sc + sh, act);
@@ -258,7 +259,8 @@ __global__ __launch_bounds__(256) void affine_act_cat_kernel(const float* x1, in
   const float mu = coef[plane * 3], sc = coef[plane * 3 + 1], sh = coef[plane * 3 + 2];
   const float* p = c < C1 ? x1 + (b * C1 + c) * HW : x2 + (b * C2 + (c - C1)) * HW;
   float* o = y + plane * HW;
-  if ((HW & 3) == 0) {
+  // float4 rows only on 16-byte boundaries (a contiguous view into a larger buffer need not start on one)
+  if ((HW & 3) == 0 && ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(o)) & 15) == 0) {
     for (int i = blockIdx.x * 256 + threadIdx.x; i < HW / 4; i += gridDim.x * 256) {
       float4 v = reinterpret_cast<const float4*>(p)[i];
       v.x = ipdm_act((v.x - mu) * sc + sh, act);
@@ -495,14 +497,21 @@ __global__ __launch_bounds__(256) void affine_avgpool5_kernel(const float* __res
 __global__ __launch_bounds__(256) void meanpool2_kernel(const float* __restrict__ x, float* __restrict__ y, int64_t n_out,
                                                         int H, int W) {
   const int OH = H / 2, OW = W / 2;
+  const bool pairs = (reinterpret_cast<uintptr_t>(x) & 7) == 0;     // W is even: every window row then sits on 8 bytes
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_out; i += (int64_t)gridDim.x * 256) {
     int ox = (int)(i % OW);
     int64_t t = i / OW;
     int oy = (int)(t % OH);
     int64_t plane = t / OH;
     const float* p = x + (plane * H + 2 * oy) * (int64_t)W + 2 * ox;
-    float2 top = *reinterpret_cast<const float2*>(p);
-    float2 bot = *reinterpret_cast<const float2*>(p + W);
+    float2 top, bot;
+    if (pairs) {
+      top = *reinterpret_cast<const float2*>(p);
+      bot = *reinterpret_cast<const float2*>(p + W);
+    } else {
+      top = make_float2(p[0], p[1]);
+      bot = make_float2(p[W], p[W + 1]);
+    }
     y[i] = (((top.x + bot.x) + top.y) + bot.y) / 4.0f;     // the reference's summation order
   }
 }

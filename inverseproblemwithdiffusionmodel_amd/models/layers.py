@@ -86,7 +86,7 @@ class Conv(ops.PackedWeightMixin, nn.Module):
         if bias_rows is not None:
             bias = bias_rows
         if (self.kernel_size == 3 and self.dilation == 1 and residual is None and min(self.in_planes, self.out_planes) <= 3
-                and ops.conv3x3_thin_ok(self.in_planes, self.out_planes, x.shape[2], x.shape[3])):
+                and ops.conv3x3_thin_ok(self.in_planes, self.out_planes, x.shape[2], x.shape[3], x)):
             return ops.conv3x3_thin(x, self.weight.data, bias)         # first / last layer: streaming kernels
         if (ops.impl_unbounded() in ops.SPLIT_IMPLS and self.kernel_size == 3
                 and ops.wino_bx3_pays(self.in_planes, self.out_planes, x.shape[2], x.shape[3], self.dilation)):

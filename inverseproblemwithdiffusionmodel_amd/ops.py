@@ -891,9 +891,22 @@ def conv_wino_supported(Cin, Cout, H, W, dilation=1):
     return bool(_lib.lib.ipdm_conv2d_wino_supported(Cin, Cout, H, W, dilation))
 
 
+def _wino_residual(residual):
+    """residual of a Winograd launch (2-D and 1-D kernels): their epilogues fetch it as pairs of columns, so it must start on
+    an 8-byte boundary.  A contiguous view at 4 bytes past one (a legal argument) is COPIED to a fresh tensor here -- a read-only
+    operand, the copy is never written -- so the same kernel runs and the result's bits do not depend on where the caller's
+    residual happened to lie; the native entries answer such a pointer with IPDM_EUNSUPPORTED."""
+    if residual is None:
+        return None
+    residual = _gpu(residual, torch.float32, "residual")
+    return residual.clone() if residual.data_ptr() % 8 else residual
+
+
 def conv2d_wino(x, U, bias=None, residual=None, act_out=ACT_NONE, raw=True, dilation=1):
-    """3x3 / dilation-1 convolution through the Winograd F(2x2,3x3) kernel (same output options as conv2d)"""
+    """3x3 / dilation-1 convolution through the Winograd F(2x2,3x3) kernel (same output options as conv2d).
+    A residual that does not start on an 8-byte boundary is copied first (_wino_residual: the epilogue fetches pairs)."""
     x = _gpu(x, torch.float32, "x")
+    residual = _wino_residual(residual)
     B, Cin, H, W = x.shape
     Cout = U.shape[2]
     want_act = act_out != ACT_NONE
@@ -1007,14 +1020,19 @@ def conv2d(x, wt, bias=None, coef=None, act=ACT_NONE, residual=None, dilation=1,
 USE_THIN_CONV = os.environ.get("IPDM_THIN_CONV", "1") != "0"
 
 
-def conv3x3_thin_ok(Cin, Cout, H, W):
-    """3x3, dilation 1, no fused input norm / residual / second output, and a thin side: the streaming kernels"""
+def conv3x3_thin_ok(Cin, Cout, H, W, x=None):
+    """3x3, dilation 1, no fused input norm / residual / second output, and a thin side: the streaming kernels.
+    x: the tensor the layer is about to read -- the kernels move float4 rows, so an input off a 16-byte boundary (a contiguous
+    view into a larger buffer) is not theirs; the caller's next branch (the matrix-core kernels) takes it"""
+    if x is not None and x.data_ptr() % 16:
+        return False
     return USE_THIN_CONV and bool(_lib.lib.ipdm_conv3x3_thin_supported(int(Cin), int(Cout), int(H), int(W)))
 
 
 def conv3x3_thin(x, weight, bias=None, coef=None):
     """first / last layer of a score network: x [B,Cin,H,W], weight [Cout,Cin,3,3] (the reference's layout), Cin <= 3 or
-    Cout <= 3; coef [B,Cin,3]: input affine (x - c0) * c1 + c2 inside the image (Cin <= 3 form)"""
+    Cout <= 3; coef [B,Cin,3]: input affine (x - c0) * c1 + c2 inside the image (Cin <= 3 form).
+    Raises IpdmUnsupported for a shape outside conv3x3_thin_ok() and for an x that is not 16-byte aligned."""
     x = _gpu(x, torch.float32, "x")
     weight = _gpu(weight, torch.float32, "weight")
     B, Cin, H, W = x.shape
@@ -1284,7 +1302,8 @@ def conv_wino1d_weight3d(w):
 
 
 def conv3d_wino1d(x, U, bias=None, residual=None, act_out=ACT_NONE, raw=True, in_amax=None, want_amax=False, res_second=False):
-    """3x3x3 'same' convolution of x [B, Cin, D, H, W] on the 1-D Winograd kernel (same output options as conv3d)"""
+    """3x3x3 'same' convolution of x [B, Cin, D, H, W] on the 1-D Winograd kernel (same output options as conv3d).
+    A residual that does not start on an 8-byte boundary is copied first (_wino_residual: the epilogue fetches pairs)."""
     x = _gpu(x, torch.float32, "x")
     B, Cin, D, H, W = x.shape
     if U.kk != 36 or U.Cin != Cin:
@@ -1294,6 +1313,7 @@ def conv3d_wino1d(x, U, bias=None, residual=None, act_out=ACT_NONE, raw=True, in
     Cout = U.Cout
     if residual is not None and tuple(residual.shape) != (B, Cout, D, H, W):
         raise ValueError(f"conv3d_wino1d: residual {tuple(residual.shape)} != output {(B, Cout, D, H, W)}")
+    residual = _wino_residual(residual)
     amax_t = None
     if in_amax is not None:
         amax_t = absmax_per_image(x) if in_amax is True else in_amax
@@ -1362,7 +1382,9 @@ def conv2d_wino_bx3(x, U, bias=None, residual=None, act_out=ACT_NONE, raw=True, 
     pool2: the ConvMeanPool form -- outputs (and the residual) are [B, Cout, H/2, W/2] 2x2 means of the convolution;
     raises IpdmUnsupported where the pooled epilogue is not built (small / odd images).
     want_stats: the result feeds an InstanceNorm++ -- where the statistics epilogue exists for this shape, its partials
-    [B, Cout, P, 3] are hung on the raw result as `_ipdm_partials` (instnorm_plus_coef picks them up)."""
+    [B, Cout, P, 3] are hung on the raw result as `_ipdm_partials` (instnorm_plus_coef picks them up).
+    x may be any contiguous tensor (off a 16-byte boundary: the dword-staged forms, no statistics epilogue, no split-K).
+    A residual that does not start on an 8-byte boundary is copied first (_wino_residual: the epilogue fetches pairs)."""
     x = _gpu(x, torch.float32, "x")
     B, Cin, H, W = x.shape
     amax_t = None
@@ -1404,6 +1426,7 @@ def conv2d_wino_bx3(x, U, bias=None, residual=None, act_out=ACT_NONE, raw=True, 
     oh, ow = (H // 2, W // 2) if pool2 else (H, W)
     if residual is not None and tuple(residual.shape) != (B, Cout, oh, ow):
         raise ValueError(f"conv2d_wino_bx3: residual {tuple(residual.shape)} != output {(B, Cout, oh, ow)}")
+    residual = _wino_residual(residual)
     out = torch.empty((B, Cout, oh, ow), dtype=torch.float32, device=x.device) if raw else None
     out_act = torch.empty((B, Cout, oh, ow), dtype=torch.float32, device=x.device) if want_act else None
     if CONV_TRACE is not None:

@@ -806,6 +806,15 @@ def test_conv3x3_thin_unsupported(ops):
     w = torch.randn(16, 16, 3, 3).cuda()
     with pytest.raises(_lib.IpdmUnsupported):
         ops.conv3x3_thin(x, w)
+    # a supported shape on a contiguous input that is not 16-byte aligned (a view into a larger buffer): the float4-row kernels
+    # have no form for it -- "unsupported" (the layers fall through to the matrix-core kernels), never "invalid argument"
+    buf = torch.randn(2 * 1 * 8 * 8 + 8).cuda()
+    for k in (1, 2, 3):
+        xm = buf[k:k + 128].view(2, 1, 8, 8)
+        assert xm.is_contiguous() and xm.data_ptr() % 16 == 4 * k
+        assert ops.conv3x3_thin_ok(1, 16, 8, 8) and not ops.conv3x3_thin_ok(1, 16, 8, 8, xm)
+        with pytest.raises(_lib.IpdmUnsupported):
+            ops.conv3x3_thin(xm, torch.randn(16, 1, 3, 3).cuda())
 
 
 # ---- MFMA convolution ---------------------------------------------------------------------------
