@@ -523,6 +523,33 @@ int ipdm_cond_instnorm_plus_coef_partials_f32(const float* partials, int P, cons
                                               void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * 1-D convolution of [N][C][L] sequences on the f16x2 arithmetic (conv1d.hip) -- the temporal score networks NCSN1D*
+ * (reference: ncsn/models/layers1d.py:28-60 conv1x1 / conv3x3 / dilated_conv3x3 as nn.Conv1d, :63-84 CRPBlock, :113-135
+ * RCUBlock, :166-187 MSFBlock, :296-324 ConvMeanPool, :415-470 ResidualBlock; ncsn/models/ncsn1d.py:53-56 begin / end
+ * convolutions).  y[n][co][t] = bias[co] + sum_{ci,j} w[co][ci][j] x[n][ci][t + (j - k/2) * dilation], zero padding, k = 1 or 3,
+ * dilation 1 / 2 / 4.  Served shapes (ipdm_conv1d_hx2_supported; IPDM_EUNSUPPORTED otherwise -- the caller then runs the
+ * (N, C, 1, L) view on ipdm_conv2d_hx2_f32 with the filter in the middle row of a 3 x 3 one, which is the same convolution):
+ * Cin % 16 == 0, Cout % 64 == 0, L >= 12 dividing 96.  x, residual, out, out_act at any 4-byte alignment.
+ *   ext->in_amax: maxima vector with one slot per SEQUENCE (dynamic range: one power-of-two input scale per sequence);
+ *   ext->out_amax / act_amax: per-sequence maxima of what is stored; ext->res_second as in ipdm_conv_ext_t; bias_bstride and
+ *   out_scale are not served.  pool2 != 0: ConvMeanPool (layers1d.py:319-324) in one launch -- out / out_act / residual are
+ *   [N][Cout][L/2] and hold (y[2j] + y[2j+1]) / 2 (+ residual, activation).  A sequence's result does not depend on N or on
+ *   its position in the batch. */
+int ipdm_conv1d_hx2_supported(int Cin, int Cout, int L, int k, int dilation);
+int64_t ipdm_conv1d_hx2_weight_bytes(int Cout, int Cin, int k);
+int ipdm_conv1d_hx2_pack_weight(const float* w /* [Cout][Cin][k] */, void* packed, int Cout, int Cin, int k, void* stream);
+int ipdm_conv1d_hx2_f32(const float* x, const void* packed, const float* bias, const float* residual, float* out,
+                        float* out_act, int act_out, int N, int Cin, int Cout, int L, int k, int dilation, int pool2,
+                        const ipdm_conv_ext_t* ext, void* stream);
+/* the pair mean on its own (layers1d.py:324; the kernel_size = 1 shortcut pools before its convolution):
+ * y[row][j] = (x[row][2j] + x[row][2j+1]) / 2, L even */
+int ipdm_meanpool1d2_f32(const float* x, float* y, int rows, int L, void* stream);
+/* y = a * x + b with the per-image maxima of y (amax_out: a maxima vector ZEROED by the caller) -- the input rescale
+ * `2 * x - 1` of ncsn/models/ncsn1d.py:104-108 as a producer of the first convolution's in_amax */
+int ipdm_scale_shift_amax_f32(const float* x, float* y, float* amax_out, int n_images, int64_t per_image, float a, float b,
+                              void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Segmentation-likelihood guidance (reference: ncsn/models/__init__.py:197-215 compute_seg_grad through a MONAI UNet --
  * stride-2 Convolution / transposed Convolution blocks with InstanceNorm + PReLU --, ALD_optimizers.py:272-286).
  * The strided (transposed) convolutions and their input-gradients run on ipdm_conv2d_bx3_f32 between these:

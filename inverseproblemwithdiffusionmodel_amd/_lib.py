@@ -121,6 +121,12 @@ SIGNATURES = {
     "ipdm_conv2d_wino_hx2_stats_f32": [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P],
     "ipdm_instnorm_plus_coef_partials_f32": [P, c_int, P, P, P, P, c_int, c_int, c_int, P, P],
     "ipdm_cond_instnorm_plus_coef_partials_f32": [P, c_int, P, P, c_int, c_int, P, c_int, c_int, c_int, P, P],
+    "ipdm_conv1d_hx2_supported": [c_int] * 5,
+    "ipdm_conv1d_hx2_weight_bytes": [c_int, c_int, c_int],
+    "ipdm_conv1d_hx2_pack_weight": [P, P, c_int, c_int, c_int, P],
+    "ipdm_conv1d_hx2_f32": [P, P, P, P, P, P, c_int] + [c_int] * 7 + [P, P],
+    "ipdm_meanpool1d2_f32": [P, P, c_int, c_int, P],
+    "ipdm_scale_shift_amax_f32": [P, P, P, c_int, c_int64, c_float, c_float, P],
     "ipdm_zero_insert2_f32": [P, P, c_int, c_int, c_int, P],
     "ipdm_subsample2_f32": [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P],
     "ipdm_in_prelu_fwd_f32": [P, P, P, P, P, c_int, c_int, c_float, P],
@@ -136,7 +142,8 @@ SIGNATURES = {
 }
 _RESTYPES = {"ipdm_build_arch": c_char_p, "ipdm_fft2c_workspace_bytes": c_int64, "ipdm_sense_workspace_bytes": c_int64, "ipdm_conv_bx3_weight_bytes": c_int64,
              "ipdm_conv_wino_bx3_weight_bytes": c_int64, "ipdm_conv_hx2_weight_bytes": c_int64,
-             "ipdm_conv_wino_hx2_weight_bytes": c_int64, "ipdm_conv_wino1d_weight_bytes": c_int64, "ipdm_conv_wino1d_weight_bytes3d": c_int64}
+             "ipdm_conv_wino_hx2_weight_bytes": c_int64, "ipdm_conv_wino1d_weight_bytes": c_int64, "ipdm_conv_wino1d_weight_bytes3d": c_int64,
+             "ipdm_conv1d_hx2_weight_bytes": c_int64}
 
 IPDM_EINVAL = -1
 IPDM_EUNSUPPORTED = -2

@@ -7,6 +7,7 @@ import torch
 
 from ..ncsn.models.ncsnv2 import NCSNv2, NCSNv2Deeper, NCSNv2Deepest
 from ..ncsn.models.ncsn3d import NCSN3DShallow
+from ..ncsn.models.ncsn1d import NCSN1D
 from ..ncsn.models.seg_unet import UNet
 
 # ncsn/configs/general_config.yml:1-6 of the reference ("Seg": the MONAI UNet arguments)
@@ -15,6 +16,7 @@ GENERAL_CONFIG = {"Seg": dict(spatial_dims=2, in_channels=1, out_channels=2, cha
 
 TASK_NAME_TO_MODEL_CTOR = {
     "Diffusion": NCSNv2Deepest,
+    "Diffusion1D": NCSN1D,
     "Diffusion3D": NCSN3DShallow,
     "DiffusionShallow": NCSNv2,
     "DiffusionDeeper": NCSNv2Deeper,
@@ -66,7 +68,7 @@ def reload_model(task_name, ds_name, mode="real-valued", ckpt_path=None, device=
                     sd[k] = torch.full_like(sd[k], 0.25)         # PReLU slope at its init value
             model.load_state_dict(sd, strict=False)
         return model.to(device).eval()
-    ds_cfg = ds_name + "_1D" if task_name == "Diffusion3D" and not ds_name.endswith("_1D") else ds_name
+    ds_cfg = ds_name + "_1D" if task_name in ("Diffusion1D", "Diffusion3D") and not ds_name.endswith("_1D") else ds_name
     config = load_config(ds_cfg, mode, device)
     model = TASK_NAME_TO_MODEL_CTOR[task_name](config)
     if ckpt_path is not None:

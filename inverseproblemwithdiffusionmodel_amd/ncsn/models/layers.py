@@ -62,7 +62,7 @@ class Conv2d(ops.PackedWeightMixin, nn.Module):
         """full_range: the layer reads a RAW network input through a fused input transform (begin_conv's `2x - 1`), whose range no
         producer bounds: on the f16x2 family it runs the three-piece bf16 kernels instead (the whole fp32 exponent range)"""
         super().__init__()
-        assert kernel_size in (1, 3) and ndim in (2, 3)
+        assert kernel_size in (1, 3) and ndim in (1, 2, 3)
         self.in_planes, self.out_planes, self.kernel_size, self.dilation = in_planes, out_planes, kernel_size, dilation
         self.ndim = ndim
         self.full_range = full_range
@@ -93,6 +93,20 @@ class Conv2d(ops.PackedWeightMixin, nn.Module):
                 and x.data_ptr() % 16 == 0 and (not ops.dynamic_range() or getattr(coef, "_ipdm_amax_bound", None) is not None)
                 and ops.wino1d_pays(self.in_planes, self.out_planes, x.shape[2], x.shape[3], self.dilation))
 
+    def packed_conv1d(self):
+        return self._cached("conv1d", ops.conv1d_weight)
+
+    def packed_rows(self):
+        """ndim = 1 on the direct 2-D kernels: the filter in the middle row of a 3 x 3 one (ops.conv1d_rows_weight)"""
+        if self.full_range and ops.CONV_IMPL == "hx2":
+            return self._cached("rows_bx3", lambda w: ops.conv1d_rows_weight(w, impl="bx3"))
+        return self._cached("rows_" + ops.CONV_IMPL, ops.conv1d_rows_weight)
+
+    def conv1d_ok(self, x):
+        """True when the 1-D kernel takes this layer (its shape alone decides: ops.conv1d_pays)"""
+        return (self.ndim == 1 and not self.full_range
+                and ops.conv1d_pays(self.in_planes, self.out_planes, x.shape[2], self.kernel_size, self.dilation))
+
     def packed(self):
         if self.full_range and ops.CONV_IMPL == "hx2":
             return self._cached("direct_bx3", lambda w: ops.conv_weight(w, impl="bx3"))
@@ -112,6 +126,16 @@ class Conv2d(ops.PackedWeightMixin, nn.Module):
         produce = dyn and feeds_conv
         if in_amax is None and dyn and coef is None and act == ops.ACT_NONE:
             in_amax = ops.in_amax_for(x)
+        if self.ndim == 1:
+            # (N, C, L) sequences (layers1d.py): the 1-D kernel where the layer shape is its, else the one-row image on the direct
+            # 2-D kernel -- a fused input (coef / act) is that kernel's too
+            if out is not None:
+                raise NotImplementedError("Conv2d(ndim=1): no `out=` form")
+            if coef is None and act == ops.ACT_NONE and self.conv1d_ok(x):
+                return ops.conv1d(x, self.packed_conv1d(), bias, residual, self.dilation, act_out=act_out, raw=raw,
+                                  in_amax=in_amax, want_amax=produce, res_second=res_second)
+            return ops.conv1d_rows(x, self.packed_rows(), bias, coef, act, residual, self.dilation, act_out=act_out, raw=raw,
+                                   in_amax=in_amax, want_amax=produce, res_second=res_second)
         if coef is not None and act == ops.ACT_ELU and out is None and self.fuses_input(x, coef):
             return ops.conv2d_wino_bx3(x, self.packed_wino1d(), bias, residual, act_out=act_out, raw=raw, want_stats=want_stats,
                                        in_amax=getattr(coef, "_ipdm_amax_bound", None) if dyn else None, want_amax=produce,
@@ -163,6 +187,8 @@ def dilated_conv3x3(in_planes, out_planes, dilation, bias=True, spec_norm=False,
 
 
 def _maxpool(x):
+    if x.dim() == 3:
+        return ops.maxpool1d5(x)
     return ops.maxpool3d5(x) if x.dim() == 5 else ops.maxpool5(x)
 
 
@@ -171,11 +197,15 @@ class ConvMeanPool(nn.Module):
         super().__init__()
         if adjust_padding or spec_norm:
             raise NotImplementedError("adjust_padding / spec_norm are unused by every shipped config")
-        if ndim != 2:
+        if ndim == 3:
             raise NotImplementedError("the 8-way 3-D ConvMeanPool is unused by NCSN3DShallow (all its stages are dilated)")
-        self.conv = Conv2d(input_dim, output_dim, kernel_size, bias=biases)
+        self.conv = Conv2d(input_dim, output_dim, kernel_size, bias=biases, ndim=ndim)
 
     def forward(self, inputs, feeds_conv=True):
+        if self.conv.ndim == 1:                          # layers1d.py:319-324: the pair mean (y[2j] + y[2j+1]) / 2
+            if self.conv.kernel_size == 1:               # (commutes with the 1-tap convolution: pool first)
+                return self.conv(ops.meanpool1d2(inputs), feeds_conv=feeds_conv)
+            return ops.meanpool1d2(self.conv(inputs, feeds_conv=feeds_conv))
         if self.conv.kernel_size == 1:
             # a 1x1 convolution (+ bias) commutes with the 2x2 mean: pool first, a quarter of the multiply-adds and of
             # the bytes (same value up to fp32 rounding order)
@@ -186,6 +216,14 @@ class ConvMeanPool(nn.Module):
         """3x3 ConvMeanPool (+ pooled-size residual, + activated copy) in ONE launch: the Winograd kernel's 2x2 output tile
         is the pooling window.  -> out or (out, out_act); None where the pooled epilogue is not built for this layer."""
         c = self.conv
+        if c.ndim == 1:                                  # the 1-D kernel's pair-mean epilogue
+            if not (FUSE_POOL and coef is None and act == ops.ACT_NONE and c.kernel_size == 3 and inputs.shape[2] % 2 == 0
+                    and c.conv1d_ok(inputs)):
+                return None
+            dyn = ops.dynamic_range()
+            return ops.conv1d(inputs, c.packed_conv1d(), None if c.bias is None else c.bias.data, residual, c.dilation,
+                              act_out=act_out, in_amax=ops.in_amax_for(inputs) if dyn else None, want_amax=dyn and feeds_conv,
+                              pool2=True)
         if not (FUSE_POOL and USE_WINOGRAD and ops.split_impl() and c.ndim == 2 and c.kernel_size == 3 and c.dilation == 1
                 and inputs.shape[2] % 2 == 0 and inputs.shape[3] % 2 == 0
                 and ops.wino_bx3_pays(c.in_planes, c.out_planes, inputs.shape[2], inputs.shape[3], 1)):
@@ -292,7 +330,10 @@ class MSFBlock(nn.Module):
             else:
                 h = conv(xs[i], feeds_conv=False)
                 resize = ops.trilinear if h.dim() == 5 else ops.bilinear
-                sums = resize(h, shape, out=sums, accumulate=sums is not None, act=last_act,
+                size = shape
+                if h.dim() == 3:                                  # layers1d.py:185: mode='linear', align_corners=True
+                    resize, size = ops.linear1d, shape[0]
+                sums = resize(h, size, out=sums, accumulate=sums is not None, act=last_act,
                               want_amax=i == n - 1 and ops.dynamic_range())      # the block's result feeds CRP's convolutions
         return sums
 

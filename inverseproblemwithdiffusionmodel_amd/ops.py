@@ -1539,3 +1539,159 @@ def adam_ascent(x, g, m, v, lr, step, betas=(0.9, 0.999), eps=1e-8):
          float(eps), int(step), _stream())
     _written(x, m, v)
     return x
+
+
+# ---- 1-D convolution of (N, C, L) sequences: the temporal score networks NCSN1D* (csrc/conv1d.hip) --------------------------
+# The f16x2 arithmetic of the direct kernels on a GEMM whose columns are the flattened (sequence, t) positions: K = k * Cin with no
+# dead taps, whole sequences per column tile, one power-of-two input scale per SEQUENCE (the maxima vectors have one slot per
+# sequence here).  Dispatch is a function of the layer shape only (conv1d_pays): every other 1-D convolution -- few channels,
+# lengths that do not divide 96, other kernel families, IPDM_CONV1D=0 -- runs as the one-row image (N, C, 1, L) on the direct 2-D
+# kernel with the filter in the middle row of a 3 x 3 one, which is the same convolution (conv1d_rows).
+USE_CONV1D = os.environ.get("IPDM_CONV1D", "1") != "0"
+CONV1D_LAUNCHES = 0                              # launches of the 1-D kernel since import (diagnostics / tests)
+CONV1D_FALLBACKS = 0                             # 1-D convolutions that ran as one-row images on the 2-D kernels
+
+
+def conv1d_pays(Cin, Cout, L, k, dilation=1):
+    """True when the 1-D kernel takes a layer of this shape (a rule of the shape and of IPDM_CONV1D / IPDM_CONV_IMPL alone).
+    Measured on the MI355X at N = 512 (profiles/ncsn1d_ab.txt): 1.4x to 5.8x faster than the one-row form per launch on every
+    census shape, none slower -- so every served shape takes the kernel."""
+    return (USE_CONV1D and CONV_IMPL == "hx2"
+            and bool(_lib.lib.ipdm_conv1d_hx2_supported(int(Cin), int(Cout), int(L), int(k), int(dilation))))
+
+
+class PackedConv1d:
+    """[Cout, Cin, k] weights as f16x2 MFMA A-fragments + per-output-channel inverse scales (ipdm_conv1d_hx2_pack_weight)"""
+    __slots__ = ("blob", "Cout", "Cin", "k")
+
+    def __init__(self, blob, Cout, Cin, k):
+        self.blob, self.Cout, self.Cin, self.k = blob, Cout, Cin, k
+
+
+def conv1d_weight(w):
+    """[Cout, Cin, k] (k = 1 or 3; Cin % 16 == 0, Cout % 32 == 0) -> PackedConv1d"""
+    w = _gpu(w, torch.float32, "weight")
+    if w.dim() != 3:
+        raise ValueError(f"conv1d_weight: expected [Cout, Cin, k], got {tuple(w.shape)}")
+    Cout, Cin, k = (int(v) for v in w.shape)
+    nbytes = _lib.lib.ipdm_conv1d_hx2_weight_bytes(Cout, Cin, k)
+    if nbytes < 0:
+        raise _lib.IpdmUnsupported(f"conv1d_weight: no 1-D kernel for a [{Cout}, {Cin}, {k}] filter")
+    blob = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
+    call("ipdm_conv1d_hx2_pack_weight", _ptr(w), _ptr(blob), Cout, Cin, k, _stream())
+    return PackedConv1d(blob, Cout, Cin, k)
+
+
+def conv1d_rows_weight(w, impl=None):
+    """[Cout, Cin, k] -> the direct 2-D kernels' packed weight of the SAME convolution on one-row images: the filter in the
+    middle row of a 3 x 3 one (k = 1: a 1 x 1 filter)"""
+    w = _gpu(w, torch.float32, "weight")
+    Cout, Cin, k = (int(v) for v in w.shape)
+    if k == 1:
+        return conv_weight(w.reshape(Cout, Cin, 1, 1), impl=impl)
+    w2 = torch.zeros((Cout, Cin, 3, 3), dtype=torch.float32, device=w.device)
+    w2[:, :, 1, :] = w
+    return conv_weight(w2, impl=impl)
+
+
+def as_rows(x):
+    """(N, C, L) -> the one-row image view (N, C, 1, L); the per-sequence maxima ride along"""
+    return carry_amax(x, x.view(x.shape[0], x.shape[1], 1, x.shape[2]))
+
+
+def as_seq(x):
+    """(N, C, 1, L) -> (N, C, L), a view; the maxima ride along"""
+    return carry_amax(x, x.view(x.shape[0], x.shape[1], x.shape[3]))
+
+
+def conv1d_rows(x, wt, bias=None, coef=None, act=ACT_NONE, residual=None, dilation=1, act_out=ACT_NONE, raw=True, in_amax=None,
+                want_amax=False, res_second=False):
+    """the fallback / A-B arm: x (N, Cin, L) as one-row images on conv2d (wt from conv1d_rows_weight); conv2d's conventions"""
+    global CONV1D_FALLBACKS
+    CONV1D_FALLBACKS += 1
+    x = _gpu(x, torch.float32, "x")
+    res = None if residual is None else as_rows(_gpu(residual, torch.float32, "residual"))
+    y = conv2d(as_rows(x), wt, bias, coef, act, res, dilation, act_out=act_out, raw=raw, in_amax=in_amax, want_amax=want_amax,
+               res_second=res_second)
+    if act_out != ACT_NONE:
+        return (None if y[0] is None else as_seq(y[0])), as_seq(y[1])
+    return as_seq(y)
+
+
+def conv1d(x, wq, bias=None, residual=None, dilation=1, act_out=ACT_NONE, raw=True, in_amax=None, want_amax=False,
+           res_second=False, pool2=False):
+    """x (N, Cin, L) float32, wq a PackedConv1d.  Output side as conv2d: bias, residual, act_out != NONE additionally returns the
+    activated copy (raw=False: only that one; ACT_COPY + res_second: (conv + bias, conv + bias + residual)).  pool2: the pair
+    mean of ConvMeanPool -- results and residual are (N, Cout, L / 2).  in_amax: None (static range contract), True (measure) or
+    a maxima vector with one slot per sequence; want_amax: the per-sequence maxima of what is stored ride on the results."""
+    global CONV1D_LAUNCHES
+    x = _gpu(x, torch.float32, "x")
+    if x.dim() != 3 or x.shape[1] != wq.Cin:
+        raise ValueError(f"conv1d: input {tuple(x.shape)} for a filter with Cin {wq.Cin}")
+    N, Cin, L = (int(v) for v in x.shape)
+    if pool2 and L % 2:
+        raise ValueError("conv1d: the pair mean needs an even length")
+    want_act = act_out != ACT_NONE
+    if not raw and not want_act:
+        raise ValueError("conv1d: raw=False needs act_out")
+    if res_second and (residual is None or not want_act or not raw):
+        raise ValueError("conv1d: res_second needs a residual and both outputs (act_out, e.g. ACT_COPY; raw=True)")
+    shape = (N, wq.Cout, L // 2 if pool2 else L)
+    if residual is not None:
+        residual = _gpu(residual, torch.float32, "residual")
+        if tuple(residual.shape) != shape:
+            raise ValueError(f"conv1d: residual {tuple(residual.shape)} != {shape}")
+    want_amax = bool(want_amax) and os.environ.get("IPDM_AMAX_PRODUCE", "1") != "0"
+    slot_o = amax_slot(N, x.device) if want_amax and raw else None
+    slot_a = amax_slot(N, x.device) if want_amax and want_act else None
+    ext = _conv_ext("hx2", in_amax, x, False, False, 1.0, 0, slot_o, slot_a, res_second)
+    out = torch.empty(shape, dtype=torch.float32, device=x.device) if raw else None
+    out_act = torch.empty(shape, dtype=torch.float32, device=x.device) if want_act else None
+    if CONV_TRACE is not None:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+    call("ipdm_conv1d_hx2_f32", _ptr(x), _ptr(wq.blob), _ptr(bias), _ptr(residual), _ptr(out), _ptr(out_act), act_out, N, Cin,
+         wq.Cout, L, wq.k, int(dilation), int(bool(pool2)), ext, _stream())
+    CONV1D_LAUNCHES += 1
+    if CONV_TRACE is not None:
+        e1.record()
+        CONV_TRACE.append(dict(B=N, Cin=Cin, Cout=wq.Cout, H=1, W=L, k=wq.k, dil=dilation, conv1d=True, res=residual is not None,
+                               n_out=int(raw) + int(want_act), e0=e0, e1=e1))
+    tag_amax(out, slot_o)
+    tag_amax(out_act, slot_a)
+    return (out, out_act) if want_act else out
+
+
+def meanpool1d2(x):
+    """(..., L) -> (..., L / 2): y[j] = (x[2j] + x[2j+1]) / 2 (ConvMeanPool's tail along one axis); the maxima ride along"""
+    x = _gpu(x, torch.float32, "x")
+    L = int(x.shape[-1])
+    if L % 2:
+        raise ValueError("meanpool1d2: the length must be even")
+    out = torch.empty(tuple(x.shape[:-1]) + (L // 2,), dtype=torch.float32, device=x.device)
+    call("ipdm_meanpool1d2_f32", _ptr(x), _ptr(out), x.numel() // L, L, _stream())
+    return carry_amax(x, out)
+
+
+def scale_shift_amax(x, a, b):
+    """a * x + b whose per-image (dim 0) maxima ride on the result: the `2x - 1` in front of a score network's first convolution
+    as a PRODUCER of that convolution's in_amax (no measuring pass)"""
+    x = _gpu(x, torch.float32, "x")
+    B = int(x.shape[0])
+    out = torch.empty_like(x)
+    slot = amax_slot(B, x.device)
+    call("ipdm_scale_shift_amax_f32", _ptr(x), _ptr(out), _ptr(slot), B, x.numel() // max(B, 1), float(a), float(b), _stream())
+    return tag_amax(out, slot)
+
+
+def maxpool1d5(x):
+    """MaxPool1d(5, 1, 2) of (N, C, L): the 5 x 5 max-pool on one-row images (its padding is -inf: the same maxima)"""
+    return as_seq(maxpool5(as_rows(x)))
+
+
+def linear1d(x, size, out=None, accumulate=False, act=ACT_NONE, want_amax=False):
+    """F.interpolate(x, size, mode='linear', align_corners=True) of (N, C, L), optionally accumulated into out: the bilinear
+    kernel on one-row images (its row ratio at 1 -> 1 is taken as 0)"""
+    x = _gpu(x, torch.float32, "x")
+    out4 = None if out is None else out.view(out.shape[0], out.shape[1], 1, out.shape[2])
+    return as_seq(bilinear(as_rows(x), (1, int(size)), out=out4, accumulate=accumulate, act=act, want_amax=want_amax))

@@ -4,6 +4,7 @@ iteration; these are recorded in DESIGN.md):
   1  MNIST-shaped unconditional ALD sampling, 1 sample, full 232 x 3 schedule
   2  ACDC 128x128 R=20 4-coil, 8 samples: Langevin iterations/s
   4  CINE 2D+time 128x128x24, R=8 masks, spatial + temporal prior: seconds per noise level (1 sample)
+     (IPDM_BENCH_TEMPORAL=Diffusion1D: the NCSN1D temporal prior instead of NCSN3DShallow)
   5  NCSN++ 256x256 (celebahq_256_ncsnpp_continuous): score forward and one predictor-corrector step, batch 8
 Usage: python scripts/bench_configs.py [1 2 4 5]"""
 import json
@@ -63,7 +64,8 @@ def cfg4():
     H = W = 128
     T = 24
     net2d = reload_model("Diffusion", "CINE127", device=dev)
-    net3d = reload_model("Diffusion3D", "CINE127", device=dev)
+    temporal_type = os.environ.get("IPDM_BENCH_TEMPORAL", "Diffusion3D")      # "Diffusion1D": the NCSN1D temporal prior
+    net3d = reload_model(temporal_type, "CINE127", device=dev)
     sig, sigT = get_sigmas(net2d.config, "recons"), get_sigmas(net3d.config, "recons")
     op = SENSE("exp", 4, 8, 1 / 20, (1, H, W), 0, mask_T=24)
     frames = phantom_image(H, W, seed=0).to(dev).repeat(T, 1, 1, 1)
@@ -78,7 +80,7 @@ def cfg4():
     s_T = timed(lambda: smp(start_level=L - 2, n_levels=1, **kw), n=2, warm=0)          # level with temporal prior
     s_S = timed(lambda: smp(start_level=0, n_levels=1, **kw), n=2, warm=0)              # spatial-only level
     total = s_T * n_T + s_S * (L - n_T)
-    return dict(config=4, levels=L, levels_with_temporal_prior=n_T, s_per_level_spatial=s_S,
+    return dict(config=4, temporal_type=temporal_type, levels=L, levels_with_temporal_prior=n_T, s_per_level_spatial=s_S,
                 s_per_level_spatial_temporal=s_T, est_seconds_per_reconstruction=total)
 
 

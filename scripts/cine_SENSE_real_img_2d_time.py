@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """2D+time ALD reconstruction on synthetic k-space (counterpart of the reference's
 ``scripts/cine_SENSE_real_img_2d_time.py``, BASELINE config 4): spatial NCSNv2Deepest prior + temporal
-NCSN3DShallow prior on 8x8xT patches, SENSE with the T=24 mask.  Same flags; prints `reconstruction time` as the
+NCSN3DShallow prior on 8x8xT patches (`--temporal_type Diffusion1D`: NCSN1D on the same patches as (kx*ky, T) sequences), SENSE with the T=24 mask.  Same flags; prints `reconstruction time` as the
 reference does.  Under torchrun the `--num_samples` posterior samples are block-partitioned over the ranks (Philox noise
 keyed by the global sample id, the per-step random shift drawn from identically seeded host generators), rank 0 writes the
 artefacts and the posterior mean / std: the result does not depend on the number of ranks."""
@@ -26,6 +26,8 @@ if __name__ == '__main__':
     parser.add_argument("--proximal_type", default="L2Penalty")
     parser.add_argument("--num_samples", type=int, default=1)
     parser.add_argument("--sens_type", default="exp")
+    parser.add_argument("--temporal_type", default="Diffusion3D", choices=["Diffusion3D", "Diffusion1D"],
+                        help="temporal prior: NCSN3DShallow on 8x8xT patches, or NCSN1D on (kx*ky, T) sequences")
     parser.add_argument("--num_sens", type=int, default=4)
     parser.add_argument("--mode_T", default="diffusion1d", choices=["tv", "diffusion1d", "none", "diffusion1d-only", "tv-only"])
     parser.add_argument("--lamda_T", type=float, default=10.)
@@ -49,7 +51,7 @@ if __name__ == '__main__':
     np.random.seed(a.seed)                    # if_random_shift: one shift per step for the whole batch, on every rank
     H = W = a.image_size
     scorenet = reload_model("Diffusion", "CINE127", device=device)
-    scorenet_T = reload_model("Diffusion3D", "CINE127", device=device)
+    scorenet_T = reload_model(a.temporal_type, "CINE127", device=device)
     sigmas = get_sigmas(scorenet.config, "recons")
     sigmas_T = get_sigmas(scorenet_T.config, "recons")
     op = SENSE(a.sens_type, a.num_sens, a.R, a.center_lines_frac, (1, H, W), a.seed, mask_T=24 if a.T == 24 else 1)
