@@ -95,3 +95,17 @@ def test_abi_names_in_header_and_table():
             assert sup(cin, cout, L, 3, 1) and sup(cin, cout, L, 3, 2) and sup(cin, cout, L, 3, 4) and sup(cin, cout, L, 1, 1)
     assert not sup(16, 4, 24, 3, 1) and not sup(4, 16, 24, 3, 1) and not sup(128, 128, 10, 3, 1) and not sup(128, 128, 24, 3, 3)
     assert not sup(128, 128, 6, 3, 1)
+
+
+def test_served_lengths_are_the_divisors_of_96_from_12():
+    """the launcher's shape rule and ops.conv1d_pays agree for L = 1..200 on every census shape and (k, dilation), and the lengths
+    served are exactly 12, 16, 24, 32, 48 and 96 (whole sequences in a 96-column group)"""
+    from inverseproblemwithdiffusionmodel_amd import _lib, ops
+    sup = _lib.lib.ipdm_conv1d_hx2_supported
+    on = ops.USE_CONV1D and ops.CONV_IMPL == "hx2"
+    for cin, cout in [(64, 128), (128, 128), (128, 256), (256, 256), (256, 128), (128, 64)]:
+        for k, d in [(1, 1), (3, 1), (3, 2), (3, 4)]:
+            served = [L for L in range(1, 201) if sup(cin, cout, L, k, d)]
+            assert served == [12, 16, 24, 32, 48, 96], (cin, cout, k, d, served)
+            for L in range(1, 201):
+                assert ops.conv1d_pays(cin, cout, L, k, d) == (on and L in served), (cin, cout, L, k, d)
