@@ -168,6 +168,24 @@ int ipdm_ald_sense_step_f32(float* x_re, float* x_im, const float* g_re, const f
                             float* work /* ipdm_sense_workspace_bytes(B, n_coils, H, W) */, int B, int n_coils, int H, int W,
                             void* stream);
 
+/* The four operators above for COMPLEX coil sensitivity maps (measured maps: ESPIRiT, body-coil division, simulation).
+ * Same argument lists and return codes; `sens` is interleaved complex64 [n_coils][H][W] (2 floats per element, must not
+ * be NULL: IPDM_EINVAL).  Forward multiplies by S_c, adjoint and proximal tail by conj(S_c).  Maps with a zero imaginary
+ * part give the values of the real-map entry points exactly (only the sign of a zero may differ); workspace sizes are
+ * unchanged (ipdm_sense_workspace_bytes). */
+int ipdm_sense_forward_csm_c64(const float* x, const float* sens, const uint8_t* mask, int mask_t,
+                               float* y, int B, int n_coils, int H, int W, void* stream);
+int ipdm_sense_adjoint_csm_c64(const float* s, const float* sens, const uint8_t* mask, int mask_t,
+                               int apply_mask, float* x, float* workspace, int B, int n_coils, int H, int W, void* stream);
+int ipdm_sense_l2prox_csm_f32(const float* z_re, const float* z_im, const float* y, const float* sens,
+                              const uint8_t* mask, int mask_t, float coef, float* out_re, float* out_im,
+                              float* work, int B, int n_coils, int H, int W, void* stream);
+int ipdm_ald_sense_step_csm_f32(float* x_re, float* x_im, const float* g_re, const float* g_im,
+                                const float* noise_re, const float* noise_im,
+                                float step, float noise_scale, uint64_t seed, int64_t sample_offset, int64_t step_id,
+                                const ipdm_sched_t* dev_sched, const float* y, const float* sens, const uint8_t* mask,
+                                int mask_t, float coef, float* work, int B, int n_coils, int H, int W, void* stream);
+
 /* Single-coil data-consistency operators (A = M F, RandomUndersamplingFourier, no coil maps) on planar real/imag
  * float32 [B][H][W], y [B][H][W] complex64; out may alias z.  mode:
  *   0  L2Penalty on a single-coil operator (proximal_op.py:19-51): x = z - coef * F^-1[M (M F z - y)],

@@ -44,6 +44,11 @@ SIGNATURES = {
     "ipdm_sense_l2prox_f32": [P, P, P, P, P, c_int, c_float, P, P, P, c_int, c_int, c_int, c_int, P],
     "ipdm_ald_sense_step_f32": [P, P, P, P, P, P, c_float, c_float, c_uint64, c_int64, c_int64, P,
                                 P, P, P, c_int, c_float, P, c_int, c_int, c_int, c_int, P],
+    "ipdm_sense_forward_csm_c64": [P, P, P, c_int, P, c_int, c_int, c_int, c_int, P],
+    "ipdm_sense_adjoint_csm_c64": [P, P, P, c_int, c_int, P, P, c_int, c_int, c_int, c_int, P],
+    "ipdm_sense_l2prox_csm_f32": [P, P, P, P, P, c_int, c_float, P, P, P, c_int, c_int, c_int, c_int, P],
+    "ipdm_ald_sense_step_csm_f32": [P, P, P, P, P, P, c_float, c_float, c_uint64, c_int64, c_int64, P,
+                                    P, P, P, c_int, c_float, P, c_int, c_int, c_int, c_int, P],
     "ipdm_singlecoil_prox_f32": [P, P, P, P, c_int, c_float, c_int, P, P, P, c_int, c_int, c_int, P],
     "ipdm_ald_singlecoil_step_f32": [P, P, P, P, P, P, c_float, c_float, c_uint64, c_int64, c_int64, P,
                                      P, P, c_int, c_float, c_int, P, c_int, c_int, c_int, P],

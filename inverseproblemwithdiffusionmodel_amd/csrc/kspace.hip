@@ -81,20 +81,23 @@ __global__ __launch_bounds__(256) void dft_rows_transposed_kernel(const float2* 
 
 // ---------------------------------------------------------------------------------------------
 
+// SensT (here and below): the coil maps' element type, float or float2 (interleaved complex64); the products are
+// sens_mul / sens_mul_conj of kspace_fft.h
+template <typename SensT>
 __global__ __launch_bounds__(FFT_THREADS) void sense_forward_kernel(const float2* __restrict__ x,
-                                                                    const float* __restrict__ sens,
+                                                                    const SensT* __restrict__ sens,
                                                                     const uint8_t* __restrict__ mask, int mask_t,
                                                                     float2* __restrict__ y, int B, int H, int W) {
   FFT_LDS_SETUP(H, W)
   const int HW = H * W;
   const int b = blockIdx.x, coil = blockIdx.y;
   const float2* src = x + (size_t)b * HW;
-  const float* sm = sens ? sens + (size_t)coil * HW : nullptr;      // NULL: single coil, S = 1
+  const SensT* sm = sens ? sens + (size_t)coil * HW : nullptr;      // NULL: single coil, S = 1
   for (int e = threadIdx.x; e < HW; e += FFT_THREADS) {
     int r = e / W, c = e - r * W;
-    float s = sm ? sign_rc(r, c) * sm[e] : sign_rc(r, c);
+    float s = sign_rc(r, c);
     float2 v = src[e];
-    L.buf[e] = make_float2(v.x * s, v.y * s);
+    L.buf[e] = sm ? sens_mul(v, s, sm[e]) : make_float2(v.x * s, v.y * s);
   }
   __syncthreads();
   fft2_lds(L, H, W, false);
@@ -111,9 +114,9 @@ __global__ __launch_bounds__(FFT_THREADS) void sense_forward_kernel(const float2
 // s [n_coils][B][H][W] -> out[b] = sum_c S_c * ifft2c(s[c][b])  (or root-sum-of-squares for SSOS).
 // The coil sum is accumulated in the (L2-resident) output image, coil by coil in index order, like the
 // reference's `X_out += ...` loop: no accumulator registers live across the FFT, deterministic.
-template <bool SSOS>
+template <bool SSOS, typename SensT>
 __global__ __launch_bounds__(FFT_THREADS) void sense_adjoint_kernel(const float2* __restrict__ s,
-                                                                    const float* __restrict__ sens,
+                                                                    const SensT* __restrict__ sens,
                                                                     const uint8_t* __restrict__ mask, int mask_t,
                                                                     int apply_mask, float* out, int B,
                                                                     int n_coils, int H, int W) {
@@ -142,8 +145,7 @@ __global__ __launch_bounds__(FFT_THREADS) void sense_adjoint_kernel(const float2
         out[gi] = last ? sqrtf(a) : a;
       } else {
         int r = e / W, c = e - r * W;
-        float w = sign_rc(r, c) * scale * sens[(size_t)coil * HW + e];
-        float2 a = make_float2(v.x * w, v.y * w);
+        float2 a = sens_mul_conj(v, sign_rc(r, c) * scale, sens[(size_t)coil * HW + e]);
         float2* o = reinterpret_cast<float2*>(out) + gi;
         if (coil > 0) {
           float2 prev = *o;
@@ -187,12 +189,12 @@ __device__ __forceinline__ void langevin_phase(float* xr, float* xi, const float
 //   per coil: LDS = S_c z ; FFT ; residual on sampled columns ; IFFT ; work += S_c * (.)
 //   final:   x = z - coef * work
 // `work` ([B][H][W] c64) carries the coil sum so that no accumulator registers live across the FFTs.
-template <bool LANGEVIN>
+template <bool LANGEVIN, typename SensT>
 __global__ __launch_bounds__(FFT_THREADS) void ald_sense_step_kernel(
     float* x_re, float* x_im, const float* __restrict__ g_re, const float* __restrict__ g_im,
     const float* __restrict__ n_re, const float* __restrict__ n_im, float step, float noise_scale, uint64_t seed,
     int64_t sample_offset, int64_t step_id, const ipdm_sched_t* __restrict__ sched, const float2* __restrict__ y,
-    const float* __restrict__ sens, const uint8_t* __restrict__ mask, int mask_t, float coef, float2* work, int B,
+    const SensT* __restrict__ sens, const uint8_t* __restrict__ mask, int mask_t, float coef, float2* work, int B,
     int n_coils, int H, int W) {
   FFT_LDS_SETUP(H, W)
   if (sched) {
@@ -214,12 +216,11 @@ __global__ __launch_bounds__(FFT_THREADS) void ald_sense_step_kernel(
   for (int pass = 0; pass < 2 * n_coils; ++pass) {
     const int coil = pass >> 1;
     const bool inv = pass & 1;
-    const float* sm = sens + (size_t)coil * HW;
+    const SensT* sm = sens + (size_t)coil * HW;
     if (!inv) {
       for (int e = threadIdx.x; e < HW; e += FFT_THREADS) {
         int r = e / W, c = e - r * W;
-        float sg = sign_rc(r, c) * sm[e];
-        L.buf[e] = make_float2(xr[e] * sg, xi[e] * sg);
+        L.buf[e] = sens_mul(make_float2(xr[e], xi[e]), sign_rc(r, c), sm[e]);
       }
     }
     __syncthreads();
@@ -244,8 +245,7 @@ __global__ __launch_bounds__(FFT_THREADS) void ald_sense_step_kernel(
       for (int e = threadIdx.x; e < HW; e += FFT_THREADS) {
         int r = e / W, c = e - r * W;
         float2 v = L.buf[e];
-        float w = sign_rc(r, c) * scale * sm[e];
-        float2 a = make_float2(v.x * w, v.y * w);
+        float2 a = sens_mul_conj(v, sign_rc(r, c) * scale, sm[e]);
         if (coil > 0) {
           float2 prev = wk[e];
           a.x += prev.x;
@@ -290,12 +290,12 @@ __device__ __forceinline__ void langevin_value(const float* xr, const float* xi,
   zi = xi[e] + step * g_im[gi] + ni * noise_scale;
 }
 
-template <bool LANGEVIN>
+template <bool LANGEVIN, typename SensT>
 __global__ __launch_bounds__(FFT_THREADS) void ald_sense_coil_kernel(
     const float* x_re, const float* x_im, const float* __restrict__ g_re, const float* __restrict__ g_im,
     const float* __restrict__ n_re, const float* __restrict__ n_im, float step, float noise_scale, uint64_t seed,
     int64_t sample_offset, int64_t step_id, const ipdm_sched_t* __restrict__ sched, const float2* __restrict__ y,
-    const float* __restrict__ sens, const uint8_t* __restrict__ mask, int mask_t, float coef, float2* work, int B,
+    const SensT* __restrict__ sens, const uint8_t* __restrict__ mask, int mask_t, float coef, float2* work, int B,
     int n_coils, int H, int W) {
   FFT_LDS_SETUP(H, W)
   if (sched) {
@@ -310,14 +310,13 @@ __global__ __launch_bounds__(FFT_THREADS) void ald_sense_coil_kernel(
   const float scale = rsqrtf((float)HW);
   const float* xr = x_re + (size_t)b * HW;
   const float* xi = x_im + (size_t)b * HW;
-  const float* sm = sens + (size_t)coil * HW;
+  const SensT* sm = sens + (size_t)coil * HW;
   for (int e = threadIdx.x; e < HW; e += FFT_THREADS) {
     float zr = xr[e], zi = xi[e];
     if constexpr (LANGEVIN)
       langevin_value(xr, xi, g_re, g_im, n_re, n_im, step, noise_scale, seed, sample_offset, step_id, b, HW, e, zr, zi);
     const int r = e / W, c = e - r * W;
-    const float sg = sign_rc(r, c) * sm[e];
-    L.buf[e] = make_float2(zr * sg, zi * sg);
+    L.buf[e] = sens_mul(make_float2(zr, zi), sign_rc(r, c), sm[e]);
   }
   __syncthreads();
   fft2_lds(L, H, W, false);
@@ -339,8 +338,7 @@ __global__ __launch_bounds__(FFT_THREADS) void ald_sense_coil_kernel(
   for (int e = threadIdx.x; e < HW; e += FFT_THREADS) {
     const int r = e / W, c = e - r * W;
     const float2 v = L.buf[e];
-    const float w = sign_rc(r, c) * scale * sm[e];
-    wk[e] = make_float2(v.x * w, v.y * w);
+    wk[e] = sens_mul_conj(v, sign_rc(r, c) * scale, sm[e]);
   }
 }
 
@@ -465,17 +463,17 @@ static int set_lds_limit(K kernel, size_t bytes) {
   return e == hipSuccess ? IPDM_OK : (int)e;
 }
 
-template <bool LANGEVIN>
+template <bool LANGEVIN, typename SensT>
 static int launch_sense_step_coils(float* x_re, float* x_im, const float* g_re, const float* g_im, const float* n_re,
                                    const float* n_im, float step, float noise_scale, uint64_t seed, int64_t sample_offset,
-                                   int64_t step_id, const ipdm_sched_t* sched, const float2* y, const float* sens,
+                                   int64_t step_id, const ipdm_sched_t* sched, const float2* y, const SensT* sens,
                                    const uint8_t* mask, int mask_t, float coef, float2* work, int B, int n_coils, int H,
                                    int W, hipStream_t st) {
   if (B > 65535) return IPDM_EUNSUPPORTED;
   const size_t lds = lds_bytes(H, W);
-  const int rc = set_lds_limit(ald_sense_coil_kernel<LANGEVIN>, lds);
+  const int rc = set_lds_limit(ald_sense_coil_kernel<LANGEVIN, SensT>, lds);
   if (rc) return rc;
-  hipLaunchKernelGGL(ald_sense_coil_kernel<LANGEVIN>, dim3(n_coils, B), dim3(FFT_THREADS), lds, st, x_re, x_im, g_re, g_im,
+  hipLaunchKernelGGL((ald_sense_coil_kernel<LANGEVIN, SensT>), dim3(n_coils, B), dim3(FFT_THREADS), lds, st, x_re, x_im, g_re, g_im,
                      n_re, n_im, step, noise_scale, seed, (long long)sample_offset, (long long)step_id, sched, y, sens, mask,
                      mask_t, coef, work, B, n_coils, H, W);
   const int HW = H * W;
@@ -535,7 +533,8 @@ extern "C" int ipdm_fft2c_c64(const float* in, float* out, int batch, int H, int
   return ipdm_launch_status();
 }
 
-extern "C" int ipdm_sense_forward_c64(const float* x, const float* sens, const uint8_t* mask, int mask_t, float* y,
+template <typename SensT>
+static int sense_forward_impl(const float* x, const SensT* sens, const uint8_t* mask, int mask_t, float* y,
                                       int B, int n_coils, int H, int W, void* stream) {
   IPDM_REQUIRE(B >= 0 && n_coils > 0 && H > 0 && W > 0 && mask_t > 0);
   if (B == 0) return IPDM_OK;
@@ -545,14 +544,15 @@ extern "C" int ipdm_sense_forward_c64(const float* x, const float* sens, const u
                                             reinterpret_cast<float2*>(y), B, n_coils, H, W, ipdm_stream(stream));
   if (!lds_fft_ok(H, W)) return IPDM_EUNSUPPORTED;
   size_t lds = lds_bytes(H, W);
-  int rc = set_lds_limit(sense_forward_kernel, lds);
+  int rc = set_lds_limit(sense_forward_kernel<SensT>, lds);
   if (rc) return rc;
-  hipLaunchKernelGGL(sense_forward_kernel, dim3(B, n_coils), dim3(FFT_THREADS), lds, ipdm_stream(stream),
+  hipLaunchKernelGGL(sense_forward_kernel<SensT>, dim3(B, n_coils), dim3(FFT_THREADS), lds, ipdm_stream(stream),
                      reinterpret_cast<const float2*>(x), sens, mask, mask_t, reinterpret_cast<float2*>(y), B, H, W);
   return ipdm_launch_status();
 }
 
-extern "C" int ipdm_sense_adjoint_c64(const float* s, const float* sens, const uint8_t* mask, int mask_t,
+template <typename SensT>
+static int sense_adjoint_impl(const float* s, const SensT* sens, const uint8_t* mask, int mask_t,
                                       int apply_mask, float* x, float* workspace, int B, int n_coils, int H, int W,
                                       void* stream) {
   IPDM_REQUIRE(B >= 0 && n_coils > 0 && H > 0 && W > 0);
@@ -567,12 +567,36 @@ extern "C" int ipdm_sense_adjoint_c64(const float* s, const float* sens, const u
   }
   if (!lds_fft_ok(H, W)) return IPDM_EUNSUPPORTED;
   size_t lds = lds_bytes(H, W);
-  int rc = set_lds_limit(sense_adjoint_kernel<false>, lds);
+  int rc = set_lds_limit(sense_adjoint_kernel<false, SensT>, lds);
   if (rc) return rc;
-  hipLaunchKernelGGL(sense_adjoint_kernel<false>, dim3(B), dim3(FFT_THREADS), lds, ipdm_stream(stream),
+  hipLaunchKernelGGL((sense_adjoint_kernel<false, SensT>), dim3(B), dim3(FFT_THREADS), lds, ipdm_stream(stream),
                      reinterpret_cast<const float2*>(s), sens, mask, mask_t > 0 ? mask_t : 1, apply_mask, x, B, n_coils,
                      H, W);
   return ipdm_launch_status();
+}
+
+extern "C" int ipdm_sense_forward_c64(const float* x, const float* sens, const uint8_t* mask, int mask_t, float* y,
+                                      int B, int n_coils, int H, int W, void* stream) {
+  return sense_forward_impl(x, sens, mask, mask_t, y, B, n_coils, H, W, stream);
+}
+
+extern "C" int ipdm_sense_forward_csm_c64(const float* x, const float* sens, const uint8_t* mask, int mask_t, float* y,
+                                          int B, int n_coils, int H, int W, void* stream) {
+  IPDM_REQUIRE(sens || B == 0);                                 // no single-coil shortcut here: complex maps are required
+  return sense_forward_impl(x, reinterpret_cast<const float2*>(sens), mask, mask_t, y, B, n_coils, H, W, stream);
+}
+
+extern "C" int ipdm_sense_adjoint_c64(const float* s, const float* sens, const uint8_t* mask, int mask_t,
+                                      int apply_mask, float* x, float* workspace, int B, int n_coils, int H, int W,
+                                      void* stream) {
+  return sense_adjoint_impl(s, sens, mask, mask_t, apply_mask, x, workspace, B, n_coils, H, W, stream);
+}
+
+extern "C" int ipdm_sense_adjoint_csm_c64(const float* s, const float* sens, const uint8_t* mask, int mask_t,
+                                          int apply_mask, float* x, float* workspace, int B, int n_coils, int H, int W,
+                                          void* stream) {
+  return sense_adjoint_impl(s, reinterpret_cast<const float2*>(sens), mask, mask_t, apply_mask, x, workspace, B, n_coils,
+                            H, W, stream);
 }
 
 extern "C" int ipdm_sense_ssos_c64(const float* s, float* out, float* workspace, int B, int n_coils, int H, int W,
@@ -582,19 +606,20 @@ extern "C" int ipdm_sense_ssos_c64(const float* s, float* out, float* workspace,
   IPDM_REQUIRE(s && out);
   if (ipdm_kspace_large::large_ok(H, W)) {
     IPDM_REQUIRE(workspace);
-    return ipdm_kspace_large::sense_adjoint(reinterpret_cast<const float2*>(s), nullptr, nullptr, 1, 0, nullptr, out,
+    return ipdm_kspace_large::sense_adjoint<float>(reinterpret_cast<const float2*>(s), nullptr, nullptr, 1, 0, nullptr, out,
                                             reinterpret_cast<float2*>(workspace), B, n_coils, H, W, ipdm_stream(stream));
   }
   if (!lds_fft_ok(H, W)) return IPDM_EUNSUPPORTED;
   size_t lds = lds_bytes(H, W);
-  int rc = set_lds_limit(sense_adjoint_kernel<true>, lds);
+  int rc = set_lds_limit(sense_adjoint_kernel<true, float>, lds);
   if (rc) return rc;
-  hipLaunchKernelGGL(sense_adjoint_kernel<true>, dim3(B), dim3(FFT_THREADS), lds, ipdm_stream(stream),
-                     reinterpret_cast<const float2*>(s), nullptr, nullptr, 1, 0, out, B, n_coils, H, W);
+  hipLaunchKernelGGL((sense_adjoint_kernel<true, float>), dim3(B), dim3(FFT_THREADS), lds, ipdm_stream(stream),
+                     reinterpret_cast<const float2*>(s), static_cast<const float*>(nullptr), nullptr, 1, 0, out, B, n_coils, H, W);
   return ipdm_launch_status();
 }
 
-extern "C" int ipdm_sense_l2prox_f32(const float* z_re, const float* z_im, const float* y, const float* sens,
+template <typename SensT>
+static int sense_l2prox_impl(const float* z_re, const float* z_im, const float* y, const SensT* sens,
                                      const uint8_t* mask, int mask_t, float coef, float* out_re, float* out_im,
                                      float* work, int B, int n_coils, int H, int W, void* stream) {
   IPDM_REQUIRE(B >= 0 && n_coils > 0 && H > 0 && W > 0 && mask_t > 0);
@@ -615,18 +640,19 @@ extern "C" int ipdm_sense_l2prox_f32(const float* z_re, const float* z_im, const
                                           reinterpret_cast<const float2*>(y), sens, mask, mask_t, coef,
                                           reinterpret_cast<float2*>(work), B, n_coils, H, W, st);
   size_t lds = lds_bytes(H, W);
-  int rc = set_lds_limit(ald_sense_step_kernel<false>, lds);
+  int rc = set_lds_limit(ald_sense_step_kernel<false, SensT>, lds);
   if (rc) return rc;
-  hipLaunchKernelGGL(ald_sense_step_kernel<false>, dim3(B), dim3(FFT_THREADS), lds, st, out_re, out_im, nullptr,
+  hipLaunchKernelGGL((ald_sense_step_kernel<false, SensT>), dim3(B), dim3(FFT_THREADS), lds, st, out_re, out_im, nullptr,
                      nullptr, nullptr, nullptr, 0.f, 0.f, 0ull, 0ll, 0ll, nullptr, reinterpret_cast<const float2*>(y), sens,
                      mask, mask_t, coef, reinterpret_cast<float2*>(work), B, n_coils, H, W);
   return ipdm_launch_status();
 }
 
-extern "C" int ipdm_ald_sense_step_f32(float* x_re, float* x_im, const float* g_re, const float* g_im,
+template <typename SensT>
+static int ald_sense_step_impl(float* x_re, float* x_im, const float* g_re, const float* g_im,
                                        const float* noise_re, const float* noise_im, float step, float noise_scale,
                                        uint64_t seed, int64_t sample_offset, int64_t step_id,
-                                       const ipdm_sched_t* dev_sched, const float* y, const float* sens, const uint8_t* mask, int mask_t, float coef, float* work,
+                                       const ipdm_sched_t* dev_sched, const float* y, const SensT* sens, const uint8_t* mask, int mask_t, float coef, float* work,
                                        int B, int n_coils, int H, int W, void* stream) {
   IPDM_REQUIRE(B >= 0 && n_coils > 0 && H > 0 && W > 0 && mask_t > 0);
   if (B == 0) return IPDM_OK;
@@ -642,13 +668,46 @@ extern "C" int ipdm_ald_sense_step_f32(float* x_re, float* x_im, const float* g_
                                          step_id, dev_sched, reinterpret_cast<const float2*>(y), sens, mask, mask_t, coef,
                                          reinterpret_cast<float2*>(work), B, n_coils, H, W, ipdm_stream(stream));
   size_t lds = lds_bytes(H, W);
-  int rc = set_lds_limit(ald_sense_step_kernel<true>, lds);
+  int rc = set_lds_limit(ald_sense_step_kernel<true, SensT>, lds);
   if (rc) return rc;
-  hipLaunchKernelGGL(ald_sense_step_kernel<true>, dim3(B), dim3(FFT_THREADS), lds, ipdm_stream(stream), x_re, x_im,
+  hipLaunchKernelGGL((ald_sense_step_kernel<true, SensT>), dim3(B), dim3(FFT_THREADS), lds, ipdm_stream(stream), x_re, x_im,
                      g_re, g_im, noise_re, noise_im, step, noise_scale, seed, (long long)sample_offset,
                      (long long)step_id, dev_sched, reinterpret_cast<const float2*>(y), sens, mask, mask_t, coef,
                      reinterpret_cast<float2*>(work), B, n_coils, H, W);
   return ipdm_launch_status();
+}
+
+extern "C" int ipdm_sense_l2prox_f32(const float* z_re, const float* z_im, const float* y, const float* sens,
+                                     const uint8_t* mask, int mask_t, float coef, float* out_re, float* out_im,
+                                     float* work, int B, int n_coils, int H, int W, void* stream) {
+  return sense_l2prox_impl(z_re, z_im, y, sens, mask, mask_t, coef, out_re, out_im, work, B, n_coils, H, W, stream);
+}
+
+extern "C" int ipdm_sense_l2prox_csm_f32(const float* z_re, const float* z_im, const float* y, const float* sens,
+                                         const uint8_t* mask, int mask_t, float coef, float* out_re, float* out_im,
+                                         float* work, int B, int n_coils, int H, int W, void* stream) {
+  return sense_l2prox_impl(z_re, z_im, y, reinterpret_cast<const float2*>(sens), mask, mask_t, coef, out_re, out_im, work, B,
+                           n_coils, H, W, stream);
+}
+
+extern "C" int ipdm_ald_sense_step_f32(float* x_re, float* x_im, const float* g_re, const float* g_im,
+                                       const float* noise_re, const float* noise_im, float step, float noise_scale,
+                                       uint64_t seed, int64_t sample_offset, int64_t step_id,
+                                       const ipdm_sched_t* dev_sched, const float* y, const float* sens, const uint8_t* mask,
+                                       int mask_t, float coef, float* work, int B, int n_coils, int H, int W, void* stream) {
+  return ald_sense_step_impl(x_re, x_im, g_re, g_im, noise_re, noise_im, step, noise_scale, seed, sample_offset, step_id,
+                             dev_sched, y, sens, mask, mask_t, coef, work, B, n_coils, H, W, stream);
+}
+
+extern "C" int ipdm_ald_sense_step_csm_f32(float* x_re, float* x_im, const float* g_re, const float* g_im,
+                                           const float* noise_re, const float* noise_im, float step, float noise_scale,
+                                           uint64_t seed, int64_t sample_offset, int64_t step_id,
+                                           const ipdm_sched_t* dev_sched, const float* y, const float* sens,
+                                           const uint8_t* mask, int mask_t, float coef, float* work, int B, int n_coils, int H,
+                                           int W, void* stream) {
+  return ald_sense_step_impl(x_re, x_im, g_re, g_im, noise_re, noise_im, step, noise_scale, seed, sample_offset, step_id,
+                             dev_sched, y, reinterpret_cast<const float2*>(sens), mask, mask_t, coef, work, B, n_coils, H, W,
+                             stream);
 }
 
 extern "C" int ipdm_singlecoil_prox_f32(const float* z_re, const float* z_im, const float* y, const uint8_t* mask,
@@ -665,7 +724,7 @@ extern "C" int ipdm_singlecoil_prox_f32(const float* z_re, const float* z_im, co
   if (out_im != z_im && hipMemcpyAsync(out_im, z_im, bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) return (int)hipGetLastError();
   if (large) {
     IPDM_REQUIRE(workspace);
-    return ipdm_kspace_large::prox_step(out_re, out_im, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, 0ull, 0, 0, nullptr,
+    return ipdm_kspace_large::prox_step<float>(out_re, out_im, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, 0ull, 0, 0, nullptr,
                                         reinterpret_cast<const float2*>(y), nullptr, mask, mask_t, coef, mode,
                                         reinterpret_cast<float2*>(workspace), B, 1, H, W, st);
   }
@@ -689,7 +748,7 @@ extern "C" int ipdm_ald_singlecoil_step_f32(float* x_re, float* x_im, const floa
   IPDM_REQUIRE((noise_re == nullptr) == (noise_im == nullptr));
   if (ipdm_kspace_large::large_ok(H, W)) {
     IPDM_REQUIRE(workspace);
-    return ipdm_kspace_large::prox_step(x_re, x_im, g_re, g_im, noise_re, noise_im, step, noise_scale, seed, sample_offset,
+    return ipdm_kspace_large::prox_step<float>(x_re, x_im, g_re, g_im, noise_re, noise_im, step, noise_scale, seed, sample_offset,
                                         step_id, dev_sched, reinterpret_cast<const float2*>(y), nullptr, mask, mask_t, coef,
                                         mode, reinterpret_cast<float2*>(workspace), B, 1, H, W, ipdm_stream(stream));
   }

@@ -107,6 +107,31 @@ __device__ __forceinline__ void fft2_lds(const FftLds& L, int H, int W, bool inv
 
 __device__ __forceinline__ float sign_rc(int r, int c) { return ((r + c) & 1) ? -1.f : 1.f; }
 
+// Coil-map products, the only place they are written.  A map element is `float` (real maps, the reference's synthetic
+// "exp" maps) or `float2` (interleaved complex64, measured maps); `g` is the real factor folded in with the map: the
+// centring sign +-1 in sens_mul, sign / sqrt(HW) in sens_mul_conj.
+//   sens_mul(v, g, S)      = (g S) v          forward:  S_c x
+//   sens_mul_conj(v, g, S) = (g conj(S)) v    adjoint and proximal tail:  conj(S_c) F^-1[...]
+// The real forms are the expressions the kernels have always used.  The complex forms fix the operation order (one
+// rounded product, one fma per component), so every kernel form rounds alike whatever the compiler's contraction
+// setting; with a zero imaginary part they give the real form's bits.
+__device__ __forceinline__ float2 sens_mul(float2 v, float g, float s) {
+  const float w = g * s;
+  return make_float2(v.x * w, v.y * w);
+}
+__device__ __forceinline__ float2 sens_mul_conj(float2 v, float g, float s) {
+  const float w = g * s;
+  return make_float2(v.x * w, v.y * w);
+}
+__device__ __forceinline__ float2 sens_mul(float2 v, float g, float2 s) {
+  const float wx = __fmul_rn(g, s.x), wy = __fmul_rn(g, s.y);
+  return make_float2(fmaf(v.x, wx, -__fmul_rn(v.y, wy)), fmaf(v.x, wy, __fmul_rn(v.y, wx)));
+}
+__device__ __forceinline__ float2 sens_mul_conj(float2 v, float g, float2 s) {
+  const float wx = __fmul_rn(g, s.x), wy = __fmul_rn(g, s.y);
+  return make_float2(fmaf(v.x, wx, __fmul_rn(v.y, wy)), fmaf(v.y, wx, -__fmul_rn(v.x, wy)));
+}
+
 __host__ __device__ __forceinline__ bool is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 static inline bool lds_fft_ok(int H, int W) {
   return is_pow2(H) && is_pow2(W) && H >= 4 && W >= 4 && (int64_t)H * W <= FFT_MAX_ELEMS;
@@ -125,12 +150,16 @@ namespace ipdm_kspace_large {
 bool large_ok(int H, int W);
 int64_t workspace_bytes(int B, int n_coils, int H, int W);
 int fft2c(const float2* in, float2* out, int batch, int H, int W, int inverse, hipStream_t s);
-int sense_forward(const float2* x, const float* sens, const uint8_t* mask, int mask_t, float2* y, int B, int n_coils,
+// SensT: float (real maps) or float2 (interleaved complex64 maps); both are instantiated in kspace_large.hip
+template <typename SensT>
+int sense_forward(const float2* x, const SensT* sens, const uint8_t* mask, int mask_t, float2* y, int B, int n_coils,
                   int H, int W, hipStream_t s);
-int sense_adjoint(const float2* sm, const float* sens, const uint8_t* mask, int mask_t, int apply_mask, float2* x_out,
+template <typename SensT>
+int sense_adjoint(const float2* sm, const SensT* sens, const uint8_t* mask, int mask_t, int apply_mask, float2* x_out,
                   float* ssos_out, float2* ws, int B, int n_coils, int H, int W, hipStream_t s);
+template <typename SensT>
 int prox_step(float* x_re, float* x_im, const float* g_re, const float* g_im, const float* n_re, const float* n_im,
               float step, float noise_scale, uint64_t seed, int64_t sample_offset, int64_t step_id,
-              const ipdm_sched_t* sched, const float2* y, const float* sens, const uint8_t* mask, int mask_t, float coef,
+              const ipdm_sched_t* sched, const float2* y, const SensT* sens, const uint8_t* mask, int mask_t, float coef,
               int mode, float2* ws, int B, int n_coils, int H, int W, hipStream_t s);
 }  // namespace ipdm_kspace_large

@@ -55,12 +55,17 @@ def build_scorenet(cfg, seed=0):
     return net.to(cfg.device).eval()
 
 
-def build_problem(device, n_samples, R=40, H=128, W=128, num_sens=4, seed=0, scorenet=None, cfg=None, lr_scaled=1.0):
-    """-> Namespace(sampler, scorenet, sigmas, op, image, measurement, call_kwargs)"""
+def build_problem(device, n_samples, R=40, H=128, W=128, num_sens=4, seed=0, scorenet=None, cfg=None, lr_scaled=1.0,
+                  sens_maps=None):
+    """-> Namespace(sampler, scorenet, sigmas, op, image, measurement, call_kwargs); sens_maps: measured coil maps
+    (num_sens, H, W), real or complex, instead of the synthetic "exp" maps (RSS-normalised where non-zero)"""
     cfg = acdc_config(device, H) if cfg is None else cfg
     scorenet = build_scorenet(cfg, seed) if scorenet is None else scorenet
     sigmas = get_sigmas(cfg, "recons")
-    op = SENSE("exp", num_sens, R, 0.04, (1, H, W), seed=seed, mask_T=1)
+    if sens_maps is None:
+        op = SENSE("exp", num_sens, R, 0.04, (1, H, W), seed=seed, mask_T=1)
+    else:
+        op = SENSE("custom", num_sens, R, 0.04, (1, H, W), seed=seed, mask_T=1, sens_maps=sens_maps)
     img = phantom_image(H, W, seed=seed).to(device)
     meas = op(img).repeat(1, n_samples, 1, 1, 1).contiguous()
     params = dict(n_steps_each=cfg.sampling.n_steps_each, step_lr=cfg.sampling.step_lr, denoise=True,
@@ -96,7 +101,7 @@ class IterationRunner:
         self.levels = lv
         self.table_dev = torch.from_numpy(table.view(np.uint8).reshape(L * n_each, -1).copy()).to(dev)
         self.label_table = torch.arange(L, device=dev)[:, None].repeat(1, 2 * B)
-        self.st = dict(x=self.x, B=B, y=meas, sc_mode=None, sens=s.linear_tfm.sens_f32(dev), mask=s.linear_tfm.mask_u8(dev),
+        self.st = dict(x=self.x, B=B, y=meas, sc_mode=None, sens=s.linear_tfm.sens_dev(dev), mask=s.linear_tfm.mask_u8(dev),
                        work=ops_mod.sense_workspace(B, s.linear_tfm.sens_maps.shape[0], H, W, dev),
                        labels=torch.zeros(2 * B, dtype=torch.long, device=dev), noise_re=None, noise_im=None,
                        seed=seed, sample_offset=sample_offset,

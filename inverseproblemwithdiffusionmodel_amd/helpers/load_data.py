@@ -202,3 +202,47 @@ def load_data(ds_name, mode="train", root_dir=None, **kwargs):
     if ds_name == "CINE127":
         return load_cine(root, mode=mode, resize_shape=128, **kwargs)
     raise NotImplementedError(f"dataset {ds_name!r}: only the ACDC .npz and CINE .mat front ends are built")
+
+
+def load_sens_maps(path):
+    """coil sensitivity maps (n_coils, H, W), real or complex, from a ``.npy`` or ``.pt`` file -> host tensor
+    (float64 / complex128), ready for ``SENSE("custom", ..., sens_maps=...)``"""
+    import numpy as np
+    import torch
+    ext = os.path.splitext(str(path))[1].lower()
+    if ext == ".npy":
+        maps = torch.from_numpy(np.load(path, allow_pickle=False))
+    elif ext == ".pt":
+        maps = torch.load(path, map_location="cpu")
+        if isinstance(maps, np.ndarray):
+            maps = torch.from_numpy(maps)
+    else:
+        raise ValueError(f"load_sens_maps: {path!r}: a .npy or .pt file")
+    if not isinstance(maps, torch.Tensor) or maps.dim() != 3:
+        raise ValueError(f"load_sens_maps: {path!r} must hold one array of shape (n_coils, H, W)")
+    if not (maps.is_complex() or maps.is_floating_point()):
+        raise TypeError(f"load_sens_maps: {path!r} holds {maps.dtype}; real or complex floating maps expected")
+    return maps.to(torch.complex128 if maps.is_complex() else torch.float64)
+
+
+def add_sens_map_args(parser):
+    """the drivers' coil-map flags: --sens_maps PATH (measured maps from a file) and --sens_phase (synthetic complex maps)"""
+    parser.add_argument("--sens_maps", default=None,
+                        help=".npy / .pt file with measured coil maps (num_sens, H, W), real or complex")
+    parser.add_argument("--sens_phase", action="store_true",
+                        help="synthetic COMPLEX coil maps: the exp magnitudes times a smooth seeded phase")
+
+
+def driver_sens_maps(path, sens_phase, num_sens, H, W, seed):
+    """-> (maps or None, num_sens): the RSS-normalised maps a driver assigns to ``op.sens_maps`` for --sens_maps PATH or
+    --sens_phase, None for the default synthetic real maps; a file sets the coil count"""
+    from ..ncsn.linear_transforms.undersampling_fourier import SENSE
+    if path:
+        maps = load_sens_maps(path)
+        if tuple(maps.shape[-2:]) != (H, W):
+            raise ValueError(f"--sens_maps {path!r}: maps {tuple(maps.shape)} for {H}x{W} images")
+        return SENSE.rss_normalize(maps), int(maps.shape[0])
+    if sens_phase:
+        from ..synthetic import complex_coil_maps
+        return complex_coil_maps(num_sens, H, W, seed), num_sens
+    return None, num_sens

@@ -10,7 +10,13 @@ Differences the reference forces on a drop-in, all explicit:
 * ``mask_mode="uniform"`` is the LEGACY mask the reference keeps commented out (:50-61): ``rand(1, 1, W) <= 1 / R`` from torch's
   generator plus a fully sampled centre window of ``int(W * center_lines_frac)`` lines -- the only mode in which ``R`` and
   ``center_lines_frac`` act as the constructor's signature promises, for any R (bit-exact against tests/golden/g30).
-* coil maps are kept float64 on the host (``.sens_maps``, as the reference) and float32 on the device.
+* coil maps are kept float64 (real) or complex128 (measured, complex maps) on the host (``.sens_maps``, as the reference)
+  and float32 / complex64 on the device (``sens_dev``); the kernels multiply by S_c forward and conj(S_c) in the adjoint
+  and the proximal tail, as the reference's ``conj_op`` (:157).  ``sens_maps`` is a property: the reference's idiom
+  ``op.sens_maps = maps`` validates the shape and drops the cached device copies, before or after first use.
+* ``sens_type="custom"`` takes ``sens_maps=`` (tensor or ndarray, real or complex, (num_sens, H, W)); ``normalize=True``
+  divides by the root-sum-of-squares where it is non-zero (measured maps are masked to the body: zero-support pixels stay
+  zero), ``normalize=False`` takes the maps as given.  ``"exp"`` is the reference's synthetic real map, unchanged.
 """
 import warnings
 
@@ -118,10 +124,20 @@ class RandomUndersamplingFourier(LinearTransform):
 
 class SENSE(LinearTransform):
     def __init__(self, sens_type, num_sens, R, center_lines_frac, in_shape, seed, mask_T=1, mask_params=None,
-                 mask_mode="variable"):
-        assert sens_type in ["exp"]
+                 mask_mode="variable", sens_maps=None, normalize=True):
+        assert sens_type in ["exp", "custom"]
         self.random_under_fourier = RandomUndersamplingFourier(R, center_lines_frac, in_shape, seed, mask_T,
                                                                mask_params, mask_mode)
+        self.num_sens = num_sens
+        self._dev = {}
+        if sens_type == "custom":
+            if sens_maps is None:
+                raise ValueError("SENSE('custom', ...) needs sens_maps= (num_sens, H, W), real or complex")
+            maps = self._as_host_maps(sens_maps)
+            self.sens_maps = self.rss_normalize(maps) if normalize else maps
+            return
+        if sens_maps is not None:
+            raise ValueError("sens_maps= goes with sens_type='custom'")
         maps = []
         for i in range(num_sens):
             s = self.random_under_fourier.seed
@@ -130,7 +146,38 @@ class SENSE(LinearTransform):
         self.sens_maps = maps / torch.sqrt((torch.abs(maps) ** 2).sum(dim=0))
         energy = (torch.abs(self.sens_maps) ** 2).sum(dim=0)
         assert torch.allclose(energy, torch.ones_like(energy))
-        self._dev = {}
+
+    @staticmethod
+    def rss_normalize(maps):
+        """maps / root-sum-of-squares over the coils where it is non-zero; zero-support pixels stay zero"""
+        maps = SENSE._as_host_maps(maps)
+        rss = torch.sqrt((torch.abs(maps) ** 2).sum(dim=0))
+        return maps / torch.where(rss > 0, rss, torch.ones_like(rss))
+
+    @staticmethod
+    def _as_host_maps(maps):
+        """tensor / ndarray -> host tensor, float64 (real input) or complex128 (complex input)"""
+        if not isinstance(maps, (torch.Tensor, np.ndarray)):
+            raise TypeError(f"sens_maps: a torch tensor or numpy array, got {type(maps).__name__}")
+        t = torch.as_tensor(maps).detach().cpu()
+        if t.is_complex():
+            return t.to(torch.complex128)
+        if t.is_floating_point():
+            return t.to(torch.float64)
+        raise TypeError(f"sens_maps: a real or complex floating dtype, got {t.dtype}")
+
+    @property
+    def sens_maps(self):
+        return self._sens_maps
+
+    @sens_maps.setter
+    def sens_maps(self, maps):
+        t = self._as_host_maps(maps)
+        want = (self.num_sens,) + tuple(self.random_under_fourier.in_shape[-2:])
+        if tuple(t.shape) != want:
+            raise ValueError(f"sens_maps: shape {tuple(t.shape)}, expected (num_sens, H, W) = {want}")
+        self._sens_maps = t.contiguous()
+        self._dev = {}                                                      # the device copies belong to the old maps
 
     def _generate_sens_map(self, sens_type, seed=0, **kwargs):
         """exp(-dist / (2 l)) around a random anchor, l = max(dist) / 2.  The reference builds the pixel list
@@ -147,11 +194,18 @@ class SENSE(LinearTransform):
         return torch.exp(-torch.tensor(dist.reshape(H, W)) / (2 * length))
 
     # device-side cached copies (the reference re-uploads on every call, :143,154)
-    def sens_f32(self, device):
+    def sens_dev(self, device):
+        """the only producer of device maps: float32 for real maps, complex64 for complex ones (ops dispatches on it)"""
         key = str(device)
         if key not in self._dev:
-            self._dev[key] = self.sens_maps.to(torch.float32).to(device).contiguous()
+            dt = torch.complex64 if self._sens_maps.is_complex() else torch.float32
+            self._dev[key] = self._sens_maps.to(dt).to(device).contiguous()
         return self._dev[key]
+
+    def sens_f32(self, device):
+        if self._sens_maps.is_complex():
+            raise TypeError("SENSE.sens_f32: the coil maps are complex; use sens_dev(device) (complex64)")
+        return self.sens_dev(device)
 
     def mask_u8(self, device):
         return self.random_under_fourier.mask_u8(device)
@@ -160,12 +214,12 @@ class SENSE(LinearTransform):
         """X (B, C, H, W) complex -> (num_sens, B, C, H, W) complex64"""
         _check_gpu(X, "SENSE")
         X = X.to(torch.complex64)
-        return ops.sense_forward(X, self.sens_f32(X.device), self.mask_u8(X.device))
+        return ops.sense_forward(X, self.sens_dev(X.device), self.mask_u8(X.device))
 
     def conj_op(self, S: torch.Tensor) -> torch.Tensor:
         _check_gpu(S, "SENSE.conj_op")
         S = S.to(torch.complex64)
-        return ops.sense_adjoint(S, self.sens_f32(S.device))
+        return ops.sense_adjoint(S, self.sens_dev(S.device))
 
     def SSOS(self, S: torch.Tensor) -> torch.Tensor:
         _check_gpu(S, "SENSE.SSOS")

@@ -230,7 +230,7 @@ class ALDInvSegProximalRealImag(ALDOptimizer):
         lv0 = kwargs.get("start_level", 0)
         lv1 = L if kwargs.get("n_levels") is None else min(L, lv0 + kwargs["n_levels"])
 
-        st = dict(x=x, B=B, y=meas, sc_mode=sc_mode, sens=lin.sens_f32(dev) if sc_mode is None else None,
+        st = dict(x=x, B=B, y=meas, sc_mode=sc_mode, sens=lin.sens_dev(dev) if sc_mode is None else None,
                   mask=lin.mask_u8(dev),
                   work=ops.sense_workspace(B, lin.sens_maps.shape[0] if sc_mode is None else 1, H, W, dev),
                   labels=torch.zeros(2 * B, dtype=torch.long, device=dev),

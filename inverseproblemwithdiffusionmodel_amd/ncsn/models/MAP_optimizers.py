@@ -58,7 +58,7 @@ class MAPModel:
         tfm, dev = self.lin_tfm, self.device
         B, H, W = self.X.shape[0], self.X.shape[-2], self.X.shape[-1]
         x = torch.cat([self.X.real, self.X.imag], dim=0).contiguous().float()        # planar state (2B, 1, H, W)
-        sens, mask = tfm.sens_f32(dev), tfm.mask_u8(dev)
+        sens, mask = tfm.sens_dev(dev), tfm.mask_u8(dev)
         m, v = torch.zeros_like(x), torch.zeros_like(x)
         px = torch.empty_like(x)
         work = ops.sense_workspace(B, sens.shape[0], H, W, dev)
@@ -109,7 +109,7 @@ class MAPOptimizer(object):
         B, H, W = x0.shape[0], x0.shape[-2], x0.shape[-1]
         x = torch.cat([x0.real, x0.imag], dim=0).contiguous().float()                 # planar state (2B, 1, H, W)
         y = self.measurement.to(dev).to(torch.complex64).contiguous()
-        sens, mask = tfm.sens_f32(dev), tfm.mask_u8(dev)
+        sens, mask = tfm.sens_dev(dev), tfm.mask_u8(dev)
         m, v = torch.zeros_like(x), torch.zeros_like(x)
         px = torch.empty_like(x)
         work = ops.sense_workspace(B, sens.shape[0], H, W, dev)
@@ -204,7 +204,7 @@ class MAPOptimizer2DTime(object):
         N = B * T * C
         xs = torch.cat([x0.real.reshape(N, 1, H, W), x0.imag.reshape(N, 1, H, W)], dim=0).contiguous().float()
         y = self.measurement.to(dev).to(torch.complex64).reshape(self.measurement.shape[0], N, 1, H, W).contiguous()
-        sens, mask = tfm.sens_f32(dev), tfm.mask_u8(dev)
+        sens, mask = tfm.sens_dev(dev), tfm.mask_u8(dev)
         m, v = torch.zeros_like(xs), torch.zeros_like(xs)
         px = torch.empty_like(xs)
         work = ops.sense_workspace(N, sens.shape[0], H, W, dev)

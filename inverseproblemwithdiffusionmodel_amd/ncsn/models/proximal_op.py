@@ -49,7 +49,7 @@ class L2Penalty(Proximal):
         if isinstance(self.lin_tfm, SENSE):
             zr = torch.view_as_real(z)
             o_re, o_im = ops.sense_l2prox(zr[..., 0].contiguous(), zr[..., 1].contiguous(), y,
-                                          self.lin_tfm.sens_f32(z.device), self.lin_tfm.mask_u8(z.device), c)
+                                          self.lin_tfm.sens_dev(z.device), self.lin_tfm.mask_u8(z.device), c)
             return torch.complex(o_re, o_im)
         if isinstance(self.lin_tfm, RandomUndersamplingFourier):
             return _singlecoil(self.lin_tfm, z, y, c, ops.SC_L2PENALTY)

@@ -152,14 +152,32 @@ def _mask_u8(mask, W, device):
     return (m != 0).to(torch.uint8).contiguous()
 
 
+def _sens_entry(sens, real_name, csm_name, H, W):
+    """entry point for the coil maps' dtype: contiguous GPU [n, H, W], float32 (real maps) or complex64 (measured maps;
+    the *_csm_* kernels).  Anything else -- float64, complex128, a strided view, a CPU tensor -- is refused, never
+    converted: a complex tensor read by a real kernel is interleaved garbage."""
+    if not isinstance(sens, torch.Tensor) or not sens.is_cuda:
+        raise RuntimeError("ipdm: coil maps must be a GPU tensor (the HIP path has no CPU fallback)")
+    if sens.dtype not in (torch.float32, torch.complex64):
+        raise TypeError(f"ipdm: coil maps must be float32 or complex64, got {sens.dtype}")
+    if not sens.is_contiguous():
+        raise TypeError("ipdm: coil maps must be contiguous (call .contiguous() and keep the result)")
+    if sens.dim() != 3 or tuple(sens.shape[-2:]) != (H, W):
+        raise ValueError(f"ipdm: coil maps {tuple(sens.shape)} do not match [n_coils, {H}, {W}]")
+    return csm_name if sens.dtype == torch.complex64 else real_name
+
+
 def sense_forward(x, sens_f32, mask_u8):
-    """sens_f32 None: single coil (S = 1), returns y with a leading axis of length 1"""
+    """sens_f32 None: single coil (S = 1), returns y with a leading axis of length 1; otherwise the coil maps [n, H, W],
+    float32 or complex64"""
     x = _gpu(x, torch.complex64, "x")
     B = x.numel() // (x.shape[-1] * x.shape[-2])
     H, W = x.shape[-2:]
     n = 1 if sens_f32 is None else sens_f32.shape[0]
+    fn = "ipdm_sense_forward_c64" if sens_f32 is None else _sens_entry(sens_f32, "ipdm_sense_forward_c64",
+                                                                        "ipdm_sense_forward_csm_c64", H, W)
     y = torch.empty((n,) + tuple(x.shape), dtype=torch.complex64, device=x.device)
-    call("ipdm_sense_forward_c64", _ptr(x), _ptr(sens_f32), _ptr(mask_u8), mask_u8.shape[0], _ptr(y), B, n, H, W,
+    call(fn, _ptr(x), _ptr(sens_f32), _ptr(mask_u8), mask_u8.shape[0], _ptr(y), B, n, H, W,
          _stream())
     return y
 
@@ -190,9 +208,12 @@ def sense_adjoint(s, sens_f32, mask_u8=None, apply_mask=False):
     n = s.shape[0]
     H, W = s.shape[-2:]
     B = s[0].numel() // (H * W)
+    fn = _sens_entry(sens_f32, "ipdm_sense_adjoint_c64", "ipdm_sense_adjoint_csm_c64", H, W)
+    if sens_f32.shape[0] != n:
+        raise ValueError(f"sense_adjoint: {n} coil images, {sens_f32.shape[0]} coil maps")
     x = torch.empty(tuple(s.shape[1:]), dtype=torch.complex64, device=s.device)
     ws = sense_workspace(B, n, H, W, s.device) if _large_image(H, W) else None
-    call("ipdm_sense_adjoint_c64", _ptr(s), _ptr(sens_f32), _ptr(mask_u8), 1 if mask_u8 is None else mask_u8.shape[0],
+    call(fn, _ptr(s), _ptr(sens_f32), _ptr(mask_u8), 1 if mask_u8 is None else mask_u8.shape[0],
          int(bool(apply_mask)), _ptr(x), _ptr(ws), B, n, H, W, _stream())
     return x
 
@@ -213,11 +234,14 @@ def sense_l2prox(z_re, z_im, y, sens_f32, mask_u8, coef, out_re=None, out_im=Non
     y = _gpu(y, torch.complex64, "y")
     H, W = z_re.shape[-2:]
     B = z_re.numel() // (H * W)
+    fn = _sens_entry(sens_f32, "ipdm_sense_l2prox_f32", "ipdm_sense_l2prox_csm_f32", H, W)
+    if y.numel() != sens_f32.shape[0] * B * H * W:
+        raise ValueError("sense_l2prox: measurement does not match [n_coils, B, H, W]")
     out_re = torch.empty_like(z_re) if out_re is None else out_re
     out_im = torch.empty_like(z_im) if out_im is None else out_im
     work = sense_workspace(B, sens_f32.shape[0], H, W, z_re.device) if work is None else work
     _check_work(work, B, sens_f32.shape[0], H, W, "sense_l2prox")
-    call("ipdm_sense_l2prox_f32", _ptr(z_re), _ptr(z_im), _ptr(y), _ptr(sens_f32), _ptr(mask_u8), mask_u8.shape[0],
+    call(fn, _ptr(z_re), _ptr(z_im), _ptr(y), _ptr(sens_f32), _ptr(mask_u8), mask_u8.shape[0],
          float(coef), _ptr(out_re), _ptr(out_im), _ptr(work), B, sens_f32.shape[0], H, W, _stream())
     _written(out_re, out_im)
     return out_re, out_im
@@ -225,9 +249,11 @@ def sense_l2prox(z_re, z_im, y, sens_f32, mask_u8, coef, out_re=None, out_im=Non
 
 def ald_sense_step(x_re, x_im, g_re, g_im, y, sens_f32, mask_u8, work, step=0.0, noise_scale=0.0, coef=0.0,
                    noise_re=None, noise_im=None, seed=0, sample_offset=0, step_id=0, dev_sched=None):
-    """in place on x_re / x_im.  dev_sched: uint8/any device tensor holding an ipdm_sched_t."""
-    for t, n in ((x_re, "x_re"), (x_im, "x_im"), (g_re, "g_re"), (g_im, "g_im"), (sens_f32, "sens")):
+    """in place on x_re / x_im.  dev_sched: uint8/any device tensor holding an ipdm_sched_t.  sens_f32: the coil maps,
+    float32 or complex64."""
+    for t, n in ((x_re, "x_re"), (x_im, "x_im"), (g_re, "g_re"), (g_im, "g_im")):
         _inplace_operand(t, torch.float32, n)
+    fn = _sens_entry(sens_f32, "ipdm_ald_sense_step_f32", "ipdm_ald_sense_step_csm_f32", *x_re.shape[-2:])
     _inplace_operand(y, torch.complex64, "y")
     for t, n in ((noise_re, "noise_re"), (noise_im, "noise_im")):
         if t is not None:
@@ -237,7 +263,7 @@ def ald_sense_step(x_re, x_im, g_re, g_im, y, sens_f32, mask_u8, work, step=0.0,
     if g_re.numel() != x_re.numel() or g_im.numel() != x_im.numel() or y.numel() != sens_f32.shape[0] * B * H * W:
         raise ValueError("ald_sense_step: operand sizes do not match the state")
     _check_work(work, B, sens_f32.shape[0], H, W, "ald_sense_step")
-    call("ipdm_ald_sense_step_f32", _ptr(x_re), _ptr(x_im), _ptr(g_re), _ptr(g_im), _ptr(noise_re), _ptr(noise_im),
+    call(fn, _ptr(x_re), _ptr(x_im), _ptr(g_re), _ptr(g_im), _ptr(noise_re), _ptr(noise_im),
          float(step), float(noise_scale), int(seed), int(sample_offset), int(step_id), _ptr(dev_sched),
          _ptr(y), _ptr(sens_f32), _ptr(mask_u8), mask_u8.shape[0], float(coef), _ptr(work), B, sens_f32.shape[0], H, W,
          _stream())

@@ -71,3 +71,23 @@ def phantom_image(H=128, W=128, seed=0, n_ellipses=6, phase_patch=(5, 5)):
     phase = F.interpolate(patch, size=(H, W), mode="bicubic", align_corners=True)[0, 0]
     img = torch.polar(mag, phase).to(torch.complex64)
     return img[None, None]
+
+
+def complex_coil_maps(n, H, W, seed=0):
+    """complex128 (n, H, W) coil sensitivity maps for runs without external data: the magnitudes of the synthetic "exp"
+    maps (SENSE("exp", ...): exp(-dist / 2l) around a seeded anchor) times a smooth seeded phase, a second-order
+    polynomial in the normalised coordinates with coefficients drawn from N(0, 1) per coil; RSS-normalised (the phase has
+    unit modulus, so the "exp" normalisation carries over)."""
+    import numpy as np
+    from .ncsn.linear_transforms.undersampling_fourier import SENSE
+    mag = SENSE("exp", n, 8, 0.04, (1, H, W), seed=seed, mask_mode="uniform").sens_maps.numpy()
+    rng = np.random.RandomState(seed)
+    u = np.linspace(-1.0, 1.0, H)[:, None]
+    v = np.linspace(-1.0, 1.0, W)[None, :]
+    maps = np.empty((n, H, W), dtype=np.complex128)
+    for i in range(n):
+        a = rng.randn(6)
+        phase = a[0] + a[1] * u + a[2] * v + a[3] * u * v + a[4] * u * u + a[5] * v * v
+        maps[i] = mag[i] * np.exp(1j * np.pi * 0.5 * phase)
+    maps /= np.sqrt((np.abs(maps) ** 2).sum(0))
+    return torch.from_numpy(maps)

@@ -23,11 +23,16 @@ if __name__ == '__main__':
     parser.add_argument("--save_dir", default="../outputs")
     parser.add_argument("--lamda", type=float, default=1e-2)
     parser.add_argument("--n_iters", type=int, default=None, help="default: config.MAP.n_iters")
+    parser.add_argument("--sens_maps", default=None,
+                        help=".npy / .pt file with measured coil maps (num_sens, H, W), real or complex")
+    parser.add_argument("--sens_phase", action="store_true",
+                        help="synthetic COMPLEX coil maps: the exp magnitudes times a smooth seeded phase")
     args_dict = vars(parser.parse_args())
 
     from inverseproblemwithdiffusionmodel_amd import engine
     from inverseproblemwithdiffusionmodel_amd.ncsn.linear_transforms.undersampling_fourier import SENSE
     from inverseproblemwithdiffusionmodel_amd.ncsn.models.MAP_optimizers import SENSEMAP
+    from inverseproblemwithdiffusionmodel_amd.helpers.load_data import driver_sens_maps
     from inverseproblemwithdiffusionmodel_amd.synthetic import phantom_image
 
     device = torch.device("cuda")
@@ -35,8 +40,12 @@ if __name__ == '__main__':
     if args_dict["n_iters"]:
         cfg.MAP.n_iters = args_dict["n_iters"]
     scorenet = engine.build_scorenet(cfg, args_dict["seed"])
+    sens_maps, args_dict["num_sens"] = driver_sens_maps(args_dict["sens_maps"], args_dict["sens_phase"], args_dict["num_sens"],
+                                                        128, 128, args_dict["seed"])
     op = SENSE(args_dict["sens_type"], args_dict["num_sens"], args_dict["R"], args_dict["center_lines_frac"], (1, 128, 128),
                args_dict["seed"])
+    if sens_maps is not None:
+        op.sens_maps = sens_maps
     img = phantom_image(128, 128, seed=args_dict["seed"] + args_dict["ds_idx"]).to(device)
     measurement = op(img)
     x_init = op.conj_op(measurement).clone()
@@ -54,5 +63,7 @@ if __name__ == '__main__':
     torch.save(x.cpu(), os.path.join(save_dir, "reconstructions.pt"))
     torch.save(zf.cpu(), os.path.join(save_dir, "ZF.pt"))
     torch.save(op.random_under_fourier.mask, os.path.join(save_dir, "mask.pt"))
+    if sens_maps is not None:
+        torch.save(op.sens_maps, os.path.join(save_dir, "sens_maps.pt"))
     with open(os.path.join(save_dir, "args_dict.pkl"), "wb") as wf:
         pickle.dump(args_dict, wf)

@@ -27,13 +27,20 @@ if __name__ == '__main__':
     parser.add_argument("--save_dir", default="../outputs")
     parser.add_argument("--log_dir", default="SENSE")
     parser.add_argument("--image_size", type=int, default=128)
+    parser.add_argument("--sens_maps", default=None,
+                        help=".npy / .pt file with measured coil maps (num_sens, H, W), real or complex")
+    parser.add_argument("--sens_phase", action="store_true",
+                        help="synthetic COMPLEX coil maps: the exp magnitudes times a smooth seeded phase")
     args_dict = vars(parser.parse_args())
 
     from inverseproblemwithdiffusionmodel_amd.ncsn.linear_transforms.undersampling_fourier import SENSE
     from inverseproblemwithdiffusionmodel_amd.ncsn.models.MAP_optimizers import MAPModel, TotalVariation
+    from inverseproblemwithdiffusionmodel_amd.helpers.load_data import driver_sens_maps
     from inverseproblemwithdiffusionmodel_amd.synthetic import phantom_image
     device = torch.device("cuda")
     H = args_dict["image_size"]
+    sens_maps, args_dict["num_sens"] = driver_sens_maps(args_dict["sens_maps"], args_dict["sens_phase"], args_dict["num_sens"],
+                                                        H, H, args_dict["seed"])
     try:
         op = SENSE(args_dict["sens_type"], args_dict["num_sens"], args_dict["R"], args_dict["center_lines_frac"], (1, H, H),
                    args_dict["seed"])
@@ -43,6 +50,8 @@ if __name__ == '__main__':
         print(f"no mask parameter set for R={args_dict['R']}: using the reference's live T=24 mask")
         op = SENSE(args_dict["sens_type"], args_dict["num_sens"], args_dict["R"], args_dict["center_lines_frac"], (1, H, H),
                    args_dict["seed"], mask_T=24)
+    if sens_maps is not None:
+        op.sens_maps = sens_maps
     img_complex = phantom_image(H, H, seed=args_dict["seed"] + args_dict["ds_idx"]).to(device)      # (1, 1, H, W)
     measurement = op(img_complex)                                                                   # (num_sens, 1, 1, H, W)
     model = MAPModel(measurement, op, TotalVariation(), args_dict["reg_weight"], device=device)
@@ -65,5 +74,7 @@ if __name__ == '__main__':
     torch.save(measurement.cpu(), os.path.join(save_dir, "measurement.pt"))
     torch.save(direct_recons.cpu(), os.path.join(save_dir, "ZF.pt"))
     torch.save(img_out.cpu(), os.path.join(save_dir, "reconstructions.pt"))
+    if sens_maps is not None:
+        torch.save(op.sens_maps, os.path.join(save_dir, "sens_maps.pt"))
     with open(os.path.join(save_dir, "args_dict.pkl"), "wb") as wf:
         pickle.dump(args_dict, wf)

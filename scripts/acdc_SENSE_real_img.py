@@ -39,6 +39,10 @@ if __name__ == '__main__':
     parser.add_argument("--ckpt", default=None, help="Lightning .ckpt of the reference (EMA weights); default: synthetic")
     parser.add_argument("--n_levels", type=int, default=None, help="run only the first n noise levels")
     parser.add_argument("--seg_ckpt", default=None, help="Lightning TrainSeg .ckpt (MONAI UNet weights) for the guidance")
+    parser.add_argument("--sens_maps", default=None,
+                        help=".npy / .pt file with measured coil maps (num_sens, H, W), real or complex")
+    parser.add_argument("--sens_phase", action="store_true",
+                        help="synthetic COMPLEX coil maps: the exp magnitudes times a smooth seeded phase")
     parser.add_argument("--seg_synthetic", action="store_true",
                         help="run the guidance with seeded random UNet weights (exercises the path; not meaningful imaging)")
     args_dict = vars(parser.parse_args())
@@ -60,8 +64,17 @@ if __name__ == '__main__':
     scorenet = engine.build_scorenet(cfg, args_dict["seed"])
     if args_dict["ckpt"]:
         load_scorenet_weights(scorenet, args_dict["ckpt"])
+    sens_maps = None
+    if args_dict["sens_maps"]:
+        from inverseproblemwithdiffusionmodel_amd.helpers.load_data import load_sens_maps
+        sens_maps = load_sens_maps(args_dict["sens_maps"])
+        args_dict["num_sens"] = sens_maps.shape[0]
+    elif args_dict["sens_phase"]:
+        from inverseproblemwithdiffusionmodel_amd.synthetic import complex_coil_maps
+        sens_maps = complex_coil_maps(args_dict["num_sens"], H, H, args_dict["seed"])
     prob = engine.build_problem(device, n_local, R=args_dict["R"], H=H, W=H, num_sens=args_dict["num_sens"],
-                                seed=args_dict["seed"], scorenet=scorenet, cfg=cfg, lr_scaled=args_dict["lr_scaled"])
+                                seed=args_dict["seed"], scorenet=scorenet, cfg=cfg, lr_scaled=args_dict["lr_scaled"],
+                                sens_maps=sens_maps)
     label = None
     if args_dict["seg_start_time"] < 1.:
         from inverseproblemwithdiffusionmodel_amd.helpers.load_model import reload_model
@@ -98,6 +111,8 @@ if __name__ == '__main__':
         torch.save(img_out.cpu(), os.path.join(save_dir, "reconstructions.pt"))
         torch.save(direct_recons.cpu(), os.path.join(save_dir, "ZF.pt"))
         torch.save(prob.op.random_under_fourier.mask, os.path.join(save_dir, "mask.pt"))
+        if sens_maps is not None:
+            torch.save(prob.op.sens_maps, os.path.join(save_dir, "sens_maps.pt"))
         if post is not None:
             torch.save({k: v.cpu() for k, v in post.items()}, os.path.join(save_dir, "posterior.pt"))
         with open(os.path.join(save_dir, "args_dict.pkl"), "wb") as wf:

@@ -36,11 +36,16 @@ if __name__ == '__main__':
     parser.add_argument("--beta1", type=float, default=0.9)
     parser.add_argument("--beta2", type=float, default=0.999)
     parser.add_argument("--max_iter", type=int, default=20)          # (LBFGS option of the reference; unused: Adam only)
+    parser.add_argument("--sens_maps", default=None,
+                        help=".npy / .pt file with measured coil maps (num_sens, H, W), real or complex")
+    parser.add_argument("--sens_phase", action="store_true",
+                        help="synthetic COMPLEX coil maps: the exp magnitudes times a smooth seeded phase")
     args_dict = vars(parser.parse_args())
 
     from inverseproblemwithdiffusionmodel_amd.helpers.load_model import reload_model
     from inverseproblemwithdiffusionmodel_amd.ncsn.linear_transforms.undersampling_fourier import SENSE
     from inverseproblemwithdiffusionmodel_amd.ncsn.models.MAP_optimizers import MAPOptimizer2DTime
+    from inverseproblemwithdiffusionmodel_amd.helpers.load_data import driver_sens_maps
     from inverseproblemwithdiffusionmodel_amd.synthetic import phantom_image
     device = torch.device("cuda")
     np.random.seed(args_dict["seed"])
@@ -50,8 +55,12 @@ if __name__ == '__main__':
     T, C = scorenet_T.config.data.image_size, scorenet.config.data.channels
     H = W = scorenet.config.data.image_size
     B = args_dict["num_samples"]
+    sens_maps, args_dict["num_sens"] = driver_sens_maps(args_dict["sens_maps"], args_dict["sens_phase"], args_dict["num_sens"],
+                                                        H, W, args_dict["seed"])
     op = SENSE(args_dict["sens_type"], args_dict["num_sens"], args_dict["R"], args_dict["center_lines_frac"], (C, H, W),
                args_dict["seed"], mask_T=24 if T == 24 else 1)
+    if sens_maps is not None:
+        op.sens_maps = sens_maps
     base = phantom_image(H, W, seed=args_dict["seed"] + args_dict["ds_idx"]).to(device)
     beat = torch.cos(torch.arange(T, device=device) * (2 * torch.pi / T)).view(T, 1, 1, 1)
     img_complex = (base * (1.0 + 0.1 * beat)).to(torch.complex64)                 # (T, 1, H, W)
@@ -81,5 +90,7 @@ if __name__ == '__main__':
     torch.save(direct_recons.cpu(), os.path.join(save_dir, "ZF.pt"))
     torch.save(img_out.cpu(), os.path.join(save_dir, "reconstructions.pt"))
     torch.save(op.random_under_fourier.mask, os.path.join(save_dir, "mask.pt"))
+    if sens_maps is not None:
+        torch.save(op.sens_maps, os.path.join(save_dir, "sens_maps.pt"))
     with open(os.path.join(save_dir, "args_dict.pkl"), "wb") as wf:
         pickle.dump(args_dict, wf)
