@@ -186,6 +186,48 @@ int ipdm_ald_sense_step_csm_f32(float* x_re, float* x_im, const float* g_re, con
                                 const ipdm_sched_t* dev_sched, const float* y, const float* sens, const uint8_t* mask,
                                 int mask_t, float coef, float* work, int B, int n_coils, int H, int W, void* stream);
 
+/* Exact multi-coil proximal by conjugate gradients (the argmin that L2Penalty's docstring states and its
+ * check_solution tests, proximal_op.py:19-69; the one-step operators above miss it by orders of magnitude):
+ *   x = argmin 1/2 |x - z|^2 + a/2 |A x - y|^2   <=>   (I + a A^H A) x = z + a A^H y,   a = alpha/lamda (by the caller)
+ * Plain CG per sample on complex vectors with real dot products, warm start x0 = z.  Sample b stops when
+ * |r| <= tol * |b|, b = z + a A^H y, or after max_iter iterations; a stopped sample is frozen (its x no longer changes)
+ * and samples never interact, so a sample's result does not depend on its batch.  tol == 0 runs max_iter iterations;
+ * a sample whose <r,r> or <p,Np> is not positive is frozen instead of divided by (z = 0, y = 0 returns exactly 0);
+ * a == 0 returns z bit for bit.  max_iter < 1, tol < 0 or not finite: IPDM_EINVAL.
+ *   z_re / z_im -> out_re / out_im   planar float32 [B][H][W], may alias
+ *   ahy         optional A^H y, complex64 [B][H][W] (constant over a sampler run); NULL: formed into the workspace
+ *   iters_out   optional device int32 [B]: CG iterations each sample ran
+ *   work        ipdm_sense_cg_workspace_bytes(B, n_coils, H, W)
+ * Sizes as the other SENSE operators (power-of-two sides: up to 128x128 in LDS, up to 2048 by row / column passes),
+ * anything else IPDM_EUNSUPPORTED.  The launch sequence is fixed by (max_iter, size) alone -- it does not depend on
+ * convergence -- and the calls are asynchronous, allocation-free and hipGraph-capturable.  Deterministic (no atomics). */
+int64_t ipdm_sense_cg_workspace_bytes(int B, int n_coils, int H, int W);
+int ipdm_sense_cgprox_f32(const float* z_re, const float* z_im, const float* y, const float* sens,
+                          const uint8_t* mask, int mask_t, float a, const float* ahy, int max_iter, float tol,
+                          float* out_re, float* out_im, float* work, int32_t* iters_out, int B, int n_coils, int H, int W,
+                          void* stream);
+/* the same with complex coil maps (interleaved complex64 [n_coils][H][W]) */
+int ipdm_sense_cgprox_csm_f32(const float* z_re, const float* z_im, const float* y, const float* sens,
+                              const uint8_t* mask, int mask_t, float a, const float* ahy, int max_iter, float tol,
+                              float* out_re, float* out_im, float* work, int32_t* iters_out, int B, int n_coils, int H, int W,
+                              void* stream);
+/* ipdm_ald_sense_step_f32 with the CG proximal as its data-consistency operator: Langevin update of both planes (same
+ * scalars, noise and Philox keying), then x = the solution above with z the updated state.  `coef` (dev_sched->coef
+ * when a device schedule is given) carries a = alpha/lamda, as for the SingleCoil closed form; ahy, max_iter, tol,
+ * iters_out and work as ipdm_sense_cgprox_f32. */
+int ipdm_ald_sense_cg_step_f32(float* x_re, float* x_im, const float* g_re, const float* g_im,
+                               const float* noise_re, const float* noise_im,
+                               float step, float noise_scale, uint64_t seed, int64_t sample_offset, int64_t step_id,
+                               const ipdm_sched_t* dev_sched, const float* y, const float* sens, const uint8_t* mask,
+                               int mask_t, float coef, float* work, const float* ahy, int max_iter, float tol,
+                               int32_t* iters_out, int B, int n_coils, int H, int W, void* stream);
+int ipdm_ald_sense_cg_step_csm_f32(float* x_re, float* x_im, const float* g_re, const float* g_im,
+                                   const float* noise_re, const float* noise_im,
+                                   float step, float noise_scale, uint64_t seed, int64_t sample_offset, int64_t step_id,
+                                   const ipdm_sched_t* dev_sched, const float* y, const float* sens, const uint8_t* mask,
+                                   int mask_t, float coef, float* work, const float* ahy, int max_iter, float tol,
+                                   int32_t* iters_out, int B, int n_coils, int H, int W, void* stream);
+
 /* Single-coil data-consistency operators (A = M F, RandomUndersamplingFourier, no coil maps) on planar real/imag
  * float32 [B][H][W], y [B][H][W] complex64; out may alias z.  mode:
  *   0  L2Penalty on a single-coil operator (proximal_op.py:19-51): x = z - coef * F^-1[M (M F z - y)],

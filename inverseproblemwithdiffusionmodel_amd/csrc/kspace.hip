@@ -14,14 +14,6 @@ namespace {
 
 using namespace ipdm_kspace;
 
-#define FFT_LDS_SETUP(H, W)                                   \
-  extern __shared__ __align__(16) unsigned char smem_raw[];  \
-  FftLds L;                                                   \
-  L.buf = reinterpret_cast<float2*>(smem_raw);               \
-  L.tw = L.buf + (size_t)(H) * (W);                          \
-  L.twN = (H) > (W) ? (H) : (W);                             \
-  fft_make_twiddles(L);
-
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(FFT_THREADS) void fft2c_lds_kernel(const float2* in, float2* out,
                                                                 int H, int W, int inverse) {
@@ -268,28 +260,6 @@ __global__ __launch_bounds__(FFT_THREADS) void ald_sense_step_kernel(
 // function of (seed, sample, step, element)), does ITS coil's transform pair and writes r_c = conj-free S_c F^-1[M (F S_c z - y_c)]
 // to work[b][coil]; ald_sense_combine_kernel then forms z once more and x = z - coef * (((r_0 + r_1) + r_2) + ...) in the
 // sequential kernel's order: bit-identical results, 56 workgroups instead of 14, one transform pair deep instead of four.
-__device__ __forceinline__ void langevin_value(const float* xr, const float* xi, const float* __restrict__ g_re,
-                                               const float* __restrict__ g_im, const float* __restrict__ n_re,
-                                               const float* __restrict__ n_im, float step, float noise_scale, uint64_t seed,
-                                               int64_t sample_offset, int64_t step_id, int b, int HW, int e, float& zr,
-                                               float& zi) {
-  const size_t gi = (size_t)b * HW + e;
-  float nr, ni;
-  if (n_re) {
-    nr = n_re[gi];
-    ni = n_im[gi];
-  } else {
-    float q[4];
-    const int lane4 = e & 3;
-    ipdm_philox_normal4(seed, sample_offset + b, step_id, 0, (uint32_t)(e >> 2), q);
-    nr = lane4 == 0 ? q[0] : lane4 == 1 ? q[1] : lane4 == 2 ? q[2] : q[3];
-    ipdm_philox_normal4(seed, sample_offset + b, step_id, 1, (uint32_t)(e >> 2), q);
-    ni = lane4 == 0 ? q[0] : lane4 == 1 ? q[1] : lane4 == 2 ? q[2] : q[3];
-  }
-  zr = xr[e] + step * g_re[gi] + nr * noise_scale;
-  zi = xi[e] + step * g_im[gi] + ni * noise_scale;
-}
-
 template <bool LANGEVIN, typename SensT>
 __global__ __launch_bounds__(FFT_THREADS) void ald_sense_coil_kernel(
     const float* x_re, const float* x_im, const float* __restrict__ g_re, const float* __restrict__ g_im,
@@ -453,14 +423,6 @@ __global__ __launch_bounds__(FFT_THREADS) void ald_singlecoil_step_kernel(
       xi[e] = v.y * w;
     }
   }
-}
-
-template <typename K>
-static int set_lds_limit(K kernel, size_t bytes) {
-  if (bytes <= 64 * 1024) return IPDM_OK;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)bytes);
-  return e == hipSuccess ? IPDM_OK : (int)e;
 }
 
 template <bool LANGEVIN, typename SensT>

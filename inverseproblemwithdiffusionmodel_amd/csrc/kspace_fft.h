@@ -143,6 +143,48 @@ __device__ __forceinline__ bool mask_at(const uint8_t* mask, int mask_t, int b, 
   return mask[(size_t)(mask_t == 1 ? 0 : b % mask_t) * W + c] != 0;
 }
 
+// whole-image LDS kernels (kspace.hip, kspace_cg.hip): the image followed by the twiddle table in dynamic LDS
+#define FFT_LDS_SETUP(H, W)                                   \
+  extern __shared__ __align__(16) unsigned char smem_raw[];  \
+  FftLds L;                                                   \
+  L.buf = reinterpret_cast<float2*>(smem_raw);               \
+  L.tw = L.buf + (size_t)(H) * (W);                          \
+  L.twN = (H) > (W) ? (H) : (W);                             \
+  fft_make_twiddles(L);
+
+// z = x + step*g + noise_scale*n at element e of sample b, in registers (the coil-parallel iteration tails: every
+// workgroup of a sample forms the same z); n injected (n_re/n_im) or Philox keyed by (seed, global sample id, step, plane)
+__device__ __forceinline__ void langevin_value(const float* xr, const float* xi, const float* __restrict__ g_re,
+                                               const float* __restrict__ g_im, const float* __restrict__ n_re,
+                                               const float* __restrict__ n_im, float step, float noise_scale, uint64_t seed,
+                                               int64_t sample_offset, int64_t step_id, int b, int HW, int e, float& zr,
+                                               float& zi) {
+  const size_t gi = (size_t)b * HW + e;
+  float nr, ni;
+  if (n_re) {
+    nr = n_re[gi];
+    ni = n_im[gi];
+  } else {
+    float q[4];
+    const int lane4 = e & 3;
+    ipdm_philox_normal4(seed, sample_offset + b, step_id, 0, (uint32_t)(e >> 2), q);
+    nr = lane4 == 0 ? q[0] : lane4 == 1 ? q[1] : lane4 == 2 ? q[2] : q[3];
+    ipdm_philox_normal4(seed, sample_offset + b, step_id, 1, (uint32_t)(e >> 2), q);
+    ni = lane4 == 0 ? q[0] : lane4 == 1 ? q[1] : lane4 == 2 ? q[2] : q[3];
+  }
+  zr = xr[e] + step * g_re[gi] + nr * noise_scale;
+  zi = xi[e] + step * g_im[gi] + ni * noise_scale;
+}
+
+// raise a kernel's dynamic-LDS limit above the 64 KiB default
+template <typename K>
+static inline int set_lds_limit(K kernel, size_t bytes) {
+  if (bytes <= 64 * 1024) return IPDM_OK;
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)bytes);
+  return e == hipSuccess ? IPDM_OK : (int)e;
+}
+
 }  // namespace ipdm_kspace
 
 // row / column-pass operators for power-of-two images beyond the LDS (kspace_large.hip)
@@ -162,4 +204,13 @@ int prox_step(float* x_re, float* x_im, const float* g_re, const float* g_im, co
               float step, float noise_scale, uint64_t seed, int64_t sample_offset, int64_t step_id,
               const ipdm_sched_t* sched, const float2* y, const SensT* sens, const uint8_t* mask, int mask_t, float coef,
               int mode, float2* ws, int B, int n_coils, int H, int W, hipStream_t s);
+// the conjugate-gradient proximal's pieces (kspace_cg.hip).  langevin: the planar update x += step*g + noise_scale*n alone.
+// normal_op: out[b] = A^H (A v - y) with v complex (xc) or planar (x_re, x_im; xc NULL) and y NULL for A^H A v alone;
+// ws holds n_coils*B images and out must not overlap it.
+int langevin(float* x_re, float* x_im, const float* g_re, const float* g_im, const float* n_re, const float* n_im, float step,
+             float noise_scale, uint64_t seed, int64_t sample_offset, int64_t step_id, const ipdm_sched_t* sched, int B, int H,
+             int W, hipStream_t s);
+template <typename SensT>
+int normal_op(const float2* xc, const float* x_re, const float* x_im, const float2* y, const SensT* sens, const uint8_t* mask,
+              int mask_t, float2* out, float2* ws, int B, int n_coils, int H, int W, hipStream_t s);
 }  // namespace ipdm_kspace_large

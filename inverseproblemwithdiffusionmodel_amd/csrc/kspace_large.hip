@@ -157,7 +157,7 @@ struct ColsInvFromS {
 struct ColsProx {
   ImgGeo g;
   float2* tmp;
-  const float2* y;                 // [coil][b][H][W]
+  const float2* y;                 // [coil][b][H][W]; NULL (mode <= 0 only): y = 0, the normal operator A^H A alone
   const uint8_t* mask;
   int mask_t, mode;
   float scale, coef_host;
@@ -174,7 +174,7 @@ struct ColsProx {
     v.x *= scale;
     v.y *= scale;
     const bool m = mask_at(mask, mask_t, b, g.W, c);
-    const float2 yy = y[g.at(coil, b, r, c)];
+    const float2 yy = y ? y[g.at(coil, b, r, c)] : make_float2(0.f, 0.f);
     const float sg = sign_rc(r, c);
     if (mode <= 0) return m ? make_float2(v.x - sg * yy.x, v.y - sg * yy.y) : make_float2(0.f, 0.f);
     const float coef = sched ? sched->coef : coef_host;
@@ -397,6 +397,40 @@ template int sense_adjoint<float>(const float2*, const float*, const uint8_t*, i
 template int sense_adjoint<float2>(const float2*, const float2*, const uint8_t*, int, int, float2*, float*, float2*, int, int,
                                    int, int, hipStream_t);
 
+static int launch_langevin(float* x_re, float* x_im, const float* g_re, const float* g_im, const float* n_re,
+                           const float* n_im, float step, float noise_scale, uint64_t seed, int64_t sample_offset,
+                           int64_t step_id, const ipdm_sched_t* sched, int B, int HW, hipStream_t s) {
+  int gx = (HW / 4 + 255) / 256;
+  if (gx > 256) gx = 256;
+  hipLaunchKernelGGL(langevin_planes_kernel, dim3(gx, B), dim3(256), 0, s, x_re, x_im, g_re, g_im, n_re, n_im, step,
+                     noise_scale, seed, (long long)sample_offset, (long long)step_id, sched, HW);
+  return ipdm_launch_status();
+}
+
+int langevin(float* x_re, float* x_im, const float* g_re, const float* g_im, const float* n_re, const float* n_im, float step,
+             float noise_scale, uint64_t seed, int64_t sample_offset, int64_t step_id, const ipdm_sched_t* sched, int B, int H,
+             int W, hipStream_t s) {
+  return launch_langevin(x_re, x_im, g_re, g_im, n_re, n_im, step, noise_scale, seed, sample_offset, step_id, sched, B, H * W, s);
+}
+
+// out[b] = A^H (A v - y): the proximal chain's three passes with the coil sum stored instead of applied
+template <typename SensT>
+int normal_op(const float2* xc, const float* x_re, const float* x_im, const float2* y, const SensT* sens, const uint8_t* mask,
+              int mask_t, float2* out, float2* ws, int B, int n_coils, int H, int W, hipStream_t s) {
+  const ImgGeo g{B, H, W};
+  RowsFwd<SensT> rf{g, xc, x_re, x_im, sens, ws};
+  int rc = launch_rows(rf, B, n_coils, H, W, 0, s);
+  if (rc) return rc;
+  ColsProx cp{g, ws, y, mask, mask_t, 0, 1.f / sqrtf((float)H * (float)W), 0.f, nullptr};
+  rc = launch_cols<ColsProx, true>(cp, B, n_coils, H, W, 0, s);
+  if (rc) return rc;
+  return launch_accum<FIN_ADJOINT>(ws, sens, out, nullptr, nullptr, nullptr, nullptr, 0.f, B, n_coils, H, W, s);
+}
+template int normal_op<float>(const float2*, const float*, const float*, const float2*, const float*, const uint8_t*, int,
+                              float2*, float2*, int, int, int, int, hipStream_t);
+template int normal_op<float2>(const float2*, const float*, const float*, const float2*, const float2*, const uint8_t*, int,
+                               float2*, float2*, int, int, int, int, hipStream_t);
+
 // Langevin (optional) + data-consistency operator on planar x (in place).  sens NULL = single coil; mode as ColsProx.
 template <typename SensT>
 int prox_step(float* x_re, float* x_im, const float* g_re, const float* g_im, const float* n_re, const float* n_im,
@@ -405,11 +439,7 @@ int prox_step(float* x_re, float* x_im, const float* g_re, const float* g_im, co
               int mode, float2* ws, int B, int n_coils, int H, int W, hipStream_t s) {
   const int HW = H * W;
   if (g_re) {
-    int gx = (HW / 4 + 255) / 256;
-    if (gx > 256) gx = 256;
-    hipLaunchKernelGGL(langevin_planes_kernel, dim3(gx, B), dim3(256), 0, s, x_re, x_im, g_re, g_im, n_re, n_im, step,
-                       noise_scale, seed, (long long)sample_offset, (long long)step_id, sched, HW);
-    int rc = ipdm_launch_status();
+    int rc = launch_langevin(x_re, x_im, g_re, g_im, n_re, n_im, step, noise_scale, seed, sample_offset, step_id, sched, B, HW, s);
     if (rc) return rc;
   }
   // (the 128x128 kernel returns early when coef == 0; here the schedule value lives on the device, so the chain always

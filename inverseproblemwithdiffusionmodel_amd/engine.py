@@ -56,9 +56,11 @@ def build_scorenet(cfg, seed=0):
 
 
 def build_problem(device, n_samples, R=40, H=128, W=128, num_sens=4, seed=0, scorenet=None, cfg=None, lr_scaled=1.0,
-                  sens_maps=None):
+                  sens_maps=None, proximal="L2Penalty", proximal_kwargs=None):
     """-> Namespace(sampler, scorenet, sigmas, op, image, measurement, call_kwargs); sens_maps: measured coil maps
-    (num_sens, H, W), real or complex, instead of the synthetic "exp" maps (RSS-normalised where non-zero)"""
+    (num_sens, H, W), real or complex, instead of the synthetic "exp" maps (RSS-normalised where non-zero); proximal: a
+    get_proximal name ("L2PenaltyCG": the exact proximal, proximal_kwargs = dict(max_iter=, tol=))"""
+    prox_cls = get_proximal(proximal)                        # an unknown name fails here, before any GPU work
     cfg = acdc_config(device, H) if cfg is None else cfg
     scorenet = build_scorenet(cfg, seed) if scorenet is None else scorenet
     sigmas = get_sigmas(cfg, "recons")
@@ -70,7 +72,7 @@ def build_problem(device, n_samples, R=40, H=128, W=128, num_sens=4, seed=0, sco
     meas = op(img).repeat(1, n_samples, 1, 1, 1).contiguous()
     params = dict(n_steps_each=cfg.sampling.n_steps_each, step_lr=cfg.sampling.step_lr, denoise=True,
                   final_only=True)
-    sampler = ALDInvSegProximalRealImag(get_proximal("L2Penalty")(op), 1.0, "linear", (n_samples, 1, H, W), scorenet,
+    sampler = ALDInvSegProximalRealImag(prox_cls(op, **(proximal_kwargs or {})), 1.0, "linear", (n_samples, 1, H, W), scorenet,
                                         sigmas, params, cfg, meas, op, seg=None, device=device)
     return Namespace(sampler=sampler, scorenet=scorenet, sigmas=sigmas, op=op, image=img, measurement=meas, cfg=cfg,
                      params=params, call_kwargs=dict(label=None, lamda=0.1, save_dir=None, lr_scaled=lr_scaled,
@@ -101,8 +103,9 @@ class IterationRunner:
         self.levels = lv
         self.table_dev = torch.from_numpy(table.view(np.uint8).reshape(L * n_each, -1).copy()).to(dev)
         self.label_table = torch.arange(L, device=dev)[:, None].repeat(1, 2 * B)
+        cg, work = s._cg_state(B, s.linear_tfm.sens_maps.shape[0], H, W, dev, x0)
         self.st = dict(x=self.x, B=B, y=meas, sc_mode=None, sens=s.linear_tfm.sens_dev(dev), mask=s.linear_tfm.mask_u8(dev),
-                       work=ops_mod.sense_workspace(B, s.linear_tfm.sens_maps.shape[0], H, W, dev),
+                       work=work, cg=cg,
                        labels=torch.zeros(2 * B, dtype=torch.long, device=dev), noise_re=None, noise_im=None,
                        seed=seed, sample_offset=sample_offset,
                        sched_dev=torch.zeros(SCHED_DTYPE.itemsize, dtype=torch.uint8, device=dev))

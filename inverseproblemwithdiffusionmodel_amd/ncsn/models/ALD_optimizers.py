@@ -8,6 +8,7 @@ everything per pixel runs in libipdm.so.  For the SENSE sampler one iteration is
     score network on the (2B, 1, H, W) batch [real planes | imaginary planes]   (InstanceNorm is per image,
                                                so batching the two reference passes is exact)
     one fused kernel: Langevin update of both planes + L2Penalty proximal (FFT in LDS)
+    (with ``L2PenaltyCG``: the same Langevin update + the exact proximal by conjugate gradients, a fixed launch sequence)
 and, with ``use_graph=True`` (default), the whole iteration is captured once into a hipGraph and replayed
 for all L * n_steps_each steps; per-step scalars live in a device-side ipdm_sched_t.
 
@@ -29,7 +30,7 @@ import numpy as np
 import torch
 
 from ... import ops
-from .proximal_op import Proximal, L2Penalty, Constrained, SingleCoil  # noqa: F401
+from .proximal_op import Proximal, L2Penalty, L2PenaltyCG, Constrained, SingleCoil  # noqa: F401
 from ..linear_transforms.undersampling_fourier import SENSE, RandomUndersamplingFourier
 from ...helpers.utils import data_transform, reshape_temporal_dim
 from ..linear_transforms.finite_diff import FiniteDiff
@@ -168,7 +169,13 @@ class ALDInvSegProximalRealImag(ALDOptimizer):
             # on the imaginary plane (same label); the scalar lh_weight / sigma of this level sits in the device schedule
             gseg = self.seg.loglh_grad(st["x"], st["seg_label"], st["seg_mode"])
             ops.axpy_sched(grad, gseg, dev_sched=st["sched_dev"])
-        if st["sc_mode"] is None:            # multi-coil SENSE + L2Penalty
+        if st.get("cg") is not None:         # multi-coil SENSE + L2PenaltyCG: exact proximal, coef = alpha / lamda
+            cg = st["cg"]
+            ops.ald_sense_cg_step(st["x"][:B], st["x"][B:], grad[:B], grad[B:], st["y"], st["sens"], st["mask"], st["work"],
+                                  noise_re=st["noise_re"], noise_im=st["noise_im"], seed=st["seed"],
+                                  sample_offset=st["sample_offset"], dev_sched=st["sched_dev"], ahy=cg["ahy"],
+                                  max_iter=cg["max_iter"], tol=cg["tol"], iters_out=cg["iters"])
+        elif st["sc_mode"] is None:          # multi-coil SENSE + L2Penalty
             ops.ald_sense_step(st["x"][:B], st["x"][B:], grad[:B], grad[B:], st["y"], st["sens"], st["mask"], st["work"],
                                noise_re=st["noise_re"], noise_im=st["noise_im"], seed=st["seed"],
                                sample_offset=st["sample_offset"], dev_sched=st["sched_dev"])
@@ -178,25 +185,35 @@ class ALDInvSegProximalRealImag(ALDOptimizer):
                                     sample_offset=st["sample_offset"], dev_sched=st["sched_dev"], work=st["work"])
 
     def _check_fast_path(self, kwargs):
-        """-> sc_mode: None for SENSE + L2Penalty, the ipdm_singlecoil_prox_f32 mode for the single-coil operators
+        """-> sc_mode: None for SENSE + L2Penalty / L2PenaltyCG, the ipdm_singlecoil_prox_f32 mode for the single-coil operators
         (the reference's acdc_inv_seg_sampling_keep_center_prox_real_imag.py:79-89 / cine_inv_sampling_...:78-88)"""
         if self._seg_active() and not hasattr(self.seg, "loglh_grad"):
             raise NotImplementedError("segmentation-likelihood guidance needs a network with the fused forward + input-gradient "
                                       f"chain (ncsn.models.seg_unet.UNet.loglh_grad); got {type(self.seg).__name__}: there is "
                                       "no autograd on the HIP path")
         if isinstance(self.linear_tfm, SENSE):
-            if isinstance(self.proximal, L2Penalty):
+            if isinstance(self.proximal, (L2Penalty, L2PenaltyCG)):
                 return None
         elif isinstance(self.linear_tfm, RandomUndersamplingFourier):
             if isinstance(self.proximal, L2Penalty):
                 return ops.SC_L2PENALTY
-            if isinstance(self.proximal, SingleCoil):
+            if isinstance(self.proximal, (SingleCoil, L2PenaltyCG)):      # single coil: the exact proximal IS the closed form
                 return ops.SC_CLOSED_FORM
         if isinstance(self.proximal, Constrained):
             # the reference's samplers call proximal(x, y, coeff, 1.) (:315); Constrained.__call__ takes (X, S, lamda)
             raise TypeError("Constrained.__call__() takes 4 positional arguments but 5 were given")
         raise NotImplementedError(f"no fused iteration for {type(self.proximal).__name__} + "
                                   f"{type(self.linear_tfm).__name__}")
+
+    def _cg_state(self, B, n_coils, H, W, dev, ahy):
+        """-> (st["cg"], workspace) of the SENSE iteration tail: None and the one-step tail's scratch, or the CG tail's
+        settings with A^H y (constant over the run), the per-sample iteration counts and its larger scratch"""
+        if not (isinstance(self.proximal, L2PenaltyCG) and isinstance(self.linear_tfm, SENSE)):
+            return None, ops.sense_workspace(B, n_coils, H, W, dev)
+        iters = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.proximal.last_iters = iters
+        return (dict(ahy=ahy.to(torch.complex64).contiguous(), max_iter=self.proximal.max_iter, tol=self.proximal.tol,
+                     iters=iters), ops.sense_cg_workspace(B, n_coils, H, W, dev))
 
     def _seg_active(self):
         return self.seg is not None and bool((self.lh_weights != 0).any())
@@ -221,7 +238,8 @@ class ALDInvSegProximalRealImag(ALDOptimizer):
         lin = self.linear_tfm
 
         x0 = kwargs.get("x_init")
-        x0 = lin.conj_op(meas) if x0 is None else x0.to(dev)                  # zero-filled SENSE recon
+        ahy = lin.conj_op(meas) if x0 is None or isinstance(self.proximal, L2PenaltyCG) else None
+        x0 = ahy if x0 is None else x0.to(dev)                                # zero-filled SENSE recon, = A^H y
         B, H, W = x0.shape[0], x0.shape[-2], x0.shape[-1]
         x = torch.cat([x0.real, x0.imag], dim=0).contiguous().float()        # (2B, 1, H, W)
         steps, noise_scales = step_schedule(sigmas, step_lr)
@@ -230,9 +248,9 @@ class ALDInvSegProximalRealImag(ALDOptimizer):
         lv0 = kwargs.get("start_level", 0)
         lv1 = L if kwargs.get("n_levels") is None else min(L, lv0 + kwargs["n_levels"])
 
+        cg, work = self._cg_state(B, lin.sens_maps.shape[0] if sc_mode is None else 1, H, W, dev, ahy)
         st = dict(x=x, B=B, y=meas, sc_mode=sc_mode, sens=lin.sens_dev(dev) if sc_mode is None else None,
-                  mask=lin.mask_u8(dev),
-                  work=ops.sense_workspace(B, lin.sens_maps.shape[0] if sc_mode is None else 1, H, W, dev),
+                  mask=lin.mask_u8(dev), work=work, cg=cg,
                   labels=torch.zeros(2 * B, dtype=torch.long, device=dev),
                   noise_re=None, noise_im=None, seed=kwargs.get("seed", 0),
                   sample_offset=kwargs.get("sample_offset", 0),

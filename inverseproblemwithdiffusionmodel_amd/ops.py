@@ -270,6 +270,93 @@ def ald_sense_step(x_re, x_im, g_re, g_im, y, sens_f32, mask_u8, work, step=0.0,
     _written(x_re, x_im)
 
 
+def sense_cg_workspace(B, n_coils, H, W, device):
+    """scratch tensor of the conjugate-gradient proximal at this size (coil planes, r, p, A^H y, per-sample state)"""
+    nbytes = _lib.lib.ipdm_sense_cg_workspace_bytes(B, n_coils, H, W)
+    return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=device) if nbytes else None
+
+
+def _check_cg_scalars(max_iter, tol, what):
+    """-> (max_iter, tol); checked before any tensor is looked at"""
+    if isinstance(max_iter, bool) or int(max_iter) != max_iter or max_iter < 1:
+        raise ValueError(f"{what}: max_iter must be an integer >= 1, got {max_iter}")
+    tol = float(tol)
+    if not (0.0 <= tol < float("inf")):
+        raise ValueError(f"{what}: tol must be finite and >= 0, got {tol}")
+    return int(max_iter), tol
+
+
+def _check_cg_args(work, ahy, iters_out, B, n_coils, H, W, device, what):
+    """-> (work, iters_out) checked: the kernels write `work` and `iters_out` through raw pointers"""
+    need = _lib.lib.ipdm_sense_cg_workspace_bytes(B, n_coils, H, W)
+    if work is None:
+        work = sense_cg_workspace(B, n_coils, H, W, device)         # None for a size without a kernel: the call reports it
+    elif (not isinstance(work, torch.Tensor) or not work.is_cuda or work.dtype != torch.float32 or not work.is_contiguous()
+            or work.numel() * 4 < need):
+        raise ValueError(f"{what}: `work` must be a contiguous float32 GPU tensor of >= {need} bytes "
+                         f"(ops.sense_cg_workspace({B}, {n_coils}, {H}, {W}, device))")
+    if ahy is not None:
+        _inplace_operand(ahy, torch.complex64, "ahy")
+        if ahy.numel() != B * H * W:
+            raise ValueError(f"{what}: ahy {tuple(ahy.shape)} does not match the image batch [{B}, {H}, {W}]")
+    if iters_out is None:
+        iters_out = torch.zeros(B, dtype=torch.int32, device=device)
+    else:
+        _inplace_operand(iters_out, torch.int32, "iters_out")
+        if iters_out.numel() < B:
+            raise ValueError(f"{what}: iters_out holds {iters_out.numel()} < {B} entries")
+    return work, iters_out
+
+
+def sense_cgprox(z_re, z_im, y, sens_f32, mask_u8, a, max_iter=10, tol=1e-5, ahy=None, out_re=None, out_im=None, work=None,
+                 iters_out=None):
+    """exact SENSE proximal (I + a A^H A) x = z + a A^H y by conjugate gradients (ipdm.h, ipdm_sense_cgprox_f32)
+    -> (out_re, out_im, iters): iters a device int32 [B], never synchronised here"""
+    max_iter, tol = _check_cg_scalars(max_iter, tol, "sense_cgprox")
+    z_re, z_im = _gpu(z_re, torch.float32, "z_re"), _gpu(z_im, torch.float32, "z_im")
+    y = _gpu(y, torch.complex64, "y")
+    H, W = z_re.shape[-2:]
+    B = z_re.numel() // (H * W) if H * W else 0
+    fn = _sens_entry(sens_f32, "ipdm_sense_cgprox_f32", "ipdm_sense_cgprox_csm_f32", H, W)
+    n = sens_f32.shape[0]
+    if y.numel() != n * B * H * W:
+        raise ValueError("sense_cgprox: measurement does not match [n_coils, B, H, W]")
+    work, iters_out = _check_cg_args(work, ahy, iters_out, B, n, H, W, z_re.device, "sense_cgprox")
+    out_re = torch.empty_like(z_re) if out_re is None else out_re
+    out_im = torch.empty_like(z_im) if out_im is None else out_im
+    call(fn, _ptr(z_re), _ptr(z_im), _ptr(y), _ptr(sens_f32), _ptr(mask_u8), mask_u8.shape[0], float(a), _ptr(ahy),
+         max_iter, tol, _ptr(out_re), _ptr(out_im), _ptr(work), _ptr(iters_out), B, n, H, W, _stream())
+    _written(out_re, out_im, iters_out)
+    return out_re, out_im, iters_out
+
+
+def ald_sense_cg_step(x_re, x_im, g_re, g_im, y, sens_f32, mask_u8, work, step=0.0, noise_scale=0.0, coef=0.0,
+                      noise_re=None, noise_im=None, seed=0, sample_offset=0, step_id=0, dev_sched=None, ahy=None,
+                      max_iter=10, tol=1e-5, iters_out=None):
+    """ald_sense_step with the conjugate-gradient proximal; in place on x_re / x_im.  coef (dev_sched's coef field)
+    carries a = alpha / lamda.  -> iters (device int32 [B])"""
+    max_iter, tol = _check_cg_scalars(max_iter, tol, "ald_sense_cg_step")
+    for t, n in ((x_re, "x_re"), (x_im, "x_im"), (g_re, "g_re"), (g_im, "g_im")):
+        _inplace_operand(t, torch.float32, n)
+    fn = _sens_entry(sens_f32, "ipdm_ald_sense_cg_step_f32", "ipdm_ald_sense_cg_step_csm_f32", *x_re.shape[-2:])
+    _inplace_operand(y, torch.complex64, "y")
+    for t, n in ((noise_re, "noise_re"), (noise_im, "noise_im")):
+        if t is not None:
+            _inplace_operand(t, torch.float32, n)
+    H, W = x_re.shape[-2:]
+    B = x_re.numel() // (H * W) if H * W else 0
+    nc = sens_f32.shape[0]
+    if g_re.numel() != x_re.numel() or g_im.numel() != x_im.numel() or y.numel() != nc * B * H * W:
+        raise ValueError("ald_sense_cg_step: operand sizes do not match the state")
+    work, iters_out = _check_cg_args(work, ahy, iters_out, B, nc, H, W, x_re.device, "ald_sense_cg_step")
+    call(fn, _ptr(x_re), _ptr(x_im), _ptr(g_re), _ptr(g_im), _ptr(noise_re), _ptr(noise_im),
+         float(step), float(noise_scale), int(seed), int(sample_offset), int(step_id), _ptr(dev_sched),
+         _ptr(y), _ptr(sens_f32), _ptr(mask_u8), mask_u8.shape[0], float(coef), _ptr(work), _ptr(ahy), max_iter, tol,
+         _ptr(iters_out), B, nc, H, W, _stream())
+    _written(x_re, x_im, iters_out)
+    return iters_out
+
+
 SC_L2PENALTY, SC_CLOSED_FORM, SC_PROJECTION = 0, 1, 2
 
 

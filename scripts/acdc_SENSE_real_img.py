@@ -15,6 +15,8 @@ import torch.distributed as dist
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+PROXIMAL_NAMES = ["L2Penalty", "Constrained", "SingleCoil", "L2PenaltyCG"]     # get_proximal's names
+
 if __name__ == '__main__':
     parser = argparse.ArgumentParser()
     parser.add_argument("--R", type=int, default=40)
@@ -26,7 +28,10 @@ if __name__ == '__main__':
     parser.add_argument("--step_lr", type=float, default=0.0000009)
     parser.add_argument("--num_steps_each", type=int, default=3)
     parser.add_argument("--lr_scaled", type=float, default=1.)
-    parser.add_argument("--proximal_type", default="L2Penalty")
+    parser.add_argument("--proximal_type", default="L2Penalty", choices=PROXIMAL_NAMES,
+                        help="data-consistency operator; L2PenaltyCG: the exact multi-coil proximal by conjugate gradients")
+    parser.add_argument("--cg_iters", type=int, default=10, help="L2PenaltyCG: CG iterations at most")
+    parser.add_argument("--cg_tol", type=float, default=1e-5, help="L2PenaltyCG: stop at |r| <= cg_tol |b|")
     parser.add_argument("--num_samples", type=int, default=1)
     parser.add_argument("--sens_type", default="exp")
     parser.add_argument("--num_sens", type=int, default=4)
@@ -74,7 +79,9 @@ if __name__ == '__main__':
         sens_maps = complex_coil_maps(args_dict["num_sens"], H, H, args_dict["seed"])
     prob = engine.build_problem(device, n_local, R=args_dict["R"], H=H, W=H, num_sens=args_dict["num_sens"],
                                 seed=args_dict["seed"], scorenet=scorenet, cfg=cfg, lr_scaled=args_dict["lr_scaled"],
-                                sens_maps=sens_maps)
+                                sens_maps=sens_maps, proximal=args_dict["proximal_type"],
+                                proximal_kwargs=(dict(max_iter=args_dict["cg_iters"], tol=args_dict["cg_tol"])
+                                                 if args_dict["proximal_type"] == "L2PenaltyCG" else None))
     label = None
     if args_dict["seg_start_time"] < 1.:
         from inverseproblemwithdiffusionmodel_amd.helpers.load_model import reload_model

@@ -7,6 +7,7 @@ keyed by the global sample id, the per-step random shift drawn from identically 
 artefacts and the posterior mean / std: the result does not depend on the number of ranks."""
 import argparse
 import os
+import pickle
 import sys
 import time
 
@@ -14,6 +15,8 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+PROXIMAL_NAMES = ["L2Penalty", "Constrained", "SingleCoil", "L2PenaltyCG"]     # get_proximal's names
 
 if __name__ == '__main__':
     parser = argparse.ArgumentParser()
@@ -23,7 +26,10 @@ if __name__ == '__main__':
     parser.add_argument("--step_lr", type=float, default=0.0001)
     parser.add_argument("--num_steps_each", type=int, default=3)
     parser.add_argument("--lr_scaled", type=float, default=1.)
-    parser.add_argument("--proximal_type", default="L2Penalty")
+    parser.add_argument("--proximal_type", default="L2Penalty", choices=PROXIMAL_NAMES,
+                        help="data-consistency operator; L2PenaltyCG: the exact multi-coil proximal by conjugate gradients")
+    parser.add_argument("--cg_iters", type=int, default=10, help="L2PenaltyCG: CG iterations at most")
+    parser.add_argument("--cg_tol", type=float, default=1e-5, help="L2PenaltyCG: stop at |r| <= cg_tol |b|")
     parser.add_argument("--num_samples", type=int, default=1)
     parser.add_argument("--sens_type", default="exp")
     parser.add_argument("--temporal_type", default="Diffusion3D", choices=["Diffusion3D", "Diffusion1D"],
@@ -68,7 +74,8 @@ if __name__ == '__main__':
     frames = base * (1.0 + 0.1 * beat)                                     # (T, 1, H, W): a slowly pulsating phantom
     meas = op(frames).reshape(a.num_sens, 1, a.T, 1, H, W).repeat(1, n_local, 1, 1, 1, 1)
     params = dict(n_steps_each=a.num_steps_each, step_lr=a.step_lr, denoise=False, final_only=True)
-    sampler = ALD2DTime(get_proximal(a.proximal_type)(op), scorenet_T, sigmas_T, (n_local, a.T, 1, H, W), scorenet,
+    prox_kw = dict(max_iter=a.cg_iters, tol=a.cg_tol) if a.proximal_type == "L2PenaltyCG" else {}
+    sampler = ALD2DTime(get_proximal(a.proximal_type)(op, **prox_kw), scorenet_T, sigmas_T, (n_local, a.T, 1, H, W), scorenet,
                         sigmas, params, scorenet.config, meas, op, device=device)
     t0 = time.time()
     out = sampler(save_dir=a.save_dir, lr_scaled=a.lr_scaled, mode_T=a.mode_T, lamda_T=a.lamda_T,
@@ -90,6 +97,8 @@ if __name__ == '__main__':
             torch.save(op.sens_maps, os.path.join(a.save_dir, "sens_maps.pt"))
         if post is not None:
             torch.save({k: v.cpu() for k, v in post.items()}, os.path.join(a.save_dir, "posterior.pt"))
+        with open(os.path.join(a.save_dir, "args_dict.pkl"), "wb") as wf:
+            pickle.dump(vars(a), wf)
     if world > 1:
         sharding.barrier(last=True)
         torch.distributed.destroy_process_group()
