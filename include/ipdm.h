@@ -104,6 +104,11 @@ int ipdm_fused_bias_act_f64(const double* x, const double* b, const double* ref,
  * :140-170 SENSE.__call__/conj_op/SSOS; ncsn/models/proximal_op.py:19-51 L2Penalty, :72-94 SingleCoil).
  * mask is uint8 [mask_t][W] (1 = sampled k-space column); mask_t == 1 broadcasts over the batch,
  * otherwise image b uses row b % mask_t (the reference's (T,1,1,W) broadcast against a (T,1,H,W) stack).
+ * A NEGATIVE mask_t = -T announces a 2-D mask, uint8 [T][H][W] (1 = sampled k-space sample: variable-density
+ * (ky, kz) patterns, partial Fourier, elliptical shutters, ...; the reference's (T,1,H,W) mask); T == 1 broadcasts
+ * over the batch, otherwise image b uses plane b % T.  Every entry point below that takes (mask, mask_t) accepts
+ * both layouts (ipdm_mask_layouts() & IPDM_MASK_2D; older builds return IPDM_EINVAL for mask_t < 0); mask_t == 0 is
+ * invalid.  A mask only selects samples: no arithmetic, normalisation included, depends on the layout.
  * sens maps are float32 [n_coils][H][W] (real, as the reference's "exp" maps).
  * ---------------------------------------------------------------------------------------------- */
 
@@ -114,6 +119,11 @@ int ipdm_fft2c_c64(const float* in, float* out, int batch, int H, int W, int inv
                    void* stream);
 /* bytes of workspace ipdm_fft2c_c64 needs for (batch,H,W); 0 when the LDS path applies */
 int64_t ipdm_fft2c_workspace_bytes(int batch, int H, int W);
+
+/* mask layouts the (mask, mask_t) entry points accept: IPDM_MASK_LINES | IPDM_MASK_2D */
+#define IPDM_MASK_LINES 1 /* mask_t > 0: uint8 [mask_t][W] */
+#define IPDM_MASK_2D 2    /* mask_t < 0: uint8 [-mask_t][H][W] */
+int ipdm_mask_layouts(void);
 
 /* y[c][b] = mask * fft2c(S_c * x[b])        x [B][H][W] c64 -> y [n_coils][B][H][W] c64 */
 /* (sens == NULL with n_coils == 1: the single-coil operator RandomUndersamplingFourier.__call__, y = M F x,

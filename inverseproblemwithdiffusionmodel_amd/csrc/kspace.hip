@@ -98,7 +98,7 @@ __global__ __launch_bounds__(FFT_THREADS) void sense_forward_kernel(const float2
   for (int e = threadIdx.x; e < HW; e += FFT_THREADS) {
     int r = e / W, c = e - r * W;
     float2 v = L.buf[e];
-    float s = mask_at(mask, mask_t, b, W, c) ? sign_rc(r, c) * scale : 0.f;
+    float s = mask_at(mask, mask_t, b, H, W, r, c) ? sign_rc(r, c) * scale : 0.f;
     dst[e] = make_float2(v.x * s, v.y * s);
   }
 }
@@ -121,7 +121,7 @@ __global__ __launch_bounds__(FFT_THREADS) void sense_adjoint_kernel(const float2
     for (int e = threadIdx.x; e < HW; e += FFT_THREADS) {
       int r = e / W, c = e - r * W;
       float sg = sign_rc(r, c);
-      if (apply_mask && !mask_at(mask, mask_t, b, W, c)) sg = 0.f;
+      if (apply_mask && !mask_at(mask, mask_t, b, H, W, r, c)) sg = 0.f;
       float2 v = src[e];
       L.buf[e] = make_float2(v.x * sg, v.y * sg);
     }
@@ -225,7 +225,7 @@ __global__ __launch_bounds__(FFT_THREADS) void ald_sense_step_kernel(
         int r = e / W, c = e - r * W;
         float2 v = L.buf[e];
         float2 res = make_float2(0.f, 0.f);
-        if (mask_at(mask, mask_t, b, W, c)) {
+        if (mask_at(mask, mask_t, b, H, W, r, c)) {
           float sg = sign_rc(r, c);
           float2 yy = yc[e];
           res = make_float2(v.x * scale - sg * yy.x, v.y * scale - sg * yy.y);
@@ -295,7 +295,7 @@ __global__ __launch_bounds__(FFT_THREADS) void ald_sense_coil_kernel(
     const int r = e / W, c = e - r * W;
     const float2 v = L.buf[e];
     float2 res = make_float2(0.f, 0.f);
-    if (mask_at(mask, mask_t, b, W, c)) {
+    if (mask_at(mask, mask_t, b, H, W, r, c)) {
       const float sg = sign_rc(r, c);
       const float2 yy = yc[e];
       res = make_float2(v.x * scale - sg * yy.x, v.y * scale - sg * yy.y);
@@ -387,7 +387,7 @@ __global__ __launch_bounds__(FFT_THREADS) void ald_singlecoil_step_kernel(
     float2 v = L.buf[e];
     v.x *= scale;
     v.y *= scale;
-    const bool m = mask_at(mask, mask_t, b, W, c);
+    const bool m = mask_at(mask, mask_t, b, H, W, r, c);
     float2 o;
     if (mode == 0) {
       o = make_float2(0.f, 0.f);
@@ -498,7 +498,7 @@ extern "C" int ipdm_fft2c_c64(const float* in, float* out, int batch, int H, int
 template <typename SensT>
 static int sense_forward_impl(const float* x, const SensT* sens, const uint8_t* mask, int mask_t, float* y,
                                       int B, int n_coils, int H, int W, void* stream) {
-  IPDM_REQUIRE(B >= 0 && n_coils > 0 && H > 0 && W > 0 && mask_t > 0);
+  IPDM_REQUIRE(B >= 0 && n_coils > 0 && H > 0 && W > 0 && mask_t_ok(mask_t));
   if (B == 0) return IPDM_OK;
   IPDM_REQUIRE(x && mask && y && (sens || n_coils == 1));
   if (ipdm_kspace_large::large_ok(H, W))
@@ -520,10 +520,10 @@ static int sense_adjoint_impl(const float* s, const SensT* sens, const uint8_t* 
   IPDM_REQUIRE(B >= 0 && n_coils > 0 && H > 0 && W > 0);
   if (B == 0) return IPDM_OK;
   IPDM_REQUIRE(s && sens && x);
-  if (apply_mask) IPDM_REQUIRE(mask && mask_t > 0);
+  if (apply_mask) IPDM_REQUIRE(mask && mask_t_ok(mask_t));
   if (ipdm_kspace_large::large_ok(H, W)) {
     IPDM_REQUIRE(workspace);
-    return ipdm_kspace_large::sense_adjoint(reinterpret_cast<const float2*>(s), sens, mask, mask_t > 0 ? mask_t : 1,
+    return ipdm_kspace_large::sense_adjoint(reinterpret_cast<const float2*>(s), sens, mask, apply_mask ? mask_t : 1,
                                             apply_mask, reinterpret_cast<float2*>(x), nullptr,
                                             reinterpret_cast<float2*>(workspace), B, n_coils, H, W, ipdm_stream(stream));
   }
@@ -532,7 +532,7 @@ static int sense_adjoint_impl(const float* s, const SensT* sens, const uint8_t* 
   int rc = set_lds_limit(sense_adjoint_kernel<false, SensT>, lds);
   if (rc) return rc;
   hipLaunchKernelGGL((sense_adjoint_kernel<false, SensT>), dim3(B), dim3(FFT_THREADS), lds, ipdm_stream(stream),
-                     reinterpret_cast<const float2*>(s), sens, mask, mask_t > 0 ? mask_t : 1, apply_mask, x, B, n_coils,
+                     reinterpret_cast<const float2*>(s), sens, mask, apply_mask ? mask_t : 1, apply_mask, x, B, n_coils,
                      H, W);
   return ipdm_launch_status();
 }
@@ -584,7 +584,7 @@ template <typename SensT>
 static int sense_l2prox_impl(const float* z_re, const float* z_im, const float* y, const SensT* sens,
                                      const uint8_t* mask, int mask_t, float coef, float* out_re, float* out_im,
                                      float* work, int B, int n_coils, int H, int W, void* stream) {
-  IPDM_REQUIRE(B >= 0 && n_coils > 0 && H > 0 && W > 0 && mask_t > 0);
+  IPDM_REQUIRE(B >= 0 && n_coils > 0 && H > 0 && W > 0 && mask_t_ok(mask_t));
   if (B == 0) return IPDM_OK;
   IPDM_REQUIRE(z_re && z_im && y && sens && mask && out_re && out_im && work);
   const bool large = ipdm_kspace_large::large_ok(H, W);
@@ -616,7 +616,7 @@ static int ald_sense_step_impl(float* x_re, float* x_im, const float* g_re, cons
                                        uint64_t seed, int64_t sample_offset, int64_t step_id,
                                        const ipdm_sched_t* dev_sched, const float* y, const SensT* sens, const uint8_t* mask, int mask_t, float coef, float* work,
                                        int B, int n_coils, int H, int W, void* stream) {
-  IPDM_REQUIRE(B >= 0 && n_coils > 0 && H > 0 && W > 0 && mask_t > 0);
+  IPDM_REQUIRE(B >= 0 && n_coils > 0 && H > 0 && W > 0 && mask_t_ok(mask_t));
   if (B == 0) return IPDM_OK;
   IPDM_REQUIRE(x_re && x_im && g_re && g_im && y && sens && mask && work);
   IPDM_REQUIRE((noise_re == nullptr) == (noise_im == nullptr));
@@ -675,7 +675,7 @@ extern "C" int ipdm_ald_sense_step_csm_f32(float* x_re, float* x_im, const float
 extern "C" int ipdm_singlecoil_prox_f32(const float* z_re, const float* z_im, const float* y, const uint8_t* mask,
                                         int mask_t, float coef, int mode, float* out_re, float* out_im, float* workspace,
                                         int B, int H, int W, void* stream) {
-  IPDM_REQUIRE(B >= 0 && H > 0 && W > 0 && mask_t > 0 && mode >= 0 && mode <= 2);
+  IPDM_REQUIRE(B >= 0 && H > 0 && W > 0 && mask_t_ok(mask_t) && mode >= 0 && mode <= 2);
   if (B == 0) return IPDM_OK;
   IPDM_REQUIRE(z_re && z_im && y && mask && out_re && out_im);
   const bool large = ipdm_kspace_large::large_ok(H, W);
@@ -704,7 +704,7 @@ extern "C" int ipdm_ald_singlecoil_step_f32(float* x_re, float* x_im, const floa
                                             uint64_t seed, int64_t sample_offset, int64_t step_id,
                                             const ipdm_sched_t* dev_sched, const float* y, const uint8_t* mask, int mask_t,
                                             float coef, int mode, float* workspace, int B, int H, int W, void* stream) {
-  IPDM_REQUIRE(B >= 0 && H > 0 && W > 0 && mask_t > 0 && mode >= 0 && mode <= 2);
+  IPDM_REQUIRE(B >= 0 && H > 0 && W > 0 && mask_t_ok(mask_t) && mode >= 0 && mode <= 2);
   if (B == 0) return IPDM_OK;
   IPDM_REQUIRE(x_re && x_im && g_re && g_im && y && mask);
   IPDM_REQUIRE((noise_re == nullptr) == (noise_im == nullptr));

@@ -114,7 +114,7 @@ __global__ __launch_bounds__(FFT_THREADS) void cg_normal_coil_kernel(
     const int r = e / W, c = e - r * W;
     const float2 v = L.buf[e];
     float2 res = make_float2(0.f, 0.f);
-    if (mask_at(mask, mask_t, b, W, c)) {
+    if (mask_at(mask, mask_t, b, H, W, r, c)) {
       res = make_float2(v.x * scale, v.y * scale);
       if constexpr (MODE != 0) {
         const float sg = sign_rc(r, c);
@@ -369,7 +369,7 @@ template <typename SensT>
 static int cgprox_impl(const float* z_re, const float* z_im, const float* y, const SensT* sens, const uint8_t* mask, int mask_t,
                        float a, const float* ahy, int max_iter, float tol, float* out_re, float* out_im, float* work,
                        int32_t* iters_out, int B, int n_coils, int H, int W, void* stream) {
-  IPDM_REQUIRE(B >= 0 && n_coils > 0 && H > 0 && W > 0 && mask_t > 0 && max_iter >= 1 && tol >= 0.f && tol < INFINITY);
+  IPDM_REQUIRE(B >= 0 && n_coils > 0 && H > 0 && W > 0 && mask_t_ok(mask_t) && max_iter >= 1 && tol >= 0.f && tol < INFINITY);
   if (B == 0) return IPDM_OK;
   if (!ipdm_kspace_large::large_ok(H, W) && !lds_fft_ok(H, W)) return IPDM_EUNSUPPORTED;
   IPDM_REQUIRE(z_re && z_im && y && sens && mask && out_re && out_im && work);
@@ -388,7 +388,7 @@ static int cg_step_impl(float* x_re, float* x_im, const float* g_re, const float
                         int64_t step_id, const ipdm_sched_t* dev_sched, const float* y, const SensT* sens, const uint8_t* mask,
                         int mask_t, float coef, float* work, const float* ahy, int max_iter, float tol, int32_t* iters_out, int B,
                         int n_coils, int H, int W, void* stream) {
-  IPDM_REQUIRE(B >= 0 && n_coils > 0 && H > 0 && W > 0 && mask_t > 0 && max_iter >= 1 && tol >= 0.f && tol < INFINITY);
+  IPDM_REQUIRE(B >= 0 && n_coils > 0 && H > 0 && W > 0 && mask_t_ok(mask_t) && max_iter >= 1 && tol >= 0.f && tol < INFINITY);
   if (B == 0) return IPDM_OK;
   if (!ipdm_kspace_large::large_ok(H, W) && !lds_fft_ok(H, W)) return IPDM_EUNSUPPORTED;
   IPDM_REQUIRE(x_re && x_im && g_re && g_im && y && sens && mask && work);

@@ -139,8 +139,16 @@ static inline bool lds_fft_ok(int H, int W) {
 static inline size_t lds_bytes(int H, int W) { return ((size_t)H * W + (size_t)(H > W ? H : W)) * sizeof(float2); }
 
 
-__device__ __forceinline__ bool mask_at(const uint8_t* mask, int mask_t, int b, int W, int c) {
-  return mask[(size_t)(mask_t == 1 ? 0 : b % mask_t) * W + c] != 0;
+// Sampling mask at k-space point (r, c) of image b, the only place the two layouts are told apart:
+//   mask_t > 0   line mask  uint8 [mask_t][W]     (sampled columns; row r is not looked at)
+//   mask_t < 0   2-D mask   uint8 [T][H][W], T = -mask_t
+// One plane broadcasts over the batch, otherwise image b uses plane b % T.  A mask only selects: no arithmetic depends
+// on the layout.
+static inline bool mask_t_ok(int mask_t) { return mask_t != 0 && mask_t > -0x7fffffff; }
+__device__ __forceinline__ bool mask_at(const uint8_t* mask, int mask_t, int b, int H, int W, int r, int c) {
+  if (mask_t > 0) return mask[(size_t)(mask_t == 1 ? 0 : b % mask_t) * W + c] != 0;
+  const int T = -mask_t;
+  return mask[((size_t)(T == 1 ? 0 : b % T) * H + r) * W + c] != 0;
 }
 
 // whole-image LDS kernels (kspace.hip, kspace_cg.hip): the image followed by the twiddle table in dynamic LDS

@@ -125,7 +125,7 @@ struct ColsFwdMask {
   float scale;
   __device__ __forceinline__ float2 load(int b, int coil, int r, int c) const { return y[g.at(coil, b, r, c)]; }
   __device__ __forceinline__ void store(int b, int coil, int r, int c, float2 v) const {
-    const float s = (!mask || mask_at(mask, mask_t, b, g.W, c)) ? sign_rc(r, c) * scale : 0.f;
+    const float s = (!mask || mask_at(mask, mask_t, b, g.H, g.W, r, c)) ? sign_rc(r, c) * scale : 0.f;
     y[g.at(coil, b, r, c)] = make_float2(v.x * s, v.y * s);
   }
   __device__ __forceinline__ bool skip(int, int, int) const { return false; }
@@ -141,7 +141,7 @@ struct ColsInvFromS {
   int mask_t, apply_mask;
   __device__ __forceinline__ float2 load(int b, int coil, int r, int c) const {
     float sg = sign_rc(r, c);
-    if (apply_mask && !mask_at(mask, mask_t, b, g.W, c)) sg = 0.f;
+    if (apply_mask && !mask_at(mask, mask_t, b, g.H, g.W, r, c)) sg = 0.f;
     const float2 v = s[g.at(coil, b, r, c)];
     return make_float2(v.x * sg, v.y * sg);
   }
@@ -164,16 +164,29 @@ struct ColsProx {
   const ipdm_sched_t* sched;       // device schedule: overrides coef_host (modes 1, 2 use it in k-space)
   __device__ __forceinline__ float2 load(int b, int coil, int r, int c) const { return tmp[g.at(coil, b, r, c)]; }
   __device__ __forceinline__ void store(int b, int coil, int r, int c, float2 v) const { tmp[g.at(coil, b, r, c)] = v; }
+  // Called by every thread of the workgroup, before any divergence; the answer is the same in all of them.
+  //   line mask: each thread scans the strip's cs column bytes (the same bytes, hence the same answer);
+  //   2-D mask:  the strip is skippable only if none of its H x cs points is sampled -- the threads share the scan and
+  //              __syncthreads_or makes the verdict uniform by construction (mask_t and mode are kernel arguments, so
+  //              all threads take this branch together and all reach the barrier).
   __device__ __forceinline__ bool skip(int b, int c0, int cs) const {
     if (mode > 0) return false;
-    for (int c = c0; c < c0 + cs; ++c)
-      if (mask_at(mask, mask_t, b, g.W, c)) return false;
-    return true;
+    if (mask_t > 0) {
+      for (int c = c0; c < c0 + cs; ++c)
+        if (mask_at(mask, mask_t, b, g.H, g.W, 0, c)) return false;
+      return true;
+    }
+    int any = 0;
+    for (int e = threadIdx.x; e < g.H * cs; e += FFT_THREADS) {
+      const int r = e / cs, lc = e - r * cs;
+      any |= mask_at(mask, mask_t, b, g.H, g.W, r, c0 + lc);
+    }
+    return !__syncthreads_or(any);
   }
   __device__ __forceinline__ float2 mid(int b, int coil, int r, int c, float2 v) const {
     v.x *= scale;
     v.y *= scale;
-    const bool m = mask_at(mask, mask_t, b, g.W, c);
+    const bool m = mask_at(mask, mask_t, b, g.H, g.W, r, c);
     const float2 yy = y ? y[g.at(coil, b, r, c)] : make_float2(0.f, 0.f);
     const float sg = sign_rc(r, c);
     if (mode <= 0) return m ? make_float2(v.x - sg * yy.x, v.y - sg * yy.y) : make_float2(0.f, 0.f);

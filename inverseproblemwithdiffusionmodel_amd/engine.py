@@ -56,18 +56,20 @@ def build_scorenet(cfg, seed=0):
 
 
 def build_problem(device, n_samples, R=40, H=128, W=128, num_sens=4, seed=0, scorenet=None, cfg=None, lr_scaled=1.0,
-                  sens_maps=None, proximal="L2Penalty", proximal_kwargs=None):
+                  sens_maps=None, proximal="L2Penalty", proximal_kwargs=None, mask=None):
     """-> Namespace(sampler, scorenet, sigmas, op, image, measurement, call_kwargs); sens_maps: measured coil maps
     (num_sens, H, W), real or complex, instead of the synthetic "exp" maps (RSS-normalised where non-zero); proximal: a
-    get_proximal name ("L2PenaltyCG": the exact proximal, proximal_kwargs = dict(max_iter=, tol=))"""
+    get_proximal name ("L2PenaltyCG": the exact proximal, proximal_kwargs = dict(max_iter=, tol=)); mask: the sampling mask
+    of an acquisition, a line or 2-D mask (SENSE mask_mode="custom"), instead of the generated line mask at R"""
     prox_cls = get_proximal(proximal)                        # an unknown name fails here, before any GPU work
     cfg = acdc_config(device, H) if cfg is None else cfg
     scorenet = build_scorenet(cfg, seed) if scorenet is None else scorenet
     sigmas = get_sigmas(cfg, "recons")
+    mk = {} if mask is None else dict(mask_mode="custom", mask=mask)
     if sens_maps is None:
-        op = SENSE("exp", num_sens, R, 0.04, (1, H, W), seed=seed, mask_T=1)
+        op = SENSE("exp", num_sens, R, 0.04, (1, H, W), seed=seed, mask_T=1, **mk)
     else:
-        op = SENSE("custom", num_sens, R, 0.04, (1, H, W), seed=seed, mask_T=1, sens_maps=sens_maps)
+        op = SENSE("custom", num_sens, R, 0.04, (1, H, W), seed=seed, mask_T=1, sens_maps=sens_maps, **mk)
     img = phantom_image(H, W, seed=seed).to(device)
     meas = op(img).repeat(1, n_samples, 1, 1, 1).contiguous()
     params = dict(n_steps_each=cfg.sampling.n_steps_each, step_lr=cfg.sampling.step_lr, denoise=True,

@@ -225,6 +225,42 @@ def load_sens_maps(path):
     return maps.to(torch.complex128 if maps.is_complex() else torch.float64)
 
 
+def load_mask(path):
+    """k-space sampling mask from a ``.npy`` or ``.pt`` file -> host tensor, dtype and shape as stored: a line mask
+    ((W,), (1, 1, W), (T, 1, 1, W)) or a 2-D mask ((H, W), (1, 1, H, W), (T, 1, H, W)), bool, integer or real floating
+    (non-zero = sampled), ready for ``SENSE(..., mask_mode="custom", mask=...)`` or ``op.random_under_fourier.mask = ...``"""
+    import numpy as np
+    import torch
+    ext = os.path.splitext(str(path))[1].lower()
+    if ext == ".npy":
+        mask = torch.from_numpy(np.load(path, allow_pickle=False))
+    elif ext == ".pt":
+        mask = torch.load(path, map_location="cpu")
+    else:
+        raise ValueError(f"load_mask: {path!r}: a .npy or .pt file")
+    if not isinstance(mask, torch.Tensor) or not 1 <= mask.dim() <= 4:
+        raise ValueError(f"load_mask: {path!r} must hold one array of 1 to 4 dims")
+    if mask.is_complex():
+        raise TypeError(f"load_mask: {path!r} holds {mask.dtype}; a bool, integer or real floating mask expected")
+    return mask
+
+
+def driver_mask(path, mask_2d, H, W, R, seed):
+    """-> the mask a driver assigns to ``op.random_under_fourier.mask`` for --mask PATH or --mask_2d, None for the default
+    line mask; a (T, H, W) stack from a file (per-frame 2-D masks) becomes (T, 1, H, W)"""
+    if path and mask_2d:
+        raise ValueError("--mask and --mask_2d exclude each other")
+    if path:
+        mask = load_mask(path)
+        if mask.dim() == 3 and tuple(mask.shape[-2:]) == (H, W) and mask.shape[0] != 1:
+            mask = mask[:, None]
+        return mask
+    if mask_2d:
+        from ..synthetic import vd_mask_2d
+        return vd_mask_2d(H, W, R, seed=seed if seed is not None else 0)
+    return None
+
+
 def add_sens_map_args(parser):
     """the drivers' coil-map flags: --sens_maps PATH (measured maps from a file) and --sens_phase (synthetic complex maps)"""
     parser.add_argument("--sens_maps", default=None,

@@ -17,6 +17,10 @@ Differences the reference forces on a drop-in, all explicit:
 * ``sens_type="custom"`` takes ``sens_maps=`` (tensor or ndarray, real or complex, (num_sens, H, W)); ``normalize=True``
   divides by the root-sum-of-squares where it is non-zero (measured maps are masked to the body: zero-support pixels stay
   zero), ``normalize=False`` takes the maps as given.  ``"exp"`` is the reference's synthetic real map, unchanged.
+* ``mask_mode="custom"`` takes ``mask=``: the sampling pattern of an actual acquisition, a line mask ((W,), (1, 1, W),
+  (T, 1, 1, W)) or a 2-D mask ((H, W), (1, 1, H, W), (T, 1, H, W)) -- whatever the reference's ``mask * i2k_complex(X)``
+  broadcasts against a (B, 1, H, W) stack.  ``mask`` is a property like ``SENSE.sens_maps``: the reference's idiom
+  ``op.random_under_fourier.mask = m`` validates the shape and drops the cached device copy, before or after first use.
 """
 import warnings
 
@@ -53,10 +57,16 @@ class UndersamplingFourier(LinearTransform):
 
 
 class RandomUndersamplingFourier(LinearTransform):
-    def __init__(self, R, center_lines_frac, in_shape, seed=None, mask_T=1, mask_params=None, mask_mode="variable"):
-        """in_shape: (C, H, W); mask_mode "variable" (generate_mask, the live reference) or "uniform" (the legacy formula)"""
-        if mask_mode not in ("variable", "uniform"):
-            raise ValueError(f"mask_mode {mask_mode!r}: 'variable' or 'uniform'")
+    def __init__(self, R, center_lines_frac, in_shape, seed=None, mask_T=1, mask_params=None, mask_mode="variable",
+                 mask=None):
+        """in_shape: (C, H, W); mask_mode "variable" (generate_mask, the live reference), "uniform" (the legacy formula) or
+        "custom" (mask=: a line or 2-D sampling mask, see the module docstring)"""
+        if mask_mode not in ("variable", "uniform", "custom"):
+            raise ValueError(f"mask_mode {mask_mode!r}: 'variable', 'uniform' or 'custom'")
+        if mask_mode == "custom" and mask is None:
+            raise ValueError("mask_mode='custom' needs mask= (a line mask (..., W) or a 2-D mask (..., H, W))")
+        if mask_mode != "custom" and mask is not None:
+            raise ValueError("mask= goes with mask_mode='custom'")
         self.R = R
         self.center_lines_frac = center_lines_frac
         self.in_shape = in_shape
@@ -64,8 +74,21 @@ class RandomUndersamplingFourier(LinearTransform):
         self.mask_T = mask_T
         self.mask_params = mask_params
         self.mask_mode = mask_mode
-        self.mask = self._generate_mask()
-        self._dev = {}
+        self.mask = mask if mask_mode == "custom" else self._generate_mask()
+
+    @property
+    def mask(self):
+        return self._mask
+
+    @mask.setter
+    def mask(self, mask):
+        """tensor / ndarray of bool, integer or real floating dtype (non-zero = sampled), kept as given on the host"""
+        if not isinstance(mask, (torch.Tensor, np.ndarray)):
+            raise TypeError(f"mask: a torch tensor or numpy array, got {type(mask).__name__}")
+        t = torch.as_tensor(mask).detach().cpu()
+        ops._mask_u8(t, self.in_shape[-2], self.in_shape[-1], "cpu")          # shape and dtype checks only
+        self._mask = t
+        self._dev = {}                                                        # the device copy belongs to the old mask
 
     def _generate_uniform_mask(self):
         """reference :50-61 (commented out there): float (1, 1, W), torch's default generator seeded with `seed`"""
@@ -99,7 +122,7 @@ class RandomUndersamplingFourier(LinearTransform):
     def mask_u8(self, device):
         key = str(device)
         if key not in self._dev:
-            self._dev[key] = ops._mask_u8(self.mask, self.in_shape[-1], device)
+            self._dev[key] = ops._mask_u8(self._mask, self.in_shape[-2], self.in_shape[-1], device)
         return self._dev[key]
 
     def __call__(self, X: torch.Tensor) -> torch.Tensor:
@@ -124,10 +147,10 @@ class RandomUndersamplingFourier(LinearTransform):
 
 class SENSE(LinearTransform):
     def __init__(self, sens_type, num_sens, R, center_lines_frac, in_shape, seed, mask_T=1, mask_params=None,
-                 mask_mode="variable", sens_maps=None, normalize=True):
+                 mask_mode="variable", sens_maps=None, normalize=True, mask=None):
         assert sens_type in ["exp", "custom"]
         self.random_under_fourier = RandomUndersamplingFourier(R, center_lines_frac, in_shape, seed, mask_T,
-                                                               mask_params, mask_mode)
+                                                               mask_params, mask_mode, mask)
         self.num_sens = num_sens
         self._dev = {}
         if sens_type == "custom":

@@ -143,13 +143,48 @@ def fft2c(x, inverse=False):
     return out
 
 
-def _mask_u8(mask, W, device):
-    """bool/any mask broadcastable over (..., W) -> uint8 [mask_t, W]."""
-    m = mask.to(device=device)
-    if m.shape[-1] != W:
-        raise ValueError(f"mask last dim {m.shape[-1]} != W {W}")
-    m = m.reshape(-1, W)
+def _mask_u8(mask, H, W, device):
+    """host mask -> the kernels' uint8 table, by the reference's right-aligned broadcast of the mask against a
+    (B, 1, H, W) stack (`mask * i2k_complex(X)`): last dim W, dim -2 either 1 (a line mask: sampled k-space columns) or H (a
+    2-D mask), channel dim 1, dim -4 the number of planes T (image b uses plane b % T).
+      line mask  (W,), (1, W), (1, 1, W), (T, 1, 1, W)   -> uint8 [T, W]
+      2-D mask   (H, W), (1, 1, H, W), (T, 1, H, W)      -> uint8 [T, H, W]
+    A shape that would not broadcast there raises ValueError; nothing is reshaped to fit."""
+    m = torch.as_tensor(mask)
+    if m.is_complex():
+        raise TypeError(f"mask: bool, integer or real floating dtype, got {m.dtype}")
+    shape = tuple(m.shape)
+    if not 1 <= len(shape) <= 4:
+        raise ValueError(f"mask {shape}: 1 to 4 dims, broadcastable against (B, 1, {H}, {W})")
+    T, C, h, w = (1,) * (4 - len(shape)) + shape
+    if w != W:
+        raise ValueError(f"mask {shape}: last dim {w} != W {W}")
+    if h not in (1, H):
+        raise ValueError(f"mask {shape}: dim -2 is {h}; 1 (a line mask) or H = {H} (a 2-D mask)")
+    if C != 1:
+        raise ValueError(f"mask {shape}: channel dim {C} != 1")
+    if T < 1:
+        raise ValueError(f"mask {shape}: no planes")
+    m = m.to(device=device).reshape((T, W) if h == 1 and H != 1 else (T, H, W))
     return (m != 0).to(torch.uint8).contiguous()
+
+
+def _mask_t(mask_u8, H, W, what):
+    """-> the C ABI's mask_t for a device mask: uint8 [mask_t, W] (line mask) gives mask_t, uint8 [T, H, W] (2-D mask)
+    gives -T.  The kernels index the table by (b % T, r, c) through a raw pointer: dtype and shape are checked, never
+    converted."""
+    if not isinstance(mask_u8, torch.Tensor) or not mask_u8.is_cuda:
+        raise RuntimeError(f"ipdm {what}: mask must be a GPU tensor (the HIP path has no CPU fallback)")
+    if mask_u8.dtype != torch.uint8:
+        raise TypeError(f"ipdm {what}: mask must be uint8 (ops._mask_u8 converts a host mask), got {mask_u8.dtype}")
+    if not mask_u8.is_contiguous():
+        raise ValueError(f"ipdm {what}: mask must be contiguous")
+    shape = tuple(mask_u8.shape)
+    if len(shape) == 2 and shape[0] >= 1 and shape[1] == W:
+        return shape[0]
+    if len(shape) == 3 and shape[0] >= 1 and shape[1:] == (H, W):
+        return -shape[0]
+    raise ValueError(f"ipdm {what}: mask {shape} is neither a line mask [mask_t, {W}] nor a 2-D mask [T, {H}, {W}]")
 
 
 def _sens_entry(sens, real_name, csm_name, H, W):
@@ -177,7 +212,8 @@ def sense_forward(x, sens_f32, mask_u8):
     fn = "ipdm_sense_forward_c64" if sens_f32 is None else _sens_entry(sens_f32, "ipdm_sense_forward_c64",
                                                                         "ipdm_sense_forward_csm_c64", H, W)
     y = torch.empty((n,) + tuple(x.shape), dtype=torch.complex64, device=x.device)
-    call(fn, _ptr(x), _ptr(sens_f32), _ptr(mask_u8), mask_u8.shape[0], _ptr(y), B, n, H, W,
+    mask_t = _mask_t(mask_u8, H, W, "sense_forward")
+    call(fn, _ptr(x), _ptr(sens_f32), _ptr(mask_u8), mask_t, _ptr(y), B, n, H, W,
          _stream())
     return y
 
@@ -213,7 +249,7 @@ def sense_adjoint(s, sens_f32, mask_u8=None, apply_mask=False):
         raise ValueError(f"sense_adjoint: {n} coil images, {sens_f32.shape[0]} coil maps")
     x = torch.empty(tuple(s.shape[1:]), dtype=torch.complex64, device=s.device)
     ws = sense_workspace(B, n, H, W, s.device) if _large_image(H, W) else None
-    call(fn, _ptr(s), _ptr(sens_f32), _ptr(mask_u8), 1 if mask_u8 is None else mask_u8.shape[0],
+    call(fn, _ptr(s), _ptr(sens_f32), _ptr(mask_u8), 1 if mask_u8 is None else _mask_t(mask_u8, H, W, "sense_adjoint"),
          int(bool(apply_mask)), _ptr(x), _ptr(ws), B, n, H, W, _stream())
     return x
 
@@ -241,7 +277,8 @@ def sense_l2prox(z_re, z_im, y, sens_f32, mask_u8, coef, out_re=None, out_im=Non
     out_im = torch.empty_like(z_im) if out_im is None else out_im
     work = sense_workspace(B, sens_f32.shape[0], H, W, z_re.device) if work is None else work
     _check_work(work, B, sens_f32.shape[0], H, W, "sense_l2prox")
-    call(fn, _ptr(z_re), _ptr(z_im), _ptr(y), _ptr(sens_f32), _ptr(mask_u8), mask_u8.shape[0],
+    mask_t = _mask_t(mask_u8, H, W, "sense_l2prox")
+    call(fn, _ptr(z_re), _ptr(z_im), _ptr(y), _ptr(sens_f32), _ptr(mask_u8), mask_t,
          float(coef), _ptr(out_re), _ptr(out_im), _ptr(work), B, sens_f32.shape[0], H, W, _stream())
     _written(out_re, out_im)
     return out_re, out_im
@@ -263,9 +300,10 @@ def ald_sense_step(x_re, x_im, g_re, g_im, y, sens_f32, mask_u8, work, step=0.0,
     if g_re.numel() != x_re.numel() or g_im.numel() != x_im.numel() or y.numel() != sens_f32.shape[0] * B * H * W:
         raise ValueError("ald_sense_step: operand sizes do not match the state")
     _check_work(work, B, sens_f32.shape[0], H, W, "ald_sense_step")
+    mask_t = _mask_t(mask_u8, H, W, "ald_sense_step")
     call(fn, _ptr(x_re), _ptr(x_im), _ptr(g_re), _ptr(g_im), _ptr(noise_re), _ptr(noise_im),
          float(step), float(noise_scale), int(seed), int(sample_offset), int(step_id), _ptr(dev_sched),
-         _ptr(y), _ptr(sens_f32), _ptr(mask_u8), mask_u8.shape[0], float(coef), _ptr(work), B, sens_f32.shape[0], H, W,
+         _ptr(y), _ptr(sens_f32), _ptr(mask_u8), mask_t, float(coef), _ptr(work), B, sens_f32.shape[0], H, W,
          _stream())
     _written(x_re, x_im)
 
@@ -324,7 +362,8 @@ def sense_cgprox(z_re, z_im, y, sens_f32, mask_u8, a, max_iter=10, tol=1e-5, ahy
     work, iters_out = _check_cg_args(work, ahy, iters_out, B, n, H, W, z_re.device, "sense_cgprox")
     out_re = torch.empty_like(z_re) if out_re is None else out_re
     out_im = torch.empty_like(z_im) if out_im is None else out_im
-    call(fn, _ptr(z_re), _ptr(z_im), _ptr(y), _ptr(sens_f32), _ptr(mask_u8), mask_u8.shape[0], float(a), _ptr(ahy),
+    mask_t = _mask_t(mask_u8, H, W, "sense_cgprox")
+    call(fn, _ptr(z_re), _ptr(z_im), _ptr(y), _ptr(sens_f32), _ptr(mask_u8), mask_t, float(a), _ptr(ahy),
          max_iter, tol, _ptr(out_re), _ptr(out_im), _ptr(work), _ptr(iters_out), B, n, H, W, _stream())
     _written(out_re, out_im, iters_out)
     return out_re, out_im, iters_out
@@ -349,9 +388,10 @@ def ald_sense_cg_step(x_re, x_im, g_re, g_im, y, sens_f32, mask_u8, work, step=0
     if g_re.numel() != x_re.numel() or g_im.numel() != x_im.numel() or y.numel() != nc * B * H * W:
         raise ValueError("ald_sense_cg_step: operand sizes do not match the state")
     work, iters_out = _check_cg_args(work, ahy, iters_out, B, nc, H, W, x_re.device, "ald_sense_cg_step")
+    mask_t = _mask_t(mask_u8, H, W, "ald_sense_cg_step")
     call(fn, _ptr(x_re), _ptr(x_im), _ptr(g_re), _ptr(g_im), _ptr(noise_re), _ptr(noise_im),
          float(step), float(noise_scale), int(seed), int(sample_offset), int(step_id), _ptr(dev_sched),
-         _ptr(y), _ptr(sens_f32), _ptr(mask_u8), mask_u8.shape[0], float(coef), _ptr(work), _ptr(ahy), max_iter, tol,
+         _ptr(y), _ptr(sens_f32), _ptr(mask_u8), mask_t, float(coef), _ptr(work), _ptr(ahy), max_iter, tol,
          _ptr(iters_out), B, nc, H, W, _stream())
     _written(x_re, x_im, iters_out)
     return iters_out
@@ -374,7 +414,8 @@ def singlecoil_prox(z_re, z_im, y, mask_u8, coef, mode, out_re=None, out_im=None
         work = sense_workspace(B, 1, H, W, z_re.device)
     if work is not None or _large_image(H, W):
         _check_work(work, B, 1, H, W, "singlecoil_prox")
-    call("ipdm_singlecoil_prox_f32", _ptr(z_re), _ptr(z_im), _ptr(y), _ptr(mask_u8), mask_u8.shape[0], float(coef),
+    mask_t = _mask_t(mask_u8, H, W, "singlecoil_prox")
+    call("ipdm_singlecoil_prox_f32", _ptr(z_re), _ptr(z_im), _ptr(y), _ptr(mask_u8), mask_t, float(coef),
          int(mode), _ptr(out_re), _ptr(out_im), _ptr(work), B, H, W, _stream())
     _written(out_re, out_im)
     return out_re, out_im
@@ -392,9 +433,10 @@ def ald_singlecoil_step(x_re, x_im, g_re, g_im, y, mask_u8, mode, step=0.0, nois
         work = sense_workspace(B, 1, H, W, x_re.device)
     if work is not None or _large_image(H, W):
         _check_work(work, B, 1, H, W, "ald_singlecoil_step")
+    mask_t = _mask_t(mask_u8, H, W, "ald_singlecoil_step")
     call("ipdm_ald_singlecoil_step_f32", _ptr(x_re), _ptr(x_im), _ptr(g_re), _ptr(g_im), _ptr(noise_re), _ptr(noise_im),
          float(step), float(noise_scale), int(seed), int(sample_offset), int(step_id), _ptr(dev_sched), _ptr(y),
-         _ptr(mask_u8), mask_u8.shape[0], float(coef), int(mode), _ptr(work), B, H, W, _stream())
+         _ptr(mask_u8), mask_t, float(coef), int(mode), _ptr(work), B, H, W, _stream())
     _written(x_re, x_im)
 
 

@@ -5,6 +5,7 @@ reference: SURVEY.md 8c/8d).
   reference's state-dict names, independent of module construction order.
 * ``phantom_image``     -- 6-ellipse magnitude phantom with a smooth phase, mirroring what
   ``helpers/load_data.py:372-387`` (add_phase: bicubic upsampling of an N(0,1) 5x5 patch) produces.
+* ``vd_mask_2d``        -- seeded variable-density 2-D (ky, kz) sampling mask with a fully sampled centre block.
 
 Everything here is host-side torch-CPU so the very same tensors are produced on the build
 container and on the GPU box.
@@ -91,3 +92,33 @@ def complex_coil_maps(n, H, W, seed=0):
         maps[i] = mag[i] * np.exp(1j * np.pi * 0.5 * phase)
     maps /= np.sqrt((np.abs(maps) ** 2).sum(0))
     return torch.from_numpy(maps)
+
+
+def vd_mask_2d(H, W, R, center_frac=0.04, seed=0, partial_fourier=None):
+    """bool (1, 1, H, W) variable-density 2-D sampling mask (the (ky, kz) pattern of a 3-D acquisition), numpy only and a
+    pure function of its arguments: a fully sampled centre block of max(2, round(center_frac * H)) by
+    max(2, round(center_frac * W)) samples, the rest drawn without replacement with a density 1 / (1 + (d / 0.25)^2) of the
+    normalised distance d from the centre, so that exactly round(H * W / R) samples are set (the block alone when it is
+    larger than that).  partial_fourier=f then zeroes the last 1 - f of the rows."""
+    import numpy as np
+    if R < 1:
+        raise ValueError(f"vd_mask_2d: R {R} < 1")
+    if partial_fourier is not None and not 0.0 < partial_fourier <= 1.0:
+        raise ValueError(f"vd_mask_2d: partial_fourier {partial_fourier} outside (0, 1]")
+    rng = np.random.RandomState(seed)
+    bh, bw = min(H, max(2, int(round(center_frac * H)))), min(W, max(2, int(round(center_frac * W))))
+    mask = np.zeros((H, W), dtype=bool)
+    r0, c0 = H // 2 - bh // 2, W // 2 - bw // 2
+    mask[r0:r0 + bh, c0:c0 + bw] = True
+    n_draw = int(round(H * W / R)) - bh * bw
+    if n_draw > 0:
+        u = (np.arange(H) - H // 2) / (H / 2.0)
+        v = (np.arange(W) - W // 2) / (W / 2.0)
+        d2 = u[:, None] ** 2 + v[None, :] ** 2
+        p = 1.0 / (1.0 + d2 / 0.25 ** 2)
+        p[mask] = 0.0
+        p = (p / p.sum()).ravel()
+        mask.ravel()[rng.choice(H * W, size=n_draw, replace=False, p=p)] = True
+    if partial_fourier is not None:
+        mask[int(round(partial_fourier * H)):] = False
+    return torch.from_numpy(mask)[None, None]

@@ -48,6 +48,10 @@ if __name__ == '__main__':
                         help=".npy / .pt file with measured coil maps (num_sens, H, W), real or complex")
     parser.add_argument("--sens_phase", action="store_true",
                         help="synthetic COMPLEX coil maps: the exp magnitudes times a smooth seeded phase")
+    parser.add_argument("--mask", default=None,
+                        help=".npy / .pt file with the sampling mask: a line mask (..., W) or a 2-D mask (..., H, W)")
+    parser.add_argument("--mask_2d", action="store_true",
+                        help="synthetic variable-density 2-D (ky, kz) sampling mask at --R instead of the line mask")
     parser.add_argument("--seg_synthetic", action="store_true",
                         help="run the guidance with seeded random UNet weights (exercises the path; not meaningful imaging)")
     args_dict = vars(parser.parse_args())
@@ -77,9 +81,11 @@ if __name__ == '__main__':
     elif args_dict["sens_phase"]:
         from inverseproblemwithdiffusionmodel_amd.synthetic import complex_coil_maps
         sens_maps = complex_coil_maps(args_dict["num_sens"], H, H, args_dict["seed"])
+    from inverseproblemwithdiffusionmodel_amd.helpers.load_data import driver_mask
+    mask = driver_mask(args_dict["mask"], args_dict["mask_2d"], H, H, args_dict["R"], args_dict["seed"])
     prob = engine.build_problem(device, n_local, R=args_dict["R"], H=H, W=H, num_sens=args_dict["num_sens"],
                                 seed=args_dict["seed"], scorenet=scorenet, cfg=cfg, lr_scaled=args_dict["lr_scaled"],
-                                sens_maps=sens_maps, proximal=args_dict["proximal_type"],
+                                sens_maps=sens_maps, mask=mask, proximal=args_dict["proximal_type"],
                                 proximal_kwargs=(dict(max_iter=args_dict["cg_iters"], tol=args_dict["cg_tol"])
                                                  if args_dict["proximal_type"] == "L2PenaltyCG" else None))
     label = None

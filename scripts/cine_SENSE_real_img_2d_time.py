@@ -47,13 +47,18 @@ if __name__ == '__main__':
                         help=".npy / .pt file with measured coil maps (num_sens, H, W), real or complex")
     parser.add_argument("--sens_phase", action="store_true",
                         help="synthetic COMPLEX coil maps: the exp magnitudes times a smooth seeded phase")
+    parser.add_argument("--mask", default=None,
+                        help=".npy / .pt file with the sampling mask: a line mask (..., W) or a 2-D mask (..., H, W), "
+                             "per frame as (T, 1, 1, W), (T, 1, H, W) or (T, H, W)")
+    parser.add_argument("--mask_2d", action="store_true",
+                        help="synthetic variable-density 2-D (ky, kz) sampling mask at --R instead of the line mask")
     a = parser.parse_args()
     from inverseproblemwithdiffusionmodel_amd.helpers.load_model import reload_model
     from inverseproblemwithdiffusionmodel_amd.ncsn.models import get_sigmas
     from inverseproblemwithdiffusionmodel_amd.ncsn.models.ALD_optimizers import ALD2DTime
     from inverseproblemwithdiffusionmodel_amd.ncsn.models.proximal_op import get_proximal
     from inverseproblemwithdiffusionmodel_amd.ncsn.linear_transforms.undersampling_fourier import SENSE
-    from inverseproblemwithdiffusionmodel_amd.helpers.load_data import driver_sens_maps
+    from inverseproblemwithdiffusionmodel_amd.helpers.load_data import driver_mask, driver_sens_maps
     from inverseproblemwithdiffusionmodel_amd.synthetic import phantom_image
     from inverseproblemwithdiffusionmodel_amd import sharding
     world, rank, device = sharding.init_distributed()
@@ -69,6 +74,9 @@ if __name__ == '__main__':
     op = SENSE(a.sens_type, a.num_sens, a.R, a.center_lines_frac, (1, H, W), a.seed, mask_T=24 if a.T == 24 else 1)
     if sens_maps is not None:
         op.sens_maps = sens_maps
+    mask = driver_mask(a.mask, a.mask_2d, H, W, a.R, a.seed)
+    if mask is not None:
+        op.random_under_fourier.mask = mask
     base = phantom_image(H, W, seed=a.seed).to(device)
     beat = torch.cos(torch.arange(a.T, device=device) * (2 * torch.pi / a.T)).view(a.T, 1, 1, 1)
     frames = base * (1.0 + 0.1 * beat)                                     # (T, 1, H, W): a slowly pulsating phantom
