@@ -151,28 +151,13 @@ __global__ __launch_bounds__(FFT_THREADS) void sense_adjoint_kernel(const float2
   }
 }
 
-// Langevin update of one sample's two planes, in place (the first phase of the fused iteration tails):
-//   x += step*g + noise_scale*n, n injected (n_re/n_im) or Philox keyed by (seed, global sample id, step, plane)
-__device__ __forceinline__ void langevin_phase(float* xr, float* xi, const float* __restrict__ g_re,
-                                               const float* __restrict__ g_im, const float* __restrict__ n_re,
-                                               const float* __restrict__ n_im, float step, float noise_scale,
-                                               uint64_t seed, int64_t sample_offset, int64_t step_id, int b, int HW) {
+// Langevin update of one sample's two planes, in place (the first phase of the fused iteration tails): x = langevin_value
+__device__ __forceinline__ void langevin_phase(float* xr, float* xi, const LangevinArgs& lg, int b, int HW) {
   for (int e = threadIdx.x; e < HW; e += FFT_THREADS) {
-    size_t gi = (size_t)b * HW + e;
-    float nr, ni;
-    if (n_re) {
-      nr = n_re[gi];
-      ni = n_im[gi];
-    } else {
-      float q[4];
-      const int lane4 = e & 3;
-      ipdm_philox_normal4(seed, sample_offset + b, step_id, 0, (uint32_t)(e >> 2), q);
-      nr = lane4 == 0 ? q[0] : lane4 == 1 ? q[1] : lane4 == 2 ? q[2] : q[3];
-      ipdm_philox_normal4(seed, sample_offset + b, step_id, 1, (uint32_t)(e >> 2), q);
-      ni = lane4 == 0 ? q[0] : lane4 == 1 ? q[1] : lane4 == 2 ? q[2] : q[3];
-    }
-    xr[e] = xr[e] + step * g_re[gi] + nr * noise_scale;
-    xi[e] = xi[e] + step * g_im[gi] + ni * noise_scale;
+    float zr, zi;
+    langevin_value(xr, xi, lg, b, HW, e, zr, zi);
+    xr[e] = zr;
+    xi[e] = zi;
   }
 }
 
@@ -182,27 +167,21 @@ __device__ __forceinline__ void langevin_phase(float* xr, float* xi, const float
 //   final:   x = z - coef * work
 // `work` ([B][H][W] c64) carries the coil sum so that no accumulator registers live across the FFTs.
 template <bool LANGEVIN, typename SensT>
-__global__ __launch_bounds__(FFT_THREADS) void ald_sense_step_kernel(
-    float* x_re, float* x_im, const float* __restrict__ g_re, const float* __restrict__ g_im,
-    const float* __restrict__ n_re, const float* __restrict__ n_im, float step, float noise_scale, uint64_t seed,
-    int64_t sample_offset, int64_t step_id, const ipdm_sched_t* __restrict__ sched, const float2* __restrict__ y,
-    const SensT* __restrict__ sens, const uint8_t* __restrict__ mask, int mask_t, float coef, float2* work, int B,
-    int n_coils, int H, int W) {
+__global__ __launch_bounds__(FFT_THREADS) void ald_sense_step_kernel(float* x_re, float* x_im, LangevinArgs lg,
+                                                                     const SenseProblem<SensT> pb, float coef, float2* work) {
+  const int B = pb.B, n_coils = pb.n_coils, H = pb.H, W = pb.W, mask_t = pb.mask_t;
+  const float2* __restrict__ y = pb.y;
+  const SensT* __restrict__ sens = pb.sens;
+  const uint8_t* __restrict__ mask = pb.mask;
   FFT_LDS_SETUP(H, W)
-  if (sched) {
-    step = sched->step;
-    noise_scale = sched->noise_scale;
-    coef = sched->coef;
-    step_id = sched->step_id;
-  }
+  coef = sched_override(lg, coef);
   const int HW = H * W;
   const int b = blockIdx.x;
   const float scale = rsqrtf((float)HW);
   float* xr = x_re + (size_t)b * HW;
   float* xi = x_im + (size_t)b * HW;
   float2* wk = work + (size_t)b * HW;
-  if constexpr (LANGEVIN)
-    langevin_phase(xr, xi, g_re, g_im, n_re, n_im, step, noise_scale, seed, sample_offset, step_id, b, HW);
+  if constexpr (LANGEVIN) langevin_phase(xr, xi, lg, b, HW);
   if (coef == 0.f) return;
   // pass 2c: forward transform of S_c z ; pass 2c+1: inverse transform of the masked residual
   for (int pass = 0; pass < 2 * n_coils; ++pass) {
@@ -218,19 +197,12 @@ __global__ __launch_bounds__(FFT_THREADS) void ald_sense_step_kernel(
     __syncthreads();
     fft2_lds(L, H, W, inv);
     if (!inv) {
-      // residual on the sampled columns, re-modulated for the inverse transform:
-      //   sign*(sign*scale*v - y) = scale*v - sign*y
       const float2* yc = y + ((size_t)coil * B + b) * HW;
       for (int e = threadIdx.x; e < HW; e += FFT_THREADS) {
         int r = e / W, c = e - r * W;
         float2 v = L.buf[e];
-        float2 res = make_float2(0.f, 0.f);
-        if (mask_at(mask, mask_t, b, H, W, r, c)) {
-          float sg = sign_rc(r, c);
-          float2 yy = yc[e];
-          res = make_float2(v.x * scale - sg * yy.x, v.y * scale - sg * yy.y);
-        }
-        L.buf[e] = res;
+        L.buf[e] = masked_residual(mask_at(mask, mask_t, b, H, W, r, c), make_float2(v.x * scale, v.y * scale), sign_rc(r, c),
+                                   yc + e);
       }
     } else {
       const bool last = coil == n_coils - 1;
@@ -254,90 +226,77 @@ __global__ __launch_bounds__(FFT_THREADS) void ald_sense_step_kernel(
   }
 }
 
-// The same iteration tail with the coils in parallel: a rank's batch is 13-14 samples, i.e. 14 of 256 CUs busy for four
-// dependent (FFT, inverse FFT) pairs in the one-workgroup-per-sample kernel above.  Here workgroup (coil, b) forms the
-// Langevin update z in registers (every coil workgroup of a sample computes the same z: the noise is injected or a pure
-// function of (seed, sample, step, element)), does ITS coil's transform pair and writes r_c = conj-free S_c F^-1[M (F S_c z - y_c)]
-// to work[b][coil]; ald_sense_combine_kernel then forms z once more and x = z - coef * (((r_0 + r_1) + r_2) + ...) in the
-// sequential kernel's order: bit-identical results, 56 workgroups instead of 14, one transform pair deep instead of four.
-template <bool LANGEVIN, typename SensT>
-__global__ __launch_bounds__(FFT_THREADS) void ald_sense_coil_kernel(
-    const float* x_re, const float* x_im, const float* __restrict__ g_re, const float* __restrict__ g_im,
-    const float* __restrict__ n_re, const float* __restrict__ n_im, float step, float noise_scale, uint64_t seed,
-    int64_t sample_offset, int64_t step_id, const ipdm_sched_t* __restrict__ sched, const float2* __restrict__ y,
-    const SensT* __restrict__ sens, const uint8_t* __restrict__ mask, int mask_t, float coef, float2* work, int B,
-    int n_coils, int H, int W) {
-  FFT_LDS_SETUP(H, W)
-  if (sched) {
-    step = sched->step;
-    noise_scale = sched->noise_scale;
-    coef = sched->coef;
-    step_id = sched->step_id;
-  }
-  if (coef == 0.f) return;                                    // the combine pass then only applies the Langevin update
-  const int HW = H * W;
+// The normal operator with the coils in parallel (launch_normal_coils, kspace_fft.h), the first half of the coil-parallel
+// iteration tail and of every conjugate-gradient step.  A rank's batch is 13-14 samples, i.e. 14 of 256 CUs busy for four
+// dependent (FFT, inverse FFT) pairs in the one-workgroup-per-sample kernel above.  Here workgroup (coil, b) forms its input
+// v in registers (MODE 2: every coil workgroup of a sample computes the same Langevin update z: the noise is injected or a
+// pure function of (seed, sample, step, element)), does ITS coil's transform pair and writes
+// r_c = conj(S_c) F^-1[M (F S_c v - y_c)] to planes[b][coil]: 56 workgroups instead of 14, one transform pair deep instead
+// of four.
+template <int MODE, typename SensT>
+__global__ __launch_bounds__(FFT_THREADS) void sense_normal_coil_kernel(const float* x_re, const float* x_im, LangevinArgs lg,
+                                                                        float coef, const float2* __restrict__ p,
+                                                                        const CgState* __restrict__ state,
+                                                                        const SenseProblem<SensT> pb, float2* __restrict__ planes) {
+  const int B = pb.B, n_coils = pb.n_coils, H = pb.H, W = pb.W, mask_t = pb.mask_t;
+  const SensT* __restrict__ sens = pb.sens;
+  const uint8_t* __restrict__ mask = pb.mask;
   const int coil = blockIdx.x, b = blockIdx.y;
+  if constexpr (MODE == 0) {
+    if (state[b].frozen) return;
+  } else {
+    // the tail's combine pass then only applies the Langevin update; the CG init pass leaves x = z and freezes the sample
+    if (sched_override(lg, coef) == 0.f) return;
+  }
+  FFT_LDS_SETUP(H, W)
+  const int HW = H * W;
   const float scale = rsqrtf((float)HW);
-  const float* xr = x_re + (size_t)b * HW;
-  const float* xi = x_im + (size_t)b * HW;
   const SensT* sm = sens + (size_t)coil * HW;
   for (int e = threadIdx.x; e < HW; e += FFT_THREADS) {
-    float zr = xr[e], zi = xi[e];
-    if constexpr (LANGEVIN)
-      langevin_value(xr, xi, g_re, g_im, n_re, n_im, step, noise_scale, seed, sample_offset, step_id, b, HW, e, zr, zi);
+    float2 v;
+    if constexpr (MODE == 0) {
+      v = p[(size_t)b * HW + e];
+    } else {
+      const float* xr = x_re + (size_t)b * HW;
+      const float* xi = x_im + (size_t)b * HW;
+      v = make_float2(xr[e], xi[e]);
+      if constexpr (MODE == 2) langevin_value(xr, xi, lg, b, HW, e, v.x, v.y);
+    }
     const int r = e / W, c = e - r * W;
-    L.buf[e] = sens_mul(make_float2(zr, zi), sign_rc(r, c), sm[e]);
+    L.buf[e] = sens_mul(v, sign_rc(r, c), sm[e]);
   }
   __syncthreads();
   fft2_lds(L, H, W, false);
-  const float2* yc = y + ((size_t)coil * B + b) * HW;
+  const float2* __restrict__ yc = MODE == 0 ? nullptr : pb.y + ((size_t)coil * B + b) * HW;
   for (int e = threadIdx.x; e < HW; e += FFT_THREADS) {
     const int r = e / W, c = e - r * W;
     const float2 v = L.buf[e];
-    float2 res = make_float2(0.f, 0.f);
-    if (mask_at(mask, mask_t, b, H, W, r, c)) {
-      const float sg = sign_rc(r, c);
-      const float2 yy = yc[e];
-      res = make_float2(v.x * scale - sg * yy.x, v.y * scale - sg * yy.y);
-    }
-    L.buf[e] = res;
+    L.buf[e] = masked_residual(mask_at(mask, mask_t, b, H, W, r, c), make_float2(v.x * scale, v.y * scale), sign_rc(r, c),
+                               MODE == 0 ? nullptr : yc + e);
   }
   __syncthreads();
   fft2_lds(L, H, W, true);
-  float2* wk = work + ((size_t)b * n_coils + coil) * HW;
+  float2* wk = planes + ((size_t)b * n_coils + coil) * HW;
   for (int e = threadIdx.x; e < HW; e += FFT_THREADS) {
     const int r = e / W, c = e - r * W;
-    const float2 v = L.buf[e];
-    wk[e] = sens_mul_conj(v, sign_rc(r, c) * scale, sm[e]);
+    wk[e] = sens_mul_conj(L.buf[e], sign_rc(r, c) * scale, sm[e]);
   }
 }
 
+// Second half of the coil-parallel tail: forms z once more and x = z - coef * (((r_0 + r_1) + r_2) + ...), the sequential
+// kernel's order: bit-identical results.
 template <bool LANGEVIN>
-__global__ __launch_bounds__(256) void ald_sense_combine_kernel(
-    float* x_re, float* x_im, const float* __restrict__ g_re, const float* __restrict__ g_im,
-    const float* __restrict__ n_re, const float* __restrict__ n_im, float step, float noise_scale, uint64_t seed,
-    int64_t sample_offset, int64_t step_id, const ipdm_sched_t* __restrict__ sched, float coef,
-    const float2* __restrict__ work, int B, int n_coils, int HW) {
-  if (sched) {
-    step = sched->step;
-    noise_scale = sched->noise_scale;
-    coef = sched->coef;
-    step_id = sched->step_id;
-  }
+__global__ __launch_bounds__(256) void ald_sense_combine_kernel(float* x_re, float* x_im, LangevinArgs lg, float coef,
+                                                                const float2* __restrict__ work, int n_coils, int HW) {
+  coef = sched_override(lg, coef);
   const int b = blockIdx.y;
   float* xr = x_re + (size_t)b * HW;
   float* xi = x_im + (size_t)b * HW;
   for (int e = blockIdx.x * 256 + threadIdx.x; e < HW; e += gridDim.x * 256) {
     float zr = xr[e], zi = xi[e];
-    if constexpr (LANGEVIN)
-      langevin_value(xr, xi, g_re, g_im, n_re, n_im, step, noise_scale, seed, sample_offset, step_id, b, HW, e, zr, zi);
+    if constexpr (LANGEVIN) langevin_value(xr, xi, lg, b, HW, e, zr, zi);
     if (coef != 0.f) {
-      const float2* wk = work + (size_t)b * n_coils * HW + e;
-      float2 a = wk[0];
-      for (int c = 1; c < n_coils; ++c) {                     // a_c = r_c + a_(c-1): the one-workgroup kernel's order
-        const float2 rc = wk[(size_t)c * HW];
-        a = make_float2(rc.x + a.x, rc.y + a.y);
-      }
+      const float2 a = plane_sum(work + (size_t)b * n_coils * HW, n_coils, HW, e);
       zr = zr - coef * a.x;
       zi = zi - coef * a.y;
     }
@@ -351,27 +310,21 @@ __global__ __launch_bounds__(256) void ald_sense_combine_kernel(
 //   mode 0  L2Penalty   x = z - coef * F^-1[ M (M F z - y) ]               (proximal_op.py:19-51, coef = 0.05 a/(l K), K = B)
 //   mode 1  SingleCoil  x = F^-1[ (F z + coef*y) / (1 + coef*M) ]          (proximal_op.py:72-94, coef = alpha/lamda)
 //   mode 2  projection  x = F^-1[ coef*y + (1-coef) M F z + (1-M) F z ]   (undersampling_fourier.py:89-97, coef = lamda)
-// The image stays in LDS between the two transforms; z is re-read from x (L2-resident) for mode 0.
+// The image stays in LDS between the two transforms; z is re-read from x (L2-resident) for mode 0.  pb.sens is not used.
 template <bool LANGEVIN>
-__global__ __launch_bounds__(FFT_THREADS) void ald_singlecoil_step_kernel(
-    float* x_re, float* x_im, const float* __restrict__ g_re, const float* __restrict__ g_im,
-    const float* __restrict__ n_re, const float* __restrict__ n_im, float step, float noise_scale, uint64_t seed,
-    int64_t sample_offset, int64_t step_id, const ipdm_sched_t* __restrict__ sched, const float2* __restrict__ y,
-    const uint8_t* __restrict__ mask, int mask_t, float coef, int mode, int B, int H, int W) {
+__global__ __launch_bounds__(FFT_THREADS) void ald_singlecoil_step_kernel(float* x_re, float* x_im, LangevinArgs lg,
+                                                                          const SenseProblem<float> pb, float coef, int mode) {
+  const int H = pb.H, W = pb.W, mask_t = pb.mask_t;
+  const float2* __restrict__ y = pb.y;
+  const uint8_t* __restrict__ mask = pb.mask;
   FFT_LDS_SETUP(H, W)
-  if (sched) {
-    step = sched->step;
-    noise_scale = sched->noise_scale;
-    coef = sched->coef;
-    step_id = sched->step_id;
-  }
+  coef = sched_override(lg, coef);
   const int HW = H * W;
   const int b = blockIdx.x;
   const float scale = rsqrtf((float)HW);
   float* xr = x_re + (size_t)b * HW;
   float* xi = x_im + (size_t)b * HW;
-  if constexpr (LANGEVIN)
-    langevin_phase(xr, xi, g_re, g_im, n_re, n_im, step, noise_scale, seed, sample_offset, step_id, b, HW);
+  if constexpr (LANGEVIN) langevin_phase(xr, xi, lg, b, HW);
   if (mode == 0 && coef == 0.f) return;
   for (int e = threadIdx.x; e < HW; e += FFT_THREADS) {
     int r = e / W, c = e - r * W;
@@ -390,12 +343,7 @@ __global__ __launch_bounds__(FFT_THREADS) void ald_singlecoil_step_kernel(
     const bool m = mask_at(mask, mask_t, b, H, W, r, c);
     float2 o;
     if (mode == 0) {
-      o = make_float2(0.f, 0.f);
-      if (m) {
-        float sg = sign_rc(r, c);
-        float2 yy = yb[e];
-        o = make_float2(v.x - sg * yy.x, v.y - sg * yy.y);
-      }
+      o = masked_residual(m, v, sign_rc(r, c), yb + e);
     } else if (mode == 1) {
       float sg = sign_rc(r, c) * coef;
       float2 yy = yb[e];
@@ -425,28 +373,48 @@ __global__ __launch_bounds__(FFT_THREADS) void ald_singlecoil_step_kernel(
   }
 }
 
-template <bool LANGEVIN, typename SensT>
-static int launch_sense_step_coils(float* x_re, float* x_im, const float* g_re, const float* g_im, const float* n_re,
-                                   const float* n_im, float step, float noise_scale, uint64_t seed, int64_t sample_offset,
-                                   int64_t step_id, const ipdm_sched_t* sched, const float2* y, const SensT* sens,
-                                   const uint8_t* mask, int mask_t, float coef, float2* work, int B, int n_coils, int H,
-                                   int W, hipStream_t st) {
-  if (B > 65535) return IPDM_EUNSUPPORTED;
-  const size_t lds = lds_bytes(H, W);
-  const int rc = set_lds_limit(ald_sense_coil_kernel<LANGEVIN, SensT>, lds);
+template <int MODE, typename SensT>
+static int launch_normal_coils_mode(const float* x_re, const float* x_im, const LangevinArgs& lg, float coef, const float2* p,
+                                    const CgState* state, const SenseProblem<SensT>& pb, float2* planes, hipStream_t st) {
+  const size_t lds = lds_bytes(pb.H, pb.W);
+  const int rc = set_lds_limit(sense_normal_coil_kernel<MODE, SensT>, lds);
   if (rc) return rc;
-  hipLaunchKernelGGL((ald_sense_coil_kernel<LANGEVIN, SensT>), dim3(n_coils, B), dim3(FFT_THREADS), lds, st, x_re, x_im, g_re, g_im,
-                     n_re, n_im, step, noise_scale, seed, (long long)sample_offset, (long long)step_id, sched, y, sens, mask,
-                     mask_t, coef, work, B, n_coils, H, W);
-  const int HW = H * W;
+  hipLaunchKernelGGL((sense_normal_coil_kernel<MODE, SensT>), dim3(pb.n_coils, pb.B), dim3(FFT_THREADS), lds, st, x_re, x_im, lg,
+                     coef, p, state, pb, planes);
+  return ipdm_launch_status();
+}
+
+// the coil-parallel iteration tail: normal operator per coil, then the combine pass
+template <typename SensT>
+static int launch_sense_step_coils(float* x_re, float* x_im, const LangevinArgs& lg, const SenseProblem<SensT>& pb, float coef,
+                                   float2* work, hipStream_t st) {
+  if (pb.B > 65535) return IPDM_EUNSUPPORTED;
+  const int rc = launch_normal_coils(lg.g_re ? 2 : 1, x_re, x_im, lg, coef, nullptr, nullptr, pb, work, st);
+  if (rc) return rc;
+  const int HW = pb.H * pb.W;
   int gx = (HW + 255) / 256;
   if (gx > 64) gx = 64;
-  hipLaunchKernelGGL(ald_sense_combine_kernel<LANGEVIN>, dim3(gx, B), dim3(256), 0, st, x_re, x_im, g_re, g_im, n_re, n_im,
-                     step, noise_scale, seed, (long long)sample_offset, (long long)step_id, sched, coef, work, B, n_coils, HW);
+  if (lg.g_re)
+    hipLaunchKernelGGL(ald_sense_combine_kernel<true>, dim3(gx, pb.B), dim3(256), 0, st, x_re, x_im, lg, coef, work, pb.n_coils, HW);
+  else
+    hipLaunchKernelGGL(ald_sense_combine_kernel<false>, dim3(gx, pb.B), dim3(256), 0, st, x_re, x_im, lg, coef, work, pb.n_coils, HW);
   return ipdm_launch_status();
 }
 
 }  // namespace
+
+template <typename SensT>
+int ipdm_kspace::launch_normal_coils(int mode, const float* x_re, const float* x_im, const LangevinArgs& lg, float coef,
+                                     const float2* p, const CgState* state, const SenseProblem<SensT>& pb, float2* planes,
+                                     hipStream_t st) {
+  if (mode == 0) return launch_normal_coils_mode<0>(x_re, x_im, lg, coef, p, state, pb, planes, st);
+  if (mode == 1) return launch_normal_coils_mode<1>(x_re, x_im, lg, coef, p, state, pb, planes, st);
+  return launch_normal_coils_mode<2>(x_re, x_im, lg, coef, p, state, pb, planes, st);
+}
+template int ipdm_kspace::launch_normal_coils(int, const float*, const float*, const LangevinArgs&, float, const float2*,
+                                              const CgState*, const SenseProblem<float>&, float2*, hipStream_t);
+template int ipdm_kspace::launch_normal_coils(int, const float*, const float*, const LangevinArgs&, float, const float2*,
+                                              const CgState*, const SenseProblem<float2>&, float2*, hipStream_t);
 
 extern "C" int64_t ipdm_fft2c_workspace_bytes(int batch, int H, int W) {
   if (batch <= 0 || H <= 0 || W <= 0) return 0;
@@ -496,69 +464,66 @@ extern "C" int ipdm_fft2c_c64(const float* in, float* out, int batch, int H, int
 }
 
 template <typename SensT>
-static int sense_forward_impl(const float* x, const SensT* sens, const uint8_t* mask, int mask_t, float* y,
-                                      int B, int n_coils, int H, int W, void* stream) {
-  IPDM_REQUIRE(B >= 0 && n_coils > 0 && H > 0 && W > 0 && mask_t_ok(mask_t));
-  if (B == 0) return IPDM_OK;
-  IPDM_REQUIRE(x && mask && y && (sens || n_coils == 1));
-  if (ipdm_kspace_large::large_ok(H, W))
-    return ipdm_kspace_large::sense_forward(reinterpret_cast<const float2*>(x), sens, mask, mask_t,
-                                            reinterpret_cast<float2*>(y), B, n_coils, H, W, ipdm_stream(stream));
-  if (!lds_fft_ok(H, W)) return IPDM_EUNSUPPORTED;
-  size_t lds = lds_bytes(H, W);
+static int sense_forward_impl(const float* x, const SenseProblem<SensT>& pb, float* y, void* stream) {
+  IPDM_REQUIRE(dims_ok(pb));
+  if (pb.B == 0) return IPDM_OK;
+  IPDM_REQUIRE(x && pb.mask && y && (pb.sens || pb.n_coils == 1));
+  if (ipdm_kspace_large::large_ok(pb.H, pb.W))
+    return ipdm_kspace_large::sense_forward(reinterpret_cast<const float2*>(x), pb, reinterpret_cast<float2*>(y),
+                                            ipdm_stream(stream));
+  if (!lds_fft_ok(pb.H, pb.W)) return IPDM_EUNSUPPORTED;
+  size_t lds = lds_bytes(pb.H, pb.W);
   int rc = set_lds_limit(sense_forward_kernel<SensT>, lds);
   if (rc) return rc;
-  hipLaunchKernelGGL(sense_forward_kernel<SensT>, dim3(B, n_coils), dim3(FFT_THREADS), lds, ipdm_stream(stream),
-                     reinterpret_cast<const float2*>(x), sens, mask, mask_t, reinterpret_cast<float2*>(y), B, H, W);
+  hipLaunchKernelGGL(sense_forward_kernel<SensT>, dim3(pb.B, pb.n_coils), dim3(FFT_THREADS), lds, ipdm_stream(stream),
+                     reinterpret_cast<const float2*>(x), pb.sens, pb.mask, pb.mask_t, reinterpret_cast<float2*>(y), pb.B, pb.H,
+                     pb.W);
   return ipdm_launch_status();
 }
 
+// pb.y: the coil images s; pb.mask_t is looked at only with apply_mask
 template <typename SensT>
-static int sense_adjoint_impl(const float* s, const SensT* sens, const uint8_t* mask, int mask_t,
-                                      int apply_mask, float* x, float* workspace, int B, int n_coils, int H, int W,
-                                      void* stream) {
-  IPDM_REQUIRE(B >= 0 && n_coils > 0 && H > 0 && W > 0);
-  if (B == 0) return IPDM_OK;
-  IPDM_REQUIRE(s && sens && x);
-  if (apply_mask) IPDM_REQUIRE(mask && mask_t_ok(mask_t));
-  if (ipdm_kspace_large::large_ok(H, W)) {
+static int sense_adjoint_impl(SenseProblem<SensT> pb, int apply_mask, float* x, float* workspace, void* stream) {
+  IPDM_REQUIRE(pb.B >= 0 && pb.n_coils > 0 && pb.H > 0 && pb.W > 0);
+  if (pb.B == 0) return IPDM_OK;
+  IPDM_REQUIRE(pb.y && pb.sens && x);
+  if (apply_mask) IPDM_REQUIRE(pb.mask && mask_t_ok(pb.mask_t));
+  else pb.mask_t = 1;
+  if (ipdm_kspace_large::large_ok(pb.H, pb.W)) {
     IPDM_REQUIRE(workspace);
-    return ipdm_kspace_large::sense_adjoint(reinterpret_cast<const float2*>(s), sens, mask, apply_mask ? mask_t : 1,
-                                            apply_mask, reinterpret_cast<float2*>(x), nullptr,
-                                            reinterpret_cast<float2*>(workspace), B, n_coils, H, W, ipdm_stream(stream));
+    return ipdm_kspace_large::sense_adjoint(pb, apply_mask, reinterpret_cast<float2*>(x), nullptr,
+                                            reinterpret_cast<float2*>(workspace), ipdm_stream(stream));
   }
-  if (!lds_fft_ok(H, W)) return IPDM_EUNSUPPORTED;
-  size_t lds = lds_bytes(H, W);
+  if (!lds_fft_ok(pb.H, pb.W)) return IPDM_EUNSUPPORTED;
+  size_t lds = lds_bytes(pb.H, pb.W);
   int rc = set_lds_limit(sense_adjoint_kernel<false, SensT>, lds);
   if (rc) return rc;
-  hipLaunchKernelGGL((sense_adjoint_kernel<false, SensT>), dim3(B), dim3(FFT_THREADS), lds, ipdm_stream(stream),
-                     reinterpret_cast<const float2*>(s), sens, mask, apply_mask ? mask_t : 1, apply_mask, x, B, n_coils,
-                     H, W);
+  hipLaunchKernelGGL((sense_adjoint_kernel<false, SensT>), dim3(pb.B), dim3(FFT_THREADS), lds, ipdm_stream(stream), pb.y, pb.sens,
+                     pb.mask, pb.mask_t, apply_mask, x, pb.B, pb.n_coils, pb.H, pb.W);
   return ipdm_launch_status();
 }
 
 extern "C" int ipdm_sense_forward_c64(const float* x, const float* sens, const uint8_t* mask, int mask_t, float* y,
                                       int B, int n_coils, int H, int W, void* stream) {
-  return sense_forward_impl(x, sens, mask, mask_t, y, B, n_coils, H, W, stream);
+  return sense_forward_impl(x, sense_problem<float>(nullptr, sens, mask, mask_t, B, n_coils, H, W), y, stream);
 }
 
 extern "C" int ipdm_sense_forward_csm_c64(const float* x, const float* sens, const uint8_t* mask, int mask_t, float* y,
                                           int B, int n_coils, int H, int W, void* stream) {
   IPDM_REQUIRE(sens || B == 0);                                 // no single-coil shortcut here: complex maps are required
-  return sense_forward_impl(x, reinterpret_cast<const float2*>(sens), mask, mask_t, y, B, n_coils, H, W, stream);
+  return sense_forward_impl(x, sense_problem<float2>(nullptr, sens, mask, mask_t, B, n_coils, H, W), y, stream);
 }
 
 extern "C" int ipdm_sense_adjoint_c64(const float* s, const float* sens, const uint8_t* mask, int mask_t,
                                       int apply_mask, float* x, float* workspace, int B, int n_coils, int H, int W,
                                       void* stream) {
-  return sense_adjoint_impl(s, sens, mask, mask_t, apply_mask, x, workspace, B, n_coils, H, W, stream);
+  return sense_adjoint_impl(sense_problem<float>(s, sens, mask, mask_t, B, n_coils, H, W), apply_mask, x, workspace, stream);
 }
 
 extern "C" int ipdm_sense_adjoint_csm_c64(const float* s, const float* sens, const uint8_t* mask, int mask_t,
                                           int apply_mask, float* x, float* workspace, int B, int n_coils, int H, int W,
                                           void* stream) {
-  return sense_adjoint_impl(s, reinterpret_cast<const float2*>(sens), mask, mask_t, apply_mask, x, workspace, B, n_coils,
-                            H, W, stream);
+  return sense_adjoint_impl(sense_problem<float2>(s, sens, mask, mask_t, B, n_coils, H, W), apply_mask, x, workspace, stream);
 }
 
 extern "C" int ipdm_sense_ssos_c64(const float* s, float* out, float* workspace, int B, int n_coils, int H, int W,
@@ -568,8 +533,8 @@ extern "C" int ipdm_sense_ssos_c64(const float* s, float* out, float* workspace,
   IPDM_REQUIRE(s && out);
   if (ipdm_kspace_large::large_ok(H, W)) {
     IPDM_REQUIRE(workspace);
-    return ipdm_kspace_large::sense_adjoint<float>(reinterpret_cast<const float2*>(s), nullptr, nullptr, 1, 0, nullptr, out,
-                                            reinterpret_cast<float2*>(workspace), B, n_coils, H, W, ipdm_stream(stream));
+    return ipdm_kspace_large::sense_adjoint(sense_problem<float>(s, nullptr, nullptr, 1, B, n_coils, H, W), 0, nullptr, out,
+                                            reinterpret_cast<float2*>(workspace), ipdm_stream(stream));
   }
   if (!lds_fft_ok(H, W)) return IPDM_EUNSUPPORTED;
   size_t lds = lds_bytes(H, W);
@@ -580,76 +545,60 @@ extern "C" int ipdm_sense_ssos_c64(const float* s, float* out, float* workspace,
   return ipdm_launch_status();
 }
 
+// x_re / x_im hold z (Langevin pending when lg.g_re) and receive the proximal
 template <typename SensT>
-static int sense_l2prox_impl(const float* z_re, const float* z_im, const float* y, const SensT* sens,
-                                     const uint8_t* mask, int mask_t, float coef, float* out_re, float* out_im,
-                                     float* work, int B, int n_coils, int H, int W, void* stream) {
-  IPDM_REQUIRE(B >= 0 && n_coils > 0 && H > 0 && W > 0 && mask_t_ok(mask_t));
-  if (B == 0) return IPDM_OK;
-  IPDM_REQUIRE(z_re && z_im && y && sens && mask && out_re && out_im && work);
-  const bool large = ipdm_kspace_large::large_ok(H, W);
-  if (!large && !lds_fft_ok(H, W)) return IPDM_EUNSUPPORTED;
-  hipStream_t st = ipdm_stream(stream);
-  const size_t bytes = (size_t)B * H * W * sizeof(float);
-  if (out_re != z_re && hipMemcpyAsync(out_re, z_re, bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) return (int)hipGetLastError();
-  if (out_im != z_im && hipMemcpyAsync(out_im, z_im, bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) return (int)hipGetLastError();
-  if (large)
-    return ipdm_kspace_large::prox_step(out_re, out_im, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, 0ull, 0, 0, nullptr,
-                                        reinterpret_cast<const float2*>(y), sens, mask, mask_t, coef, 0,
-                                        reinterpret_cast<float2*>(work), B, n_coils, H, W, st);
-  if (sense_coil_parallel())
-    return launch_sense_step_coils<false>(out_re, out_im, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, 0ull, 0, 0, nullptr,
-                                          reinterpret_cast<const float2*>(y), sens, mask, mask_t, coef,
-                                          reinterpret_cast<float2*>(work), B, n_coils, H, W, st);
-  size_t lds = lds_bytes(H, W);
-  int rc = set_lds_limit(ald_sense_step_kernel<false, SensT>, lds);
-  if (rc) return rc;
-  hipLaunchKernelGGL((ald_sense_step_kernel<false, SensT>), dim3(B), dim3(FFT_THREADS), lds, st, out_re, out_im, nullptr,
-                     nullptr, nullptr, nullptr, 0.f, 0.f, 0ull, 0ll, 0ll, nullptr, reinterpret_cast<const float2*>(y), sens,
-                     mask, mask_t, coef, reinterpret_cast<float2*>(work), B, n_coils, H, W);
+static int sense_step(float* x_re, float* x_im, const LangevinArgs& lg, const SenseProblem<SensT>& pb, float coef, float* work,
+                      hipStream_t st) {
+  float2* wk = reinterpret_cast<float2*>(work);
+  if (ipdm_kspace_large::large_ok(pb.H, pb.W)) return ipdm_kspace_large::prox_step(x_re, x_im, lg, pb, coef, 0, wk, st);
+  if (!lds_fft_ok(pb.H, pb.W)) return IPDM_EUNSUPPORTED;
+  if (sense_coil_parallel()) return launch_sense_step_coils(x_re, x_im, lg, pb, coef, wk, st);
+  const size_t lds = lds_bytes(pb.H, pb.W);
+  if (lg.g_re) {
+    int rc = set_lds_limit(ald_sense_step_kernel<true, SensT>, lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL((ald_sense_step_kernel<true, SensT>), dim3(pb.B), dim3(FFT_THREADS), lds, st, x_re, x_im, lg, pb, coef, wk);
+  } else {
+    int rc = set_lds_limit(ald_sense_step_kernel<false, SensT>, lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL((ald_sense_step_kernel<false, SensT>), dim3(pb.B), dim3(FFT_THREADS), lds, st, x_re, x_im, lg, pb, coef, wk);
+  }
   return ipdm_launch_status();
 }
 
 template <typename SensT>
-static int ald_sense_step_impl(float* x_re, float* x_im, const float* g_re, const float* g_im,
-                                       const float* noise_re, const float* noise_im, float step, float noise_scale,
-                                       uint64_t seed, int64_t sample_offset, int64_t step_id,
-                                       const ipdm_sched_t* dev_sched, const float* y, const SensT* sens, const uint8_t* mask, int mask_t, float coef, float* work,
-                                       int B, int n_coils, int H, int W, void* stream) {
-  IPDM_REQUIRE(B >= 0 && n_coils > 0 && H > 0 && W > 0 && mask_t_ok(mask_t));
-  if (B == 0) return IPDM_OK;
-  IPDM_REQUIRE(x_re && x_im && g_re && g_im && y && sens && mask && work);
-  IPDM_REQUIRE((noise_re == nullptr) == (noise_im == nullptr));
-  if (ipdm_kspace_large::large_ok(H, W))
-    return ipdm_kspace_large::prox_step(x_re, x_im, g_re, g_im, noise_re, noise_im, step, noise_scale, seed, sample_offset,
-                                        step_id, dev_sched, reinterpret_cast<const float2*>(y), sens, mask, mask_t, coef, 0,
-                                        reinterpret_cast<float2*>(work), B, n_coils, H, W, ipdm_stream(stream));
-  if (!lds_fft_ok(H, W)) return IPDM_EUNSUPPORTED;
-  if (sense_coil_parallel())
-    return launch_sense_step_coils<true>(x_re, x_im, g_re, g_im, noise_re, noise_im, step, noise_scale, seed, sample_offset,
-                                         step_id, dev_sched, reinterpret_cast<const float2*>(y), sens, mask, mask_t, coef,
-                                         reinterpret_cast<float2*>(work), B, n_coils, H, W, ipdm_stream(stream));
-  size_t lds = lds_bytes(H, W);
-  int rc = set_lds_limit(ald_sense_step_kernel<true, SensT>, lds);
-  if (rc) return rc;
-  hipLaunchKernelGGL((ald_sense_step_kernel<true, SensT>), dim3(B), dim3(FFT_THREADS), lds, ipdm_stream(stream), x_re, x_im,
-                     g_re, g_im, noise_re, noise_im, step, noise_scale, seed, (long long)sample_offset,
-                     (long long)step_id, dev_sched, reinterpret_cast<const float2*>(y), sens, mask, mask_t, coef,
-                     reinterpret_cast<float2*>(work), B, n_coils, H, W);
-  return ipdm_launch_status();
+static int sense_l2prox_impl(const float* z_re, const float* z_im, const SenseProblem<SensT>& pb, float coef, float* out_re,
+                             float* out_im, float* work, void* stream) {
+  IPDM_REQUIRE(dims_ok(pb));
+  if (pb.B == 0) return IPDM_OK;
+  IPDM_REQUIRE(z_re && z_im && pb.y && pb.sens && pb.mask && out_re && out_im && work);
+  if (!ipdm_kspace_large::large_ok(pb.H, pb.W) && !lds_fft_ok(pb.H, pb.W)) return IPDM_EUNSUPPORTED;
+  hipStream_t st = ipdm_stream(stream);
+  const int rc = copy_planes(out_re, out_im, z_re, z_im, (size_t)pb.B * pb.H * pb.W, st);
+  return rc ? rc : sense_step(out_re, out_im, NO_LANGEVIN, pb, coef, work, st);
+}
+
+template <typename SensT>
+static int ald_sense_step_impl(float* x_re, float* x_im, const LangevinArgs& lg, const SenseProblem<SensT>& pb, float coef,
+                               float* work, void* stream) {
+  IPDM_REQUIRE(dims_ok(pb));
+  if (pb.B == 0) return IPDM_OK;
+  IPDM_REQUIRE(step_ptrs_ok(x_re, x_im, lg, pb) && pb.sens && work);
+  return sense_step(x_re, x_im, lg, pb, coef, work, ipdm_stream(stream));
 }
 
 extern "C" int ipdm_sense_l2prox_f32(const float* z_re, const float* z_im, const float* y, const float* sens,
                                      const uint8_t* mask, int mask_t, float coef, float* out_re, float* out_im,
                                      float* work, int B, int n_coils, int H, int W, void* stream) {
-  return sense_l2prox_impl(z_re, z_im, y, sens, mask, mask_t, coef, out_re, out_im, work, B, n_coils, H, W, stream);
+  return sense_l2prox_impl(z_re, z_im, sense_problem<float>(y, sens, mask, mask_t, B, n_coils, H, W), coef, out_re, out_im, work,
+                           stream);
 }
 
 extern "C" int ipdm_sense_l2prox_csm_f32(const float* z_re, const float* z_im, const float* y, const float* sens,
                                          const uint8_t* mask, int mask_t, float coef, float* out_re, float* out_im,
                                          float* work, int B, int n_coils, int H, int W, void* stream) {
-  return sense_l2prox_impl(z_re, z_im, y, reinterpret_cast<const float2*>(sens), mask, mask_t, coef, out_re, out_im, work, B,
-                           n_coils, H, W, stream);
+  return sense_l2prox_impl(z_re, z_im, sense_problem<float2>(y, sens, mask, mask_t, B, n_coils, H, W), coef, out_re, out_im, work,
+                           stream);
 }
 
 extern "C" int ipdm_ald_sense_step_f32(float* x_re, float* x_im, const float* g_re, const float* g_im,
@@ -657,8 +606,8 @@ extern "C" int ipdm_ald_sense_step_f32(float* x_re, float* x_im, const float* g_
                                        uint64_t seed, int64_t sample_offset, int64_t step_id,
                                        const ipdm_sched_t* dev_sched, const float* y, const float* sens, const uint8_t* mask,
                                        int mask_t, float coef, float* work, int B, int n_coils, int H, int W, void* stream) {
-  return ald_sense_step_impl(x_re, x_im, g_re, g_im, noise_re, noise_im, step, noise_scale, seed, sample_offset, step_id,
-                             dev_sched, y, sens, mask, mask_t, coef, work, B, n_coils, H, W, stream);
+  return ald_sense_step_impl(x_re, x_im, {g_re, g_im, noise_re, noise_im, step, noise_scale, seed, sample_offset, step_id, dev_sched},
+                             sense_problem<float>(y, sens, mask, mask_t, B, n_coils, H, W), coef, work, stream);
 }
 
 extern "C" int ipdm_ald_sense_step_csm_f32(float* x_re, float* x_im, const float* g_re, const float* g_im,
@@ -667,36 +616,42 @@ extern "C" int ipdm_ald_sense_step_csm_f32(float* x_re, float* x_im, const float
                                            const ipdm_sched_t* dev_sched, const float* y, const float* sens,
                                            const uint8_t* mask, int mask_t, float coef, float* work, int B, int n_coils, int H,
                                            int W, void* stream) {
-  return ald_sense_step_impl(x_re, x_im, g_re, g_im, noise_re, noise_im, step, noise_scale, seed, sample_offset, step_id,
-                             dev_sched, y, reinterpret_cast<const float2*>(sens), mask, mask_t, coef, work, B, n_coils, H, W,
-                             stream);
+  return ald_sense_step_impl(x_re, x_im, {g_re, g_im, noise_re, noise_im, step, noise_scale, seed, sample_offset, step_id, dev_sched},
+                             sense_problem<float2>(y, sens, mask, mask_t, B, n_coils, H, W), coef, work, stream);
+}
+
+// x_re / x_im hold z (Langevin pending when lg.g_re) and receive the single-coil operator's result
+static int singlecoil_step(float* x_re, float* x_im, const LangevinArgs& lg, const SenseProblem<float>& pb, float coef, int mode,
+                           float* workspace, hipStream_t st) {
+  if (ipdm_kspace_large::large_ok(pb.H, pb.W)) {
+    IPDM_REQUIRE(workspace);
+    return ipdm_kspace_large::prox_step(x_re, x_im, lg, pb, coef, mode, reinterpret_cast<float2*>(workspace), st);
+  }
+  if (!lds_fft_ok(pb.H, pb.W)) return IPDM_EUNSUPPORTED;
+  const size_t lds = lds_bytes(pb.H, pb.W);
+  if (lg.g_re) {
+    int rc = set_lds_limit(ald_singlecoil_step_kernel<true>, lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL(ald_singlecoil_step_kernel<true>, dim3(pb.B), dim3(FFT_THREADS), lds, st, x_re, x_im, lg, pb, coef, mode);
+  } else {
+    int rc = set_lds_limit(ald_singlecoil_step_kernel<false>, lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL(ald_singlecoil_step_kernel<false>, dim3(pb.B), dim3(FFT_THREADS), lds, st, x_re, x_im, lg, pb, coef, mode);
+  }
+  return ipdm_launch_status();
 }
 
 extern "C" int ipdm_singlecoil_prox_f32(const float* z_re, const float* z_im, const float* y, const uint8_t* mask,
                                         int mask_t, float coef, int mode, float* out_re, float* out_im, float* workspace,
                                         int B, int H, int W, void* stream) {
-  IPDM_REQUIRE(B >= 0 && H > 0 && W > 0 && mask_t_ok(mask_t) && mode >= 0 && mode <= 2);
+  const SenseProblem<float> pb = sense_problem<float>(y, nullptr, mask, mask_t, B, 1, H, W);
+  IPDM_REQUIRE(dims_ok(pb) && mode >= 0 && mode <= 2);
   if (B == 0) return IPDM_OK;
   IPDM_REQUIRE(z_re && z_im && y && mask && out_re && out_im);
-  const bool large = ipdm_kspace_large::large_ok(H, W);
-  if (!large && !lds_fft_ok(H, W)) return IPDM_EUNSUPPORTED;
+  if (!ipdm_kspace_large::large_ok(H, W) && !lds_fft_ok(H, W)) return IPDM_EUNSUPPORTED;
   hipStream_t st = ipdm_stream(stream);
-  const size_t bytes = (size_t)B * H * W * sizeof(float);
-  if (out_re != z_re && hipMemcpyAsync(out_re, z_re, bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) return (int)hipGetLastError();
-  if (out_im != z_im && hipMemcpyAsync(out_im, z_im, bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) return (int)hipGetLastError();
-  if (large) {
-    IPDM_REQUIRE(workspace);
-    return ipdm_kspace_large::prox_step<float>(out_re, out_im, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, 0ull, 0, 0, nullptr,
-                                        reinterpret_cast<const float2*>(y), nullptr, mask, mask_t, coef, mode,
-                                        reinterpret_cast<float2*>(workspace), B, 1, H, W, st);
-  }
-  size_t lds = lds_bytes(H, W);
-  int rc = set_lds_limit(ald_singlecoil_step_kernel<false>, lds);
-  if (rc) return rc;
-  hipLaunchKernelGGL(ald_singlecoil_step_kernel<false>, dim3(B), dim3(FFT_THREADS), lds, st, out_re, out_im, nullptr,
-                     nullptr, nullptr, nullptr, 0.f, 0.f, 0ull, 0ll, 0ll, nullptr, reinterpret_cast<const float2*>(y), mask,
-                     mask_t, coef, mode, B, H, W);
-  return ipdm_launch_status();
+  const int rc = copy_planes(out_re, out_im, z_re, z_im, (size_t)B * H * W, st);
+  return rc ? rc : singlecoil_step(out_re, out_im, NO_LANGEVIN, pb, coef, mode, workspace, st);
 }
 
 extern "C" int ipdm_ald_singlecoil_step_f32(float* x_re, float* x_im, const float* g_re, const float* g_im,
@@ -704,22 +659,10 @@ extern "C" int ipdm_ald_singlecoil_step_f32(float* x_re, float* x_im, const floa
                                             uint64_t seed, int64_t sample_offset, int64_t step_id,
                                             const ipdm_sched_t* dev_sched, const float* y, const uint8_t* mask, int mask_t,
                                             float coef, int mode, float* workspace, int B, int H, int W, void* stream) {
-  IPDM_REQUIRE(B >= 0 && H > 0 && W > 0 && mask_t_ok(mask_t) && mode >= 0 && mode <= 2);
+  const LangevinArgs lg{g_re, g_im, noise_re, noise_im, step, noise_scale, seed, sample_offset, step_id, dev_sched};
+  const SenseProblem<float> pb = sense_problem<float>(y, nullptr, mask, mask_t, B, 1, H, W);
+  IPDM_REQUIRE(dims_ok(pb) && mode >= 0 && mode <= 2);
   if (B == 0) return IPDM_OK;
-  IPDM_REQUIRE(x_re && x_im && g_re && g_im && y && mask);
-  IPDM_REQUIRE((noise_re == nullptr) == (noise_im == nullptr));
-  if (ipdm_kspace_large::large_ok(H, W)) {
-    IPDM_REQUIRE(workspace);
-    return ipdm_kspace_large::prox_step<float>(x_re, x_im, g_re, g_im, noise_re, noise_im, step, noise_scale, seed, sample_offset,
-                                        step_id, dev_sched, reinterpret_cast<const float2*>(y), nullptr, mask, mask_t, coef,
-                                        mode, reinterpret_cast<float2*>(workspace), B, 1, H, W, ipdm_stream(stream));
-  }
-  if (!lds_fft_ok(H, W)) return IPDM_EUNSUPPORTED;
-  size_t lds = lds_bytes(H, W);
-  int rc = set_lds_limit(ald_singlecoil_step_kernel<true>, lds);
-  if (rc) return rc;
-  hipLaunchKernelGGL(ald_singlecoil_step_kernel<true>, dim3(B), dim3(FFT_THREADS), lds, ipdm_stream(stream), x_re, x_im,
-                     g_re, g_im, noise_re, noise_im, step, noise_scale, seed, (long long)sample_offset,
-                     (long long)step_id, dev_sched, reinterpret_cast<const float2*>(y), mask, mask_t, coef, mode, B, H, W);
-  return ipdm_launch_status();
+  IPDM_REQUIRE(step_ptrs_ok(x_re, x_im, lg, pb));
+  return singlecoil_step(x_re, x_im, lg, pb, coef, mode, workspace, ipdm_stream(stream));
 }

@@ -22,13 +22,6 @@ namespace {
 
 using namespace ipdm_kspace;
 
-struct CgState {
-  float rr;        // <r, r>
-  float bb;        // |b|^2, b = z + a A^H y
-  int iters;       // CG iterations done
-  int frozen;      // 1: x is final
-};
-
 struct CgWork {    // the caller's workspace, carved up (float2 units; ipdm_sense_cg_workspace_bytes)
   float2 *planes, *nout, *r, *p, *ahy;
   CgState* state;
@@ -57,98 +50,15 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
   return s;
 }
 
-// (((w_0 + w_1) + w_2) + ...) over the planes of one sample at element e, fixed order
-__device__ __forceinline__ float2 plane_sum(const float2* __restrict__ pl, int n_planes, int HW, int e) {
-  float2 a = pl[e];
-  for (int c = 1; c < n_planes; ++c) {
-    const float2 w = pl[(size_t)c * HW + e];
-    a = make_float2(a.x + w.x, a.y + w.y);
-  }
-  return a;
-}
-
-// Normal operator, workgroup (coil, b): planes[b][coil] = conj(S_c) F^-1 M (F S_c v - y_c)
-//   MODE 0: v = p[b], y = 0, skipped for a frozen sample;  MODE 1: v = z = x;  MODE 2: v = z = x + step*g + noise_scale*n
-template <int MODE, typename SensT>
-__global__ __launch_bounds__(FFT_THREADS) void cg_normal_coil_kernel(
-    const float* x_re, const float* x_im, const float* __restrict__ g_re, const float* __restrict__ g_im,
-    const float* __restrict__ n_re, const float* __restrict__ n_im, float step, float noise_scale, uint64_t seed,
-    int64_t sample_offset, int64_t step_id, const ipdm_sched_t* __restrict__ sched, float a, const float2* __restrict__ p,
-    const float2* __restrict__ y, const SensT* __restrict__ sens, const uint8_t* __restrict__ mask, int mask_t,
-    const CgState* __restrict__ state, float2* planes, int B, int n_coils, int H, int W) {
-  const int coil = blockIdx.x, b = blockIdx.y;
-  if (sched) {
-    step = sched->step;
-    noise_scale = sched->noise_scale;
-    a = sched->coef;
-    step_id = sched->step_id;
-  }
-  if constexpr (MODE == 0) {
-    if (state[b].frozen) return;
-  } else {
-    if (a == 0.f) return;                                      // the init pass then leaves x = z and freezes the sample
-  }
-  FFT_LDS_SETUP(H, W)
-  const int HW = H * W;
-  const float scale = rsqrtf((float)HW);
-  const SensT* sm = sens + (size_t)coil * HW;
-  for (int e = threadIdx.x; e < HW; e += FFT_THREADS) {
-    float2 v;
-    if constexpr (MODE == 0) {
-      v = p[(size_t)b * HW + e];
-    } else {
-      const float* xr = x_re + (size_t)b * HW;
-      const float* xi = x_im + (size_t)b * HW;
-      v = make_float2(xr[e], xi[e]);
-      if constexpr (MODE == 2)
-        langevin_value(xr, xi, g_re, g_im, n_re, n_im, step, noise_scale, seed, sample_offset, step_id, b, HW, e, v.x, v.y);
-    }
-    const int r = e / W, c = e - r * W;
-    L.buf[e] = sens_mul(v, sign_rc(r, c), sm[e]);
-  }
-  __syncthreads();
-  fft2_lds(L, H, W, false);
-  // masked k-space value, re-modulated for the inverse transform: sign*(sign*scale*v - y) = scale*v - sign*y
-  const float2* yc = MODE == 0 ? nullptr : y + ((size_t)coil * B + b) * HW;
-  for (int e = threadIdx.x; e < HW; e += FFT_THREADS) {
-    const int r = e / W, c = e - r * W;
-    const float2 v = L.buf[e];
-    float2 res = make_float2(0.f, 0.f);
-    if (mask_at(mask, mask_t, b, H, W, r, c)) {
-      res = make_float2(v.x * scale, v.y * scale);
-      if constexpr (MODE != 0) {
-        const float sg = sign_rc(r, c);
-        const float2 yy = yc[e];
-        res = make_float2(res.x - sg * yy.x, res.y - sg * yy.y);
-      }
-    }
-    L.buf[e] = res;
-  }
-  __syncthreads();
-  fft2_lds(L, H, W, true);
-  float2* wk = planes + ((size_t)b * n_coils + coil) * HW;
-  for (int e = threadIdx.x; e < HW; e += FFT_THREADS) {
-    const int r = e / W, c = e - r * W;
-    wk[e] = sens_mul_conj(L.buf[e], sign_rc(r, c) * scale, sm[e]);
-  }
-}
-
 // Init, one workgroup per sample: x = z (Langevin update applied here when LANGEVIN), r = p = -a * sum_c planes,
 // <r,r>, |b|^2 = |z + a A^H y|^2, state.  a == 0: x = z exactly, frozen at 0 iterations.
 template <bool LANGEVIN>
-__global__ __launch_bounds__(FFT_THREADS) void cg_init_kernel(
-    float* x_re, float* x_im, const float* __restrict__ g_re, const float* __restrict__ g_im,
-    const float* __restrict__ n_re, const float* __restrict__ n_im, float step, float noise_scale, uint64_t seed,
-    int64_t sample_offset, int64_t step_id, const ipdm_sched_t* __restrict__ sched, float a, float tol,
-    const float2* __restrict__ planes, int n_planes, const float2* __restrict__ ahy, float2* r, float2* p, CgState* state,
-    int32_t* iters_out, int HW) {
+__global__ __launch_bounds__(FFT_THREADS) void cg_init_kernel(float* x_re, float* x_im, LangevinArgs lg, float a, float tol,
+                                                              const float2* __restrict__ planes, int n_planes,
+                                                              const float2* __restrict__ ahy, float2* r, float2* p,
+                                                              CgState* state, int32_t* iters_out, int HW) {
   __shared__ float red[2][FFT_THREADS / 64];
-  if (sched) {
-    step = sched->step;
-    noise_scale = sched->noise_scale;
-    a = sched->coef;
-    step_id = sched->step_id;
-  }
+  a = sched_override(lg, a);
   const int b = blockIdx.x;
   float* xr = x_re + (size_t)b * HW;
   float* xi = x_im + (size_t)b * HW;
@@ -160,7 +70,7 @@ __global__ __launch_bounds__(FFT_THREADS) void cg_init_kernel(
   for (int e = threadIdx.x; e < HW; e += FFT_THREADS) {
     float zr = xr[e], zi = xi[e];
     if constexpr (LANGEVIN) {
-      langevin_value(xr, xi, g_re, g_im, n_re, n_im, step, noise_scale, seed, sample_offset, step_id, b, HW, e, zr, zi);
+      langevin_value(xr, xi, lg, b, HW, e, zr, zi);
       xr[e] = zr;
       xi[e] = zi;
     }
@@ -200,7 +110,7 @@ __global__ __launch_bounds__(FFT_THREADS) void cg_update_kernel(float* x_re, flo
   const int b = blockIdx.x;
   const CgState s = state[b];
   if (s.frozen) return;                                        // uniform over the workgroup
-  if (sched) a = sched->coef;
+  a = sched_coef(sched, a);
   float* xr = x_re + (size_t)b * HW;
   float* xi = x_im + (size_t)b * HW;
   const float2* pl = planes + (size_t)b * n_planes * HW;
@@ -276,85 +186,56 @@ __global__ __launch_bounds__(FFT_THREADS) void cg_update_kernel(float* x_re, flo
   }
 }
 
-struct Langevin {  // the fused tail's first phase; g_re NULL: none (the plain proximal)
-  const float *g_re, *g_im, *n_re, *n_im;
-  float step, noise_scale;
-  uint64_t seed;
-  int64_t sample_offset, step_id;
-  const ipdm_sched_t* sched;
-};
-
-template <int MODE, typename SensT>
-static int launch_normal_coils(float* x_re, float* x_im, const Langevin& lg, float a, const float2* p, const float2* y,
-                               const SensT* sens, const uint8_t* mask, int mask_t, const CgWork& w, int B, int n_coils, int H,
-                               int W, hipStream_t st) {
-  const size_t lds = lds_bytes(H, W);
-  const int rc = set_lds_limit(cg_normal_coil_kernel<MODE, SensT>, lds);
-  if (rc) return rc;
-  hipLaunchKernelGGL((cg_normal_coil_kernel<MODE, SensT>), dim3(n_coils, B), dim3(FFT_THREADS), lds, st, x_re, x_im, lg.g_re,
-                     lg.g_im, lg.n_re, lg.n_im, lg.step, lg.noise_scale, lg.seed, (long long)lg.sample_offset,
-                     (long long)lg.step_id, lg.sched, a, p, y, sens, mask, mask_t, w.state, w.planes, B, n_coils, H, W);
-  return ipdm_launch_status();
-}
-
 // x_re / x_im hold x (Langevin pending when lg.g_re) and receive the solution
 template <typename SensT>
-static int cg_solve(float* x_re, float* x_im, const Langevin& lg, float a, const float2* y, const SensT* sens,
-                    const uint8_t* mask, int mask_t, const float2* ahy, int max_iter, float tol, float* work,
-                    int32_t* iters_out, int B, int n_coils, int H, int W, hipStream_t st) {
+static int cg_solve(float* x_re, float* x_im, const LangevinArgs& lg, const SenseProblem<SensT>& pb, float a, const float2* ahy,
+                    int max_iter, float tol, float* work, int32_t* iters_out, hipStream_t st) {
+  const int B = pb.B, H = pb.H, W = pb.W;
   const bool large = ipdm_kspace_large::large_ok(H, W);
   if (!large && !lds_fft_ok(H, W)) return IPDM_EUNSUPPORTED;
   if (B > 65535) return IPDM_EUNSUPPORTED;
-  const CgWork w = carve(work, B, n_coils, H, W);
+  const CgWork w = carve(work, B, pb.n_coils, H, W);
   const int HW = H * W;
   const bool lang = lg.g_re != nullptr;
   int rc;
   if (!ahy) {                                                  // A^H y = SENSE adjoint of the masked measurement
-    if constexpr (sizeof(SensT) == sizeof(float2))
-      rc = ipdm_sense_adjoint_csm_c64(reinterpret_cast<const float*>(y), reinterpret_cast<const float*>(sens), mask, mask_t, 1,
-                                      reinterpret_cast<float*>(w.ahy), reinterpret_cast<float*>(w.planes), B, n_coils, H, W, st);
-    else
-      rc = ipdm_sense_adjoint_c64(reinterpret_cast<const float*>(y), reinterpret_cast<const float*>(sens), mask, mask_t, 1,
-                                  reinterpret_cast<float*>(w.ahy), reinterpret_cast<float*>(w.planes), B, n_coils, H, W, st);
+    rc = (sizeof(SensT) == sizeof(float2) ? ipdm_sense_adjoint_csm_c64 : ipdm_sense_adjoint_c64)(
+        reinterpret_cast<const float*>(pb.y), reinterpret_cast<const float*>(pb.sens), pb.mask, pb.mask_t, 1,
+        reinterpret_cast<float*>(w.ahy), reinterpret_cast<float*>(w.planes), B, pb.n_coils, H, W, st);
     if (rc) return rc;
     ahy = w.ahy;
   }
+  SenseProblem<SensT> no_y = pb;                               // the iterations apply A^H A alone
+  no_y.y = nullptr;
   const float2* planes = large ? w.nout : w.planes;
-  const int n_planes = large ? 1 : n_coils;
+  const int n_planes = large ? 1 : pb.n_coils;
   if (large) {
     if (lang) {
-      rc = ipdm_kspace_large::langevin(x_re, x_im, lg.g_re, lg.g_im, lg.n_re, lg.n_im, lg.step, lg.noise_scale, lg.seed,
-                                       lg.sample_offset, lg.step_id, lg.sched, B, H, W, st);
+      rc = ipdm_kspace_large::langevin(x_re, x_im, lg, B, H, W, st);
       if (rc) return rc;
     }
-    rc = ipdm_kspace_large::normal_op<SensT>(nullptr, x_re, x_im, y, sens, mask, mask_t, w.nout, w.planes, B, n_coils, H, W, st);
-    if (rc) return rc;
-    hipLaunchKernelGGL(cg_init_kernel<false>, dim3(B), dim3(FFT_THREADS), 0, st, x_re, x_im, nullptr, nullptr, nullptr, nullptr,
-                       0.f, 0.f, 0ull, 0ll, 0ll, lg.sched, a, tol, planes, n_planes, ahy, w.r, w.p, w.state, iters_out, HW);
-  } else if (lang) {
-    rc = launch_normal_coils<2>(x_re, x_im, lg, a, nullptr, y, sens, mask, mask_t, w, B, n_coils, H, W, st);
-    if (rc) return rc;
-    hipLaunchKernelGGL(cg_init_kernel<true>, dim3(B), dim3(FFT_THREADS), 0, st, x_re, x_im, lg.g_re, lg.g_im, lg.n_re, lg.n_im,
-                       lg.step, lg.noise_scale, lg.seed, (long long)lg.sample_offset, (long long)lg.step_id, lg.sched, a, tol,
-                       planes, n_planes, ahy, w.r, w.p, w.state, iters_out, HW);
+    rc = ipdm_kspace_large::normal_op(nullptr, x_re, x_im, pb, w.nout, w.planes, st);
   } else {
-    rc = launch_normal_coils<1>(x_re, x_im, lg, a, nullptr, y, sens, mask, mask_t, w, B, n_coils, H, W, st);
-    if (rc) return rc;
-    hipLaunchKernelGGL(cg_init_kernel<false>, dim3(B), dim3(FFT_THREADS), 0, st, x_re, x_im, nullptr, nullptr, nullptr, nullptr,
-                       0.f, 0.f, 0ull, 0ll, 0ll, lg.sched, a, tol, planes, n_planes, ahy, w.r, w.p, w.state, iters_out, HW);
+    rc = launch_normal_coils(lang ? 2 : 1, x_re, x_im, lg, a, nullptr, nullptr, pb, w.planes, st);
   }
+  if (rc) return rc;
+  if (lang && !large)
+    hipLaunchKernelGGL(cg_init_kernel<true>, dim3(B), dim3(FFT_THREADS), 0, st, x_re, x_im, lg, a, tol, planes, n_planes, ahy, w.r,
+                       w.p, w.state, iters_out, HW);
+  else                                                         // no update, or (strips) already applied: only lg.sched is read
+    hipLaunchKernelGGL(cg_init_kernel<false>, dim3(B), dim3(FFT_THREADS), 0, st, x_re, x_im, lg, a, tol, planes, n_planes, ahy,
+                       w.r, w.p, w.state, iters_out, HW);
   rc = ipdm_launch_status();
   if (rc) return rc;
   for (int it = 0; it < max_iter; ++it) {
     if (large) {
       // (the strip passes have no per-sample exit: a frozen sample's planes are computed and ignored)
-      rc = ipdm_kspace_large::normal_op<SensT>(w.p, nullptr, nullptr, nullptr, sens, mask, mask_t, w.nout, w.planes, B, n_coils,
-                                               H, W, st);
+      rc = ipdm_kspace_large::normal_op(w.p, nullptr, nullptr, no_y, w.nout, w.planes, st);
       if (rc) return rc;
       hipLaunchKernelGGL(cg_update_kernel<false>, dim3(B), dim3(FFT_THREADS), 0, st, x_re, x_im, lg.sched, a, tol, planes,
                          n_planes, w.r, w.p, w.state, iters_out, HW);
     } else {
-      rc = launch_normal_coils<0>(x_re, x_im, lg, a, w.p, nullptr, sens, mask, mask_t, w, B, n_coils, H, W, st);
+      rc = launch_normal_coils(0, x_re, x_im, lg, a, w.p, w.state, no_y, w.planes, st);
       if (rc) return rc;
       hipLaunchKernelGGL(cg_update_kernel<true>, dim3(B), dim3(FFT_THREADS), 0, st, x_re, x_im, lg.sched, a, tol, planes,
                          n_planes, w.r, w.p, w.state, iters_out, HW);
@@ -365,37 +246,30 @@ static int cg_solve(float* x_re, float* x_im, const Langevin& lg, float a, const
   return IPDM_OK;
 }
 
+static inline bool cg_scalars_ok(int max_iter, float tol) { return max_iter >= 1 && tol >= 0.f && tol < INFINITY; }
+
 template <typename SensT>
-static int cgprox_impl(const float* z_re, const float* z_im, const float* y, const SensT* sens, const uint8_t* mask, int mask_t,
-                       float a, const float* ahy, int max_iter, float tol, float* out_re, float* out_im, float* work,
-                       int32_t* iters_out, int B, int n_coils, int H, int W, void* stream) {
-  IPDM_REQUIRE(B >= 0 && n_coils > 0 && H > 0 && W > 0 && mask_t_ok(mask_t) && max_iter >= 1 && tol >= 0.f && tol < INFINITY);
-  if (B == 0) return IPDM_OK;
-  if (!ipdm_kspace_large::large_ok(H, W) && !lds_fft_ok(H, W)) return IPDM_EUNSUPPORTED;
-  IPDM_REQUIRE(z_re && z_im && y && sens && mask && out_re && out_im && work);
+static int cgprox_impl(const float* z_re, const float* z_im, const SenseProblem<SensT>& pb, float a, const float* ahy, int max_iter,
+                       float tol, float* out_re, float* out_im, float* work, int32_t* iters_out, void* stream) {
+  IPDM_REQUIRE(dims_ok(pb) && cg_scalars_ok(max_iter, tol));
+  if (pb.B == 0) return IPDM_OK;
+  if (!ipdm_kspace_large::large_ok(pb.H, pb.W) && !lds_fft_ok(pb.H, pb.W)) return IPDM_EUNSUPPORTED;
+  IPDM_REQUIRE(z_re && z_im && pb.y && pb.sens && pb.mask && out_re && out_im && work);
   hipStream_t st = ipdm_stream(stream);
-  const size_t bytes = (size_t)B * H * W * sizeof(float);
-  if (out_re != z_re && hipMemcpyAsync(out_re, z_re, bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) return (int)hipGetLastError();
-  if (out_im != z_im && hipMemcpyAsync(out_im, z_im, bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) return (int)hipGetLastError();
-  const Langevin none{nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, 0ull, 0, 0, nullptr};
-  return cg_solve(out_re, out_im, none, a, reinterpret_cast<const float2*>(y), sens, mask, mask_t,
-                  reinterpret_cast<const float2*>(ahy), max_iter, tol, work, iters_out, B, n_coils, H, W, st);
+  const int rc = copy_planes(out_re, out_im, z_re, z_im, (size_t)pb.B * pb.H * pb.W, st);
+  return rc ? rc : cg_solve(out_re, out_im, NO_LANGEVIN, pb, a, reinterpret_cast<const float2*>(ahy), max_iter, tol, work,
+                            iters_out, st);
 }
 
 template <typename SensT>
-static int cg_step_impl(float* x_re, float* x_im, const float* g_re, const float* g_im, const float* noise_re,
-                        const float* noise_im, float step, float noise_scale, uint64_t seed, int64_t sample_offset,
-                        int64_t step_id, const ipdm_sched_t* dev_sched, const float* y, const SensT* sens, const uint8_t* mask,
-                        int mask_t, float coef, float* work, const float* ahy, int max_iter, float tol, int32_t* iters_out, int B,
-                        int n_coils, int H, int W, void* stream) {
-  IPDM_REQUIRE(B >= 0 && n_coils > 0 && H > 0 && W > 0 && mask_t_ok(mask_t) && max_iter >= 1 && tol >= 0.f && tol < INFINITY);
-  if (B == 0) return IPDM_OK;
-  if (!ipdm_kspace_large::large_ok(H, W) && !lds_fft_ok(H, W)) return IPDM_EUNSUPPORTED;
-  IPDM_REQUIRE(x_re && x_im && g_re && g_im && y && sens && mask && work);
-  IPDM_REQUIRE((noise_re == nullptr) == (noise_im == nullptr));
-  const Langevin lg{g_re, g_im, noise_re, noise_im, step, noise_scale, seed, sample_offset, step_id, dev_sched};
-  return cg_solve(x_re, x_im, lg, coef, reinterpret_cast<const float2*>(y), sens, mask, mask_t,
-                  reinterpret_cast<const float2*>(ahy), max_iter, tol, work, iters_out, B, n_coils, H, W, ipdm_stream(stream));
+static int cg_step_impl(float* x_re, float* x_im, const LangevinArgs& lg, const SenseProblem<SensT>& pb, float coef, float* work,
+                        const float* ahy, int max_iter, float tol, int32_t* iters_out, void* stream) {
+  IPDM_REQUIRE(dims_ok(pb) && cg_scalars_ok(max_iter, tol));
+  if (pb.B == 0) return IPDM_OK;
+  if (!ipdm_kspace_large::large_ok(pb.H, pb.W) && !lds_fft_ok(pb.H, pb.W)) return IPDM_EUNSUPPORTED;
+  IPDM_REQUIRE(step_ptrs_ok(x_re, x_im, lg, pb) && pb.sens && work);
+  return cg_solve(x_re, x_im, lg, pb, coef, reinterpret_cast<const float2*>(ahy), max_iter, tol, work, iters_out,
+                  ipdm_stream(stream));
 }
 
 }  // namespace
@@ -410,16 +284,16 @@ extern "C" int ipdm_sense_cgprox_f32(const float* z_re, const float* z_im, const
                                      const uint8_t* mask, int mask_t, float a, const float* ahy, int max_iter, float tol,
                                      float* out_re, float* out_im, float* work, int32_t* iters_out, int B, int n_coils, int H,
                                      int W, void* stream) {
-  return cgprox_impl(z_re, z_im, y, sens, mask, mask_t, a, ahy, max_iter, tol, out_re, out_im, work, iters_out, B, n_coils, H, W,
-                     stream);
+  return cgprox_impl(z_re, z_im, sense_problem<float>(y, sens, mask, mask_t, B, n_coils, H, W), a, ahy, max_iter, tol, out_re,
+                     out_im, work, iters_out, stream);
 }
 
 extern "C" int ipdm_sense_cgprox_csm_f32(const float* z_re, const float* z_im, const float* y, const float* sens,
                                          const uint8_t* mask, int mask_t, float a, const float* ahy, int max_iter, float tol,
                                          float* out_re, float* out_im, float* work, int32_t* iters_out, int B, int n_coils,
                                          int H, int W, void* stream) {
-  return cgprox_impl(z_re, z_im, y, reinterpret_cast<const float2*>(sens), mask, mask_t, a, ahy, max_iter, tol, out_re, out_im,
-                     work, iters_out, B, n_coils, H, W, stream);
+  return cgprox_impl(z_re, z_im, sense_problem<float2>(y, sens, mask, mask_t, B, n_coils, H, W), a, ahy, max_iter, tol, out_re,
+                     out_im, work, iters_out, stream);
 }
 
 extern "C" int ipdm_ald_sense_cg_step_f32(float* x_re, float* x_im, const float* g_re, const float* g_im,
@@ -428,8 +302,9 @@ extern "C" int ipdm_ald_sense_cg_step_f32(float* x_re, float* x_im, const float*
                                           const float* y, const float* sens, const uint8_t* mask, int mask_t, float coef,
                                           float* work, const float* ahy, int max_iter, float tol, int32_t* iters_out, int B,
                                           int n_coils, int H, int W, void* stream) {
-  return cg_step_impl(x_re, x_im, g_re, g_im, noise_re, noise_im, step, noise_scale, seed, sample_offset, step_id, dev_sched, y,
-                      sens, mask, mask_t, coef, work, ahy, max_iter, tol, iters_out, B, n_coils, H, W, stream);
+  return cg_step_impl(x_re, x_im, {g_re, g_im, noise_re, noise_im, step, noise_scale, seed, sample_offset, step_id, dev_sched},
+                      sense_problem<float>(y, sens, mask, mask_t, B, n_coils, H, W), coef, work, ahy, max_iter, tol, iters_out,
+                      stream);
 }
 
 extern "C" int ipdm_ald_sense_cg_step_csm_f32(float* x_re, float* x_im, const float* g_re, const float* g_im,
@@ -439,7 +314,7 @@ extern "C" int ipdm_ald_sense_cg_step_csm_f32(float* x_re, float* x_im, const fl
                                               const uint8_t* mask, int mask_t, float coef, float* work, const float* ahy,
                                               int max_iter, float tol, int32_t* iters_out, int B, int n_coils, int H, int W,
                                               void* stream) {
-  return cg_step_impl(x_re, x_im, g_re, g_im, noise_re, noise_im, step, noise_scale, seed, sample_offset, step_id, dev_sched, y,
-                      reinterpret_cast<const float2*>(sens), mask, mask_t, coef, work, ahy, max_iter, tol, iters_out, B, n_coils,
-                      H, W, stream);
+  return cg_step_impl(x_re, x_im, {g_re, g_im, noise_re, noise_im, step, noise_scale, seed, sample_offset, step_id, dev_sched},
+                      sense_problem<float2>(y, sens, mask, mask_t, B, n_coils, H, W), coef, work, ahy, max_iter, tol, iters_out,
+                      stream);
 }

@@ -160,13 +160,62 @@ __device__ __forceinline__ bool mask_at(const uint8_t* mask, int mask_t, int b, 
   L.twN = (H) > (W) ? (H) : (W);                             \
   fft_make_twiddles(L);
 
-// z = x + step*g + noise_scale*n at element e of sample b, in registers (the coil-parallel iteration tails: every
-// workgroup of a sample forms the same z); n injected (n_re/n_im) or Philox keyed by (seed, global sample id, step, plane)
-__device__ __forceinline__ void langevin_value(const float* xr, const float* xi, const float* __restrict__ g_re,
-                                               const float* __restrict__ g_im, const float* __restrict__ n_re,
-                                               const float* __restrict__ n_im, float step, float noise_scale, uint64_t seed,
-                                               int64_t sample_offset, int64_t step_id, int b, int HW, int e, float& zr,
-                                               float& zi) {
+// ---- argument bundles, passed to kernels by value (like ConvArgs and the strip functors) ----------------------------------
+// The fused tails' first phase.  g_re NULL: no Langevin phase (the plain proximals); n_re NULL: Philox noise.
+struct LangevinArgs {
+  const float *g_re, *g_im, *n_re, *n_im;
+  float step, noise_scale;
+  uint64_t seed;
+  int64_t sample_offset, step_id;
+  const ipdm_sched_t* sched;       // device schedule: overrides step / noise_scale / step_id and the coefficient
+};
+constexpr LangevinArgs NO_LANGEVIN{};
+
+// The measurement model.  SensT: the coil maps' element type, float or float2 (interleaved complex64).
+template <typename SensT>
+struct SenseProblem {
+  const float2* y;                 // k-space data [n_coils][B][H][W]
+  const SensT* sens;               // [n_coils][H][W]
+  const uint8_t* mask;             // mask_at()
+  int mask_t, B, n_coils, H, W;
+};
+template <typename SensT>
+static inline SenseProblem<SensT> sense_problem(const float* y, const float* sens, const uint8_t* mask, int mask_t, int B,
+                                                int n_coils, int H, int W) {
+  return {reinterpret_cast<const float2*>(y), reinterpret_cast<const SensT*>(sens), mask, mask_t, B, n_coils, H, W};
+}
+
+// The device schedule, the only place it is read: the coefficient alone, or with the Langevin scalars as well.
+__device__ __forceinline__ float sched_coef(const ipdm_sched_t* __restrict__ sched, float coef) {
+  return sched ? sched->coef : coef;
+}
+__device__ __forceinline__ float sched_override(LangevinArgs& lg, float coef) {
+  const ipdm_sched_t* __restrict__ sched = lg.sched;
+  if (sched) {
+    lg.step = sched->step;
+    lg.noise_scale = sched->noise_scale;
+    lg.step_id = sched->step_id;
+  }
+  return sched_coef(sched, coef);
+}
+
+// ---- the Langevin update, the only place it is written ---------------------------------------------------------------------
+// Philox normals of quad q (elements 4q .. 4q+3) of sample b, keyed by (seed, global sample id, step, plane); plane 0 is
+// the real part, plane 1 the imaginary part
+__device__ __forceinline__ void langevin_quad(const LangevinArgs& lg, int b, int plane, uint32_t q, float (&n)[4]) {
+  ipdm_philox_normal4(lg.seed, lg.sample_offset + b, lg.step_id, plane, q, n);
+}
+__device__ __forceinline__ float langevin_update(const LangevinArgs& lg, float x, float g, float n) {
+  return x + lg.step * g + n * lg.noise_scale;
+}
+// z at element e of sample b, in registers: noise injected (n_re / n_im) or Philox.  Every workgroup of a sample forms the
+// same z, which is what lets the coil-parallel tails recompute it instead of exchanging it.
+__device__ __forceinline__ void langevin_value(const float* xr, const float* xi, const LangevinArgs& lg, int b, int HW, int e,
+                                               float& zr, float& zi) {
+  const float* __restrict__ g_re = lg.g_re;
+  const float* __restrict__ g_im = lg.g_im;
+  const float* __restrict__ n_re = lg.n_re;
+  const float* __restrict__ n_im = lg.n_im;
   const size_t gi = (size_t)b * HW + e;
   float nr, ni;
   if (n_re) {
@@ -174,14 +223,69 @@ __device__ __forceinline__ void langevin_value(const float* xr, const float* xi,
     ni = n_im[gi];
   } else {
     float q[4];
-    const int lane4 = e & 3;
-    ipdm_philox_normal4(seed, sample_offset + b, step_id, 0, (uint32_t)(e >> 2), q);
+    langevin_quad(lg, b, 0, (uint32_t)(e >> 2), q);
+    const int lane4 = e & 3;                                   // (selects written out: as a function they cost the packed math)
     nr = lane4 == 0 ? q[0] : lane4 == 1 ? q[1] : lane4 == 2 ? q[2] : q[3];
-    ipdm_philox_normal4(seed, sample_offset + b, step_id, 1, (uint32_t)(e >> 2), q);
+    langevin_quad(lg, b, 1, (uint32_t)(e >> 2), q);
     ni = lane4 == 0 ? q[0] : lane4 == 1 ? q[1] : lane4 == 2 ? q[2] : q[3];
   }
-  zr = xr[e] + step * g_re[gi] + nr * noise_scale;
-  zi = xi[e] + step * g_im[gi] + ni * noise_scale;
+  zr = langevin_update(lg, xr[e], g_re[gi], nr);
+  zi = langevin_update(lg, xi[e], g_im[gi], ni);
+}
+
+// masked k-space residual, re-modulated for the inverse transform: sign*(sign*scale*v - y) = scale*v - sign*y on the sampled
+// points, 0 elsewhere.  sv = scale * v.  The pointer form reads y only where sampled; y NULL: y = 0, nothing is subtracted.
+__device__ __forceinline__ float2 masked_residual(bool m, float2 sv, float sg, float2 yy) {
+  return m ? make_float2(sv.x - sg * yy.x, sv.y - sg * yy.y) : make_float2(0.f, 0.f);
+}
+__device__ __forceinline__ float2 masked_residual(bool m, float2 sv, float sg, const float2* __restrict__ y) {
+  if (!m) return make_float2(0.f, 0.f);
+  return y ? masked_residual(true, sv, sg, *y) : sv;
+}
+
+// (((w_0 + w_1) + w_2) + ...) over the planes of one sample at element e, fixed order
+__device__ __forceinline__ float2 plane_sum(const float2* __restrict__ pl, int n_planes, int HW, int e) {
+  float2 a = pl[e];
+  for (int c = 1; c < n_planes; ++c) {
+    const float2 w = pl[(size_t)c * HW + e];
+    a = make_float2(a.x + w.x, a.y + w.y);
+  }
+  return a;
+}
+
+// per-sample state of the conjugate-gradient proximal (kspace_cg.hip)
+struct CgState {
+  float rr;        // <r, r>
+  float bb;        // |b|^2, b = z + a A^H y
+  int iters;       // CG iterations done
+  int frozen;      // 1: x is final
+};
+
+// Coil-parallel normal operator on images held in LDS (kspace.hip), workgroup (coil, b):
+//     planes[b][coil] = conj(S_c) F^-1 M (F S_c v - y_c)
+//   mode 0: v = p[b], y = 0, skipped for a sample with state[b].frozen;  mode 1: v = x;  mode 2: v = x + Langevin update
+// Modes 1 and 2 return at once on a zero coefficient (planes are then not written).  planes overlaps no operand.
+template <typename SensT>
+int launch_normal_coils(int mode, const float* x_re, const float* x_im, const LangevinArgs& lg, float coef, const float2* p,
+                        const CgState* state, const SenseProblem<SensT>& pb, float2* planes, hipStream_t st);
+
+// argument checks shared by the entry points: sizes, then (after the B == 0 exit) the fused tails' pointers
+template <typename SensT>
+static inline bool dims_ok(const SenseProblem<SensT>& pb) {
+  return pb.B >= 0 && pb.n_coils > 0 && pb.H > 0 && pb.W > 0 && mask_t_ok(pb.mask_t);
+}
+template <typename SensT>
+static inline bool step_ptrs_ok(const float* x_re, const float* x_im, const LangevinArgs& lg, const SenseProblem<SensT>& pb) {
+  return x_re && x_im && lg.g_re && lg.g_im && pb.y && pb.mask && (lg.n_re == nullptr) == (lg.n_im == nullptr);
+}
+
+// out-of-place entry points: z -> out, plane by plane, unless the caller passed the same plane
+static inline int copy_planes(float* out_re, float* out_im, const float* z_re, const float* z_im, size_t n, hipStream_t st) {
+  if (out_re != z_re && hipMemcpyAsync(out_re, z_re, n * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
+    return (int)hipGetLastError();
+  if (out_im != z_im && hipMemcpyAsync(out_im, z_im, n * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
+    return (int)hipGetLastError();
+  return IPDM_OK;
 }
 
 // raise a kernel's dynamic-LDS limit above the 64 KiB default
@@ -202,23 +306,20 @@ int64_t workspace_bytes(int B, int n_coils, int H, int W);
 int fft2c(const float2* in, float2* out, int batch, int H, int W, int inverse, hipStream_t s);
 // SensT: float (real maps) or float2 (interleaved complex64 maps); both are instantiated in kspace_large.hip
 template <typename SensT>
-int sense_forward(const float2* x, const SensT* sens, const uint8_t* mask, int mask_t, float2* y, int B, int n_coils,
-                  int H, int W, hipStream_t s);
+int sense_forward(const float2* x, const ipdm_kspace::SenseProblem<SensT>& pb, float2* y, hipStream_t s);
+// adjoint of pb.y (masked first when apply_mask) into x_out, or its root-sum-of-squares into ssos_out
 template <typename SensT>
-int sense_adjoint(const float2* sm, const SensT* sens, const uint8_t* mask, int mask_t, int apply_mask, float2* x_out,
-                  float* ssos_out, float2* ws, int B, int n_coils, int H, int W, hipStream_t s);
+int sense_adjoint(const ipdm_kspace::SenseProblem<SensT>& pb, int apply_mask, float2* x_out, float* ssos_out, float2* ws,
+                  hipStream_t s);
+// Langevin (optional: lg.g_re) + data-consistency operator on planar x, in place.  pb.sens NULL: single coil; mode as ColsProx.
 template <typename SensT>
-int prox_step(float* x_re, float* x_im, const float* g_re, const float* g_im, const float* n_re, const float* n_im,
-              float step, float noise_scale, uint64_t seed, int64_t sample_offset, int64_t step_id,
-              const ipdm_sched_t* sched, const float2* y, const SensT* sens, const uint8_t* mask, int mask_t, float coef,
-              int mode, float2* ws, int B, int n_coils, int H, int W, hipStream_t s);
+int prox_step(float* x_re, float* x_im, const ipdm_kspace::LangevinArgs& lg, const ipdm_kspace::SenseProblem<SensT>& pb,
+              float coef, int mode, float2* ws, hipStream_t s);
 // the conjugate-gradient proximal's pieces (kspace_cg.hip).  langevin: the planar update x += step*g + noise_scale*n alone.
-// normal_op: out[b] = A^H (A v - y) with v complex (xc) or planar (x_re, x_im; xc NULL) and y NULL for A^H A v alone;
+// normal_op: out[b] = A^H (A v - y) with v complex (xc) or planar (x_re, x_im; xc NULL) and pb.y NULL for A^H A v alone;
 // ws holds n_coils*B images and out must not overlap it.
-int langevin(float* x_re, float* x_im, const float* g_re, const float* g_im, const float* n_re, const float* n_im, float step,
-             float noise_scale, uint64_t seed, int64_t sample_offset, int64_t step_id, const ipdm_sched_t* sched, int B, int H,
-             int W, hipStream_t s);
+int langevin(float* x_re, float* x_im, const ipdm_kspace::LangevinArgs& lg, int B, int H, int W, hipStream_t s);
 template <typename SensT>
-int normal_op(const float2* xc, const float* x_re, const float* x_im, const float2* y, const SensT* sens, const uint8_t* mask,
-              int mask_t, float2* out, float2* ws, int B, int n_coils, int H, int W, hipStream_t s);
+int normal_op(const float2* xc, const float* x_re, const float* x_im, const ipdm_kspace::SenseProblem<SensT>& pb, float2* out,
+              float2* ws, hipStream_t s);
 }  // namespace ipdm_kspace_large

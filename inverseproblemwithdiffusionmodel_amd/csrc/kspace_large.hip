@@ -189,8 +189,8 @@ struct ColsProx {
     const bool m = mask_at(mask, mask_t, b, g.H, g.W, r, c);
     const float2 yy = y ? y[g.at(coil, b, r, c)] : make_float2(0.f, 0.f);
     const float sg = sign_rc(r, c);
-    if (mode <= 0) return m ? make_float2(v.x - sg * yy.x, v.y - sg * yy.y) : make_float2(0.f, 0.f);
-    const float coef = sched ? sched->coef : coef_host;
+    if (mode <= 0) return masked_residual(m, v, sg, yy);
+    const float coef = sched_coef(sched, coef_host);
     if (mode == 1) {
       const float inv = m ? 1.f / (1.f + coef) : 1.f;
       return make_float2((v.x + coef * sg * yy.x) * inv, (v.y + coef * sg * yy.y) * inv);
@@ -213,7 +213,7 @@ __global__ __launch_bounds__(FFT_THREADS) void rows_inv_accum_kernel(const float
                                                                      const ipdm_sched_t* __restrict__ sched, float coef,
                                                                      int B, int n_coils, int H, int W) {
   STRIP_LDS_SETUP(W)
-  if (sched) coef = sched->coef;
+  coef = sched_coef(sched, coef);
   const ImgGeo g{B, H, W};
   const int RS = min(H, STRIP_ELEMS / W);
   const int r0 = blockIdx.x * RS, b = blockIdx.y;
@@ -271,18 +271,14 @@ __global__ __launch_bounds__(FFT_THREADS) void rows_inv_accum_kernel(const float
   }
 }
 
-// Langevin update of both planes in place: x += step*g + noise_scale*n (injected noise or Philox keyed exactly as the
-// fused 128x128 kernel keys it: (seed, global sample id, step, plane 0 = real / 1 = imaginary, quad))
-__global__ __launch_bounds__(256) void langevin_planes_kernel(float* x_re, float* x_im, const float* __restrict__ g_re,
-                                                              const float* __restrict__ g_im, const float* __restrict__ n_re,
-                                                              const float* __restrict__ n_im, float step, float noise_scale,
-                                                              uint64_t seed, int64_t sample_offset, int64_t step_id,
-                                                              const ipdm_sched_t* __restrict__ sched, int HW) {
-  if (sched) {
-    step = sched->step;
-    noise_scale = sched->noise_scale;
-    step_id = sched->step_id;
-  }
+// Langevin update of both planes in place, a quad of elements per thread: the update and the Philox keying are
+// langevin_update / langevin_quad of kspace_fft.h, as in the fused 128x128 kernels
+__global__ __launch_bounds__(256) void langevin_planes_kernel(float* x_re, float* x_im, LangevinArgs lg, int HW) {
+  (void)sched_override(lg, 0.f);                               // the Langevin scalars only: no coefficient here
+  const float* __restrict__ g_re = lg.g_re;
+  const float* __restrict__ g_im = lg.g_im;
+  const float* __restrict__ n_re = lg.n_re;
+  const float* __restrict__ n_im = lg.n_im;
   const int b = blockIdx.y;
   const int quads = HW / 4;                                    // HW is a multiple of 4 (power-of-two images)
   // float4 access only where all the caller's planes sit on 16-byte boundaries; otherwise element by element (same
@@ -293,14 +289,14 @@ __global__ __launch_bounds__(256) void langevin_planes_kernel(float* x_re, float
     const size_t gi = (size_t)b * HW + 4 * (size_t)q;
     float nr[4], ni[4];
     if (!n_re) {
-      ipdm_philox_normal4(seed, sample_offset + b, step_id, 0, (uint32_t)q, nr);
-      ipdm_philox_normal4(seed, sample_offset + b, step_id, 1, (uint32_t)q, ni);
+      langevin_quad(lg, b, 0, (uint32_t)q, nr);
+      langevin_quad(lg, b, 1, (uint32_t)q, ni);
     }
     if (!aligned) {
       for (int j = 0; j < 4; ++j) {
         const float a = n_re ? n_re[gi + j] : nr[j], c = n_re ? n_im[gi + j] : ni[j];
-        x_re[gi + j] = x_re[gi + j] + step * g_re[gi + j] + a * noise_scale;
-        x_im[gi + j] = x_im[gi + j] + step * g_im[gi + j] + c * noise_scale;
+        x_re[gi + j] = langevin_update(lg, x_re[gi + j], g_re[gi + j], a);
+        x_im[gi + j] = langevin_update(lg, x_im[gi + j], g_im[gi + j], c);
       }
       continue;
     }
@@ -311,10 +307,10 @@ __global__ __launch_bounds__(256) void langevin_planes_kernel(float* x_re, float
     }
     float4 xr = *reinterpret_cast<float4*>(x_re + gi), xi = *reinterpret_cast<float4*>(x_im + gi);
     const float4 gr = *reinterpret_cast<const float4*>(g_re + gi), gim = *reinterpret_cast<const float4*>(g_im + gi);
-    xr.x = xr.x + step * gr.x + nr[0] * noise_scale; xr.y = xr.y + step * gr.y + nr[1] * noise_scale;
-    xr.z = xr.z + step * gr.z + nr[2] * noise_scale; xr.w = xr.w + step * gr.w + nr[3] * noise_scale;
-    xi.x = xi.x + step * gim.x + ni[0] * noise_scale; xi.y = xi.y + step * gim.y + ni[1] * noise_scale;
-    xi.z = xi.z + step * gim.z + ni[2] * noise_scale; xi.w = xi.w + step * gim.w + ni[3] * noise_scale;
+    xr.x = langevin_update(lg, xr.x, gr.x, nr[0]); xr.y = langevin_update(lg, xr.y, gr.y, nr[1]);
+    xr.z = langevin_update(lg, xr.z, gr.z, nr[2]); xr.w = langevin_update(lg, xr.w, gr.w, nr[3]);
+    xi.x = langevin_update(lg, xi.x, gim.x, ni[0]); xi.y = langevin_update(lg, xi.y, gim.y, ni[1]);
+    xi.z = langevin_update(lg, xi.z, gim.z, ni[2]); xi.w = langevin_update(lg, xi.w, gim.w, ni[3]);
     *reinterpret_cast<float4*>(x_re + gi) = xr;
     *reinterpret_cast<float4*>(x_im + gi) = xi;
   }
@@ -354,15 +350,16 @@ static int launch_cols(const F& f, int B, int coils, int H, int W, int inverse, 
   return ipdm_launch_status();
 }
 
+// tmp: pb.n_coils * pb.B column-transformed images; the coil sum weighted by pb.sens (NULL: unweighted)
 template <int FIN, typename SensT>
-static int launch_accum(const float2* tmp, const SensT* sens, float2* out_c, float* out_f, float* x_re, float* x_im,
-                        const ipdm_sched_t* sched, float coef, int B, int coils, int H, int W, hipStream_t s) {
-  const size_t lds = strip_lds_bytes(W);
+static int launch_accum(const float2* tmp, const SenseProblem<SensT>& pb, float2* out_c, float* out_f, float* x_re, float* x_im,
+                        const ipdm_sched_t* sched, float coef, hipStream_t s) {
+  const size_t lds = strip_lds_bytes(pb.W);
   int rc = set_lds(rows_inv_accum_kernel<FIN, SensT>, lds);
   if (rc) return rc;
-  const int RS = H < STRIP_ELEMS / W ? H : STRIP_ELEMS / W;
-  hipLaunchKernelGGL((rows_inv_accum_kernel<FIN, SensT>), dim3(H / RS, B), dim3(FFT_THREADS), lds, s, tmp, sens, out_c, out_f, x_re,
-                     x_im, sched, coef, B, coils, H, W);
+  const int RS = pb.H < STRIP_ELEMS / pb.W ? pb.H : STRIP_ELEMS / pb.W;
+  hipLaunchKernelGGL((rows_inv_accum_kernel<FIN, SensT>), dim3(pb.H / RS, pb.B), dim3(FFT_THREADS), lds, s, tmp, pb.sens, out_c,
+                     out_f, x_re, x_im, sched, coef, pb.B, pb.n_coils, pb.H, pb.W);
   return ipdm_launch_status();
 }
 
@@ -381,97 +378,78 @@ int fft2c(const float2* in, float2* out, int batch, int H, int W, int inverse, h
 }
 
 template <typename SensT>
-int sense_forward(const float2* x, const SensT* sens, const uint8_t* mask, int mask_t, float2* y, int B, int n_coils,
-                  int H, int W, hipStream_t s) {
+int sense_forward(const float2* x, const SenseProblem<SensT>& pb, float2* y, hipStream_t s) {
+  const int B = pb.B, n_coils = pb.n_coils, H = pb.H, W = pb.W;
   const ImgGeo g{B, H, W};
-  RowsFwd<SensT> rf{g, x, nullptr, nullptr, sens, y};
+  RowsFwd<SensT> rf{g, x, nullptr, nullptr, pb.sens, y};
   int rc = launch_rows(rf, B, n_coils, H, W, 0, s);
   if (rc) return rc;
-  ColsFwdMask cf{g, y, mask, mask_t, 1.f / sqrtf((float)H * (float)W)};
+  ColsFwdMask cf{g, y, pb.mask, pb.mask_t, 1.f / sqrtf((float)H * (float)W)};
   return launch_cols<ColsFwdMask, false>(cf, B, n_coils, H, W, 0, s);
 }
-template int sense_forward<float>(const float2*, const float*, const uint8_t*, int, float2*, int, int, int, int, hipStream_t);
-template int sense_forward<float2>(const float2*, const float2*, const uint8_t*, int, float2*, int, int, int, int,
-                                   hipStream_t);
+template int sense_forward(const float2*, const SenseProblem<float>&, float2*, hipStream_t);
+template int sense_forward(const float2*, const SenseProblem<float2>&, float2*, hipStream_t);
 
 template <typename SensT>
-int sense_adjoint(const float2* sm, const SensT* sens, const uint8_t* mask, int mask_t, int apply_mask, float2* x_out,
-                  float* ssos_out, float2* ws, int B, int n_coils, int H, int W, hipStream_t s) {
-  const ImgGeo g{B, H, W};
-  ColsInvFromS ci{g, sm, ws, mask, mask_t, apply_mask};
-  int rc = launch_cols<ColsInvFromS, false>(ci, B, n_coils, H, W, 1, s);
+int sense_adjoint(const SenseProblem<SensT>& pb, int apply_mask, float2* x_out, float* ssos_out, float2* ws, hipStream_t s) {
+  const ImgGeo g{pb.B, pb.H, pb.W};
+  ColsInvFromS ci{g, pb.y, ws, pb.mask, pb.mask_t, apply_mask};
+  int rc = launch_cols<ColsInvFromS, false>(ci, pb.B, pb.n_coils, pb.H, pb.W, 1, s);
   if (rc) return rc;
-  if (ssos_out)
-    return launch_accum<FIN_SSOS>(ws, static_cast<const float*>(nullptr), nullptr, ssos_out, nullptr, nullptr, nullptr, 0.f, B, n_coils, H, W, s);
-  return launch_accum<FIN_ADJOINT>(ws, sens, x_out, nullptr, nullptr, nullptr, nullptr, 0.f, B, n_coils, H, W, s);
+  if (ssos_out) {                                              // no maps in a sum of squares: one kernel for both SensT
+    const SenseProblem<float> np{nullptr, nullptr, nullptr, 1, pb.B, pb.n_coils, pb.H, pb.W};
+    return launch_accum<FIN_SSOS>(ws, np, nullptr, ssos_out, nullptr, nullptr, nullptr, 0.f, s);
+  }
+  return launch_accum<FIN_ADJOINT>(ws, pb, x_out, nullptr, nullptr, nullptr, nullptr, 0.f, s);
 }
-template int sense_adjoint<float>(const float2*, const float*, const uint8_t*, int, int, float2*, float*, float2*, int, int,
-                                  int, int, hipStream_t);
-template int sense_adjoint<float2>(const float2*, const float2*, const uint8_t*, int, int, float2*, float*, float2*, int, int,
-                                   int, int, hipStream_t);
+template int sense_adjoint(const SenseProblem<float>&, int, float2*, float*, float2*, hipStream_t);
+template int sense_adjoint(const SenseProblem<float2>&, int, float2*, float*, float2*, hipStream_t);
 
-static int launch_langevin(float* x_re, float* x_im, const float* g_re, const float* g_im, const float* n_re,
-                           const float* n_im, float step, float noise_scale, uint64_t seed, int64_t sample_offset,
-                           int64_t step_id, const ipdm_sched_t* sched, int B, int HW, hipStream_t s) {
-  int gx = (HW / 4 + 255) / 256;
+int langevin(float* x_re, float* x_im, const LangevinArgs& lg, int B, int H, int W, hipStream_t s) {
+  int gx = (H * W / 4 + 255) / 256;
   if (gx > 256) gx = 256;
-  hipLaunchKernelGGL(langevin_planes_kernel, dim3(gx, B), dim3(256), 0, s, x_re, x_im, g_re, g_im, n_re, n_im, step,
-                     noise_scale, seed, (long long)sample_offset, (long long)step_id, sched, HW);
+  hipLaunchKernelGGL(langevin_planes_kernel, dim3(gx, B), dim3(256), 0, s, x_re, x_im, lg, H * W);
   return ipdm_launch_status();
 }
 
-int langevin(float* x_re, float* x_im, const float* g_re, const float* g_im, const float* n_re, const float* n_im, float step,
-             float noise_scale, uint64_t seed, int64_t sample_offset, int64_t step_id, const ipdm_sched_t* sched, int B, int H,
-             int W, hipStream_t s) {
-  return launch_langevin(x_re, x_im, g_re, g_im, n_re, n_im, step, noise_scale, seed, sample_offset, step_id, sched, B, H * W, s);
+// forward rows, then columns forward + data-consistency operator + columns inverse, in place on ws[coil][b]
+template <typename SensT>
+static int rows_cols_prox(const float2* xc, const float* x_re, const float* x_im, const SenseProblem<SensT>& pb, int mode,
+                          float coef, const ipdm_sched_t* sched, float2* ws, hipStream_t s) {
+  const ImgGeo g{pb.B, pb.H, pb.W};
+  RowsFwd<SensT> rf{g, xc, x_re, x_im, pb.sens, ws};
+  int rc = launch_rows(rf, pb.B, pb.n_coils, pb.H, pb.W, 0, s);
+  if (rc) return rc;
+  ColsProx cp{g, ws, pb.y, pb.mask, pb.mask_t, mode, 1.f / sqrtf((float)pb.H * (float)pb.W), coef, sched};
+  return launch_cols<ColsProx, true>(cp, pb.B, pb.n_coils, pb.H, pb.W, 0, s);
 }
 
 // out[b] = A^H (A v - y): the proximal chain's three passes with the coil sum stored instead of applied
 template <typename SensT>
-int normal_op(const float2* xc, const float* x_re, const float* x_im, const float2* y, const SensT* sens, const uint8_t* mask,
-              int mask_t, float2* out, float2* ws, int B, int n_coils, int H, int W, hipStream_t s) {
-  const ImgGeo g{B, H, W};
-  RowsFwd<SensT> rf{g, xc, x_re, x_im, sens, ws};
-  int rc = launch_rows(rf, B, n_coils, H, W, 0, s);
+int normal_op(const float2* xc, const float* x_re, const float* x_im, const SenseProblem<SensT>& pb, float2* out, float2* ws,
+              hipStream_t s) {
+  int rc = rows_cols_prox(xc, x_re, x_im, pb, 0, 0.f, nullptr, ws, s);
   if (rc) return rc;
-  ColsProx cp{g, ws, y, mask, mask_t, 0, 1.f / sqrtf((float)H * (float)W), 0.f, nullptr};
-  rc = launch_cols<ColsProx, true>(cp, B, n_coils, H, W, 0, s);
-  if (rc) return rc;
-  return launch_accum<FIN_ADJOINT>(ws, sens, out, nullptr, nullptr, nullptr, nullptr, 0.f, B, n_coils, H, W, s);
+  return launch_accum<FIN_ADJOINT>(ws, pb, out, nullptr, nullptr, nullptr, nullptr, 0.f, s);
 }
-template int normal_op<float>(const float2*, const float*, const float*, const float2*, const float*, const uint8_t*, int,
-                              float2*, float2*, int, int, int, int, hipStream_t);
-template int normal_op<float2>(const float2*, const float*, const float*, const float2*, const float2*, const uint8_t*, int,
-                               float2*, float2*, int, int, int, int, hipStream_t);
+template int normal_op(const float2*, const float*, const float*, const SenseProblem<float>&, float2*, float2*, hipStream_t);
+template int normal_op(const float2*, const float*, const float*, const SenseProblem<float2>&, float2*, float2*, hipStream_t);
 
-// Langevin (optional) + data-consistency operator on planar x (in place).  sens NULL = single coil; mode as ColsProx.
 template <typename SensT>
-int prox_step(float* x_re, float* x_im, const float* g_re, const float* g_im, const float* n_re, const float* n_im,
-              float step, float noise_scale, uint64_t seed, int64_t sample_offset, int64_t step_id,
-              const ipdm_sched_t* sched, const float2* y, const SensT* sens, const uint8_t* mask, int mask_t, float coef,
-              int mode, float2* ws, int B, int n_coils, int H, int W, hipStream_t s) {
-  const int HW = H * W;
-  if (g_re) {
-    int rc = launch_langevin(x_re, x_im, g_re, g_im, n_re, n_im, step, noise_scale, seed, sample_offset, step_id, sched, B, HW, s);
+int prox_step(float* x_re, float* x_im, const LangevinArgs& lg, const SenseProblem<SensT>& pb, float coef, int mode, float2* ws,
+              hipStream_t s) {
+  if (lg.g_re) {
+    int rc = langevin(x_re, x_im, lg, pb.B, pb.H, pb.W, s);
     if (rc) return rc;
   }
   // (the 128x128 kernel returns early when coef == 0; here the schedule value lives on the device, so the chain always
   //  runs -- with coef == 0 it adds exactly zero for the L2 modes)
-  const ImgGeo g{B, H, W};
-  RowsFwd<SensT> rf{g, nullptr, x_re, x_im, sens, ws};
-  int rc = launch_rows(rf, B, n_coils, H, W, 0, s);
+  int rc = rows_cols_prox(nullptr, x_re, x_im, pb, mode, coef, lg.sched, ws, s);
   if (rc) return rc;
-  ColsProx cp{g, ws, y, mask, mask_t, mode, 1.f / sqrtf((float)H * (float)W), coef, sched};
-  rc = launch_cols<ColsProx, true>(cp, B, n_coils, H, W, 0, s);
-  if (rc) return rc;
-  if (mode <= 0) return launch_accum<FIN_L2>(ws, sens, nullptr, nullptr, x_re, x_im, sched, coef, B, n_coils, H, W, s);
-  return launch_accum<FIN_REPLACE>(ws, sens, nullptr, nullptr, x_re, x_im, nullptr, 0.f, B, n_coils, H, W, s);
+  if (mode <= 0) return launch_accum<FIN_L2>(ws, pb, nullptr, nullptr, x_re, x_im, lg.sched, coef, s);
+  return launch_accum<FIN_REPLACE>(ws, pb, nullptr, nullptr, x_re, x_im, nullptr, 0.f, s);
 }
-template int prox_step<float>(float*, float*, const float*, const float*, const float*, const float*, float, float, uint64_t,
-                              int64_t, int64_t, const ipdm_sched_t*, const float2*, const float*, const uint8_t*, int, float,
-                              int, float2*, int, int, int, int, hipStream_t);
-template int prox_step<float2>(float*, float*, const float*, const float*, const float*, const float*, float, float, uint64_t,
-                               int64_t, int64_t, const ipdm_sched_t*, const float2*, const float2*, const uint8_t*, int, float,
-                               int, float2*, int, int, int, int, hipStream_t);
+template int prox_step(float*, float*, const LangevinArgs&, const SenseProblem<float>&, float, int, float2*, hipStream_t);
+template int prox_step(float*, float*, const LangevinArgs&, const SenseProblem<float2>&, float, int, float2*, hipStream_t);
 
 }  // namespace ipdm_kspace_large

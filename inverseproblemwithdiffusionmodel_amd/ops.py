@@ -284,26 +284,37 @@ def sense_l2prox(z_re, z_im, y, sens_f32, mask_u8, coef, out_re=None, out_im=Non
     return out_re, out_im
 
 
+def _fused_step(what, x_re, x_im, g_re, g_im, y, noise_re, noise_im, step, noise_scale, seed, sample_offset, step_id,
+                dev_sched, sens=None, entries=None):
+    """operand checks of a fused iteration tail, in the wrappers' order, and the 12 leading values of its C signature
+    -> (fn, B, H, W, head).  entries: the (real, complex) entry points of a SENSE step; None: single coil (fn None)"""
+    for t, n in ((x_re, "x_re"), (x_im, "x_im"), (g_re, "g_re"), (g_im, "g_im")):
+        _inplace_operand(t, torch.float32, n)
+    H, W = x_re.shape[-2:]
+    fn = _sens_entry(sens, *entries, H, W) if entries else None
+    _inplace_operand(y, torch.complex64, "y")
+    B = x_re.numel() // (H * W) if H * W else 0
+    if entries:
+        for t, n in ((noise_re, "noise_re"), (noise_im, "noise_im")):
+            if t is not None:
+                _inplace_operand(t, torch.float32, n)
+        if g_re.numel() != x_re.numel() or g_im.numel() != x_im.numel() or y.numel() != sens.shape[0] * B * H * W:
+            raise ValueError(f"{what}: operand sizes do not match the state")
+    head = (_ptr(x_re), _ptr(x_im), _ptr(g_re), _ptr(g_im), _ptr(noise_re), _ptr(noise_im), float(step), float(noise_scale),
+            int(seed), int(sample_offset), int(step_id), _ptr(dev_sched))
+    return fn, B, H, W, head
+
+
 def ald_sense_step(x_re, x_im, g_re, g_im, y, sens_f32, mask_u8, work, step=0.0, noise_scale=0.0, coef=0.0,
                    noise_re=None, noise_im=None, seed=0, sample_offset=0, step_id=0, dev_sched=None):
     """in place on x_re / x_im.  dev_sched: uint8/any device tensor holding an ipdm_sched_t.  sens_f32: the coil maps,
     float32 or complex64."""
-    for t, n in ((x_re, "x_re"), (x_im, "x_im"), (g_re, "g_re"), (g_im, "g_im")):
-        _inplace_operand(t, torch.float32, n)
-    fn = _sens_entry(sens_f32, "ipdm_ald_sense_step_f32", "ipdm_ald_sense_step_csm_f32", *x_re.shape[-2:])
-    _inplace_operand(y, torch.complex64, "y")
-    for t, n in ((noise_re, "noise_re"), (noise_im, "noise_im")):
-        if t is not None:
-            _inplace_operand(t, torch.float32, n)
-    H, W = x_re.shape[-2:]
-    B = x_re.numel() // (H * W)
-    if g_re.numel() != x_re.numel() or g_im.numel() != x_im.numel() or y.numel() != sens_f32.shape[0] * B * H * W:
-        raise ValueError("ald_sense_step: operand sizes do not match the state")
+    fn, B, H, W, head = _fused_step("ald_sense_step", x_re, x_im, g_re, g_im, y, noise_re, noise_im, step, noise_scale, seed,
+                                    sample_offset, step_id, dev_sched, sens_f32,
+                                    ("ipdm_ald_sense_step_f32", "ipdm_ald_sense_step_csm_f32"))
     _check_work(work, B, sens_f32.shape[0], H, W, "ald_sense_step")
     mask_t = _mask_t(mask_u8, H, W, "ald_sense_step")
-    call(fn, _ptr(x_re), _ptr(x_im), _ptr(g_re), _ptr(g_im), _ptr(noise_re), _ptr(noise_im),
-         float(step), float(noise_scale), int(seed), int(sample_offset), int(step_id), _ptr(dev_sched),
-         _ptr(y), _ptr(sens_f32), _ptr(mask_u8), mask_t, float(coef), _ptr(work), B, sens_f32.shape[0], H, W,
+    call(fn, *head, _ptr(y), _ptr(sens_f32), _ptr(mask_u8), mask_t, float(coef), _ptr(work), B, sens_f32.shape[0], H, W,
          _stream())
     _written(x_re, x_im)
 
@@ -375,23 +386,13 @@ def ald_sense_cg_step(x_re, x_im, g_re, g_im, y, sens_f32, mask_u8, work, step=0
     """ald_sense_step with the conjugate-gradient proximal; in place on x_re / x_im.  coef (dev_sched's coef field)
     carries a = alpha / lamda.  -> iters (device int32 [B])"""
     max_iter, tol = _check_cg_scalars(max_iter, tol, "ald_sense_cg_step")
-    for t, n in ((x_re, "x_re"), (x_im, "x_im"), (g_re, "g_re"), (g_im, "g_im")):
-        _inplace_operand(t, torch.float32, n)
-    fn = _sens_entry(sens_f32, "ipdm_ald_sense_cg_step_f32", "ipdm_ald_sense_cg_step_csm_f32", *x_re.shape[-2:])
-    _inplace_operand(y, torch.complex64, "y")
-    for t, n in ((noise_re, "noise_re"), (noise_im, "noise_im")):
-        if t is not None:
-            _inplace_operand(t, torch.float32, n)
-    H, W = x_re.shape[-2:]
-    B = x_re.numel() // (H * W) if H * W else 0
+    fn, B, H, W, head = _fused_step("ald_sense_cg_step", x_re, x_im, g_re, g_im, y, noise_re, noise_im, step, noise_scale, seed,
+                                    sample_offset, step_id, dev_sched, sens_f32,
+                                    ("ipdm_ald_sense_cg_step_f32", "ipdm_ald_sense_cg_step_csm_f32"))
     nc = sens_f32.shape[0]
-    if g_re.numel() != x_re.numel() or g_im.numel() != x_im.numel() or y.numel() != nc * B * H * W:
-        raise ValueError("ald_sense_cg_step: operand sizes do not match the state")
     work, iters_out = _check_cg_args(work, ahy, iters_out, B, nc, H, W, x_re.device, "ald_sense_cg_step")
     mask_t = _mask_t(mask_u8, H, W, "ald_sense_cg_step")
-    call(fn, _ptr(x_re), _ptr(x_im), _ptr(g_re), _ptr(g_im), _ptr(noise_re), _ptr(noise_im),
-         float(step), float(noise_scale), int(seed), int(sample_offset), int(step_id), _ptr(dev_sched),
-         _ptr(y), _ptr(sens_f32), _ptr(mask_u8), mask_t, float(coef), _ptr(work), _ptr(ahy), max_iter, tol,
+    call(fn, *head, _ptr(y), _ptr(sens_f32), _ptr(mask_u8), mask_t, float(coef), _ptr(work), _ptr(ahy), max_iter, tol,
          _ptr(iters_out), B, nc, H, W, _stream())
     _written(x_re, x_im, iters_out)
     return iters_out
@@ -424,19 +425,15 @@ def singlecoil_prox(z_re, z_im, y, mask_u8, coef, mode, out_re=None, out_im=None
 def ald_singlecoil_step(x_re, x_im, g_re, g_im, y, mask_u8, mode, step=0.0, noise_scale=0.0, coef=0.0, noise_re=None,
                         noise_im=None, seed=0, sample_offset=0, step_id=0, dev_sched=None, work=None):
     """in place on x_re / x_im (contiguous float32 GPU planes)"""
-    for t, n in ((x_re, "x_re"), (x_im, "x_im"), (g_re, "g_re"), (g_im, "g_im")):
-        _inplace_operand(t, torch.float32, n)
-    _inplace_operand(y, torch.complex64, "y")
-    H, W = x_re.shape[-2:]
-    B = x_re.numel() // (H * W)
+    _, B, H, W, head = _fused_step("ald_singlecoil_step", x_re, x_im, g_re, g_im, y, noise_re, noise_im, step, noise_scale,
+                                   seed, sample_offset, step_id, dev_sched)
     if work is None and _large_image(H, W):
         work = sense_workspace(B, 1, H, W, x_re.device)
     if work is not None or _large_image(H, W):
         _check_work(work, B, 1, H, W, "ald_singlecoil_step")
     mask_t = _mask_t(mask_u8, H, W, "ald_singlecoil_step")
-    call("ipdm_ald_singlecoil_step_f32", _ptr(x_re), _ptr(x_im), _ptr(g_re), _ptr(g_im), _ptr(noise_re), _ptr(noise_im),
-         float(step), float(noise_scale), int(seed), int(sample_offset), int(step_id), _ptr(dev_sched), _ptr(y),
-         _ptr(mask_u8), mask_t, float(coef), int(mode), _ptr(work), B, H, W, _stream())
+    call("ipdm_ald_singlecoil_step_f32", *head, _ptr(y), _ptr(mask_u8), mask_t, float(coef), int(mode), _ptr(work), B, H, W,
+         _stream())
     _written(x_re, x_im)
 
 
