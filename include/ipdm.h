@@ -113,11 +113,12 @@ int ipdm_fused_bias_act_f64(const double* x, const double* b, const double* ref,
  * ---------------------------------------------------------------------------------------------- */
 
 /* centred orthonormal 2-D DFT of `batch` images [H][W] c64; inverse != 0 -> k2i_complex.  Any H, W
- * in [1, 1024]; power-of-two sizes with H*W <= 16384 take the single-launch LDS FFT. in may equal out. */
+ * in [1, 1024] (this entry point's own limit: a served side above 1024 is IPDM_EINVAL here, though the SENSE operators
+ * take it); served sizes (ipdm_kspace_size_class) take the FFT kernels, the rest an O(N^2) direct DFT. in may equal out. */
 int ipdm_fft2c_c64(const float* in, float* out, int batch, int H, int W, int inverse,
                    float* workspace /* batch*H*W c64, only for the non-LDS path; may be NULL otherwise */,
                    void* stream);
-/* bytes of workspace ipdm_fft2c_c64 needs for (batch,H,W); 0 when the LDS path applies */
+/* bytes of workspace ipdm_fft2c_c64 needs for (batch,H,W); 0 for a served size (the direct DFT is not used) */
 int64_t ipdm_fft2c_workspace_bytes(int batch, int H, int W);
 
 /* mask layouts the (mask, mask_t) entry points accept: IPDM_MASK_LINES | IPDM_MASK_2D */
@@ -125,15 +126,27 @@ int64_t ipdm_fft2c_workspace_bytes(int batch, int H, int W);
 #define IPDM_MASK_2D 2    /* mask_t < 0: uint8 [-mask_t][H][W] */
 int ipdm_mask_layouts(void);
 
+/* Image sizes the k-space kernels serve.  A side N is served when it is a power of two from 4, or N = 2^a 3^b 5^c with
+ * a >= 4 (a multiple of 16) and 16 <= N <= 2048; a pair (H, W) may mix served sides freely (one exception: 8x2000 and
+ * 2000x8 have no kernel).
+ *   IPDM_KSPACE_LDS     H*W <= 16384: the whole image in one CU's LDS
+ *   IPDM_KSPACE_STRIPS  larger, sides up to 2048: row / column FFT passes over strips
+ *   IPDM_KSPACE_NONE    no kernel: the SENSE / single-coil / CG entry points return IPDM_EUNSUPPORTED (odd sides, a factor
+ *                       7 or larger, multiples of 8 that are not multiples of 16), ipdm_fft2c_c64 falls back to a direct DFT */
+#define IPDM_KSPACE_NONE 0
+#define IPDM_KSPACE_LDS 1
+#define IPDM_KSPACE_STRIPS 2
+int ipdm_kspace_size_class(int H, int W);
+
 /* y[c][b] = mask * fft2c(S_c * x[b])        x [B][H][W] c64 -> y [n_coils][B][H][W] c64 */
 /* (sens == NULL with n_coils == 1: the single-coil operator RandomUndersamplingFourier.__call__, y = M F x,
  *  undersampling_fourier.py:77-82) */
 int ipdm_sense_forward_c64(const float* x, const float* sens, const uint8_t* mask, int mask_t,
                            float* y, int B, int n_coils, int H, int W, void* stream);
 /* Scratch the SENSE / single-coil operators below need for (B, n_coils, H, W):
- *   power-of-two images up to 128x128 (image resident in LDS): n_coils*B*H*W*8 bytes for the proximal operators (one
+ *   IPDM_KSPACE_LDS sizes (up to 128x128; image resident in LDS): n_coils*B*H*W*8 bytes for the proximal operators (one
  *   plane per (sample, coil): the coils of a sample run in parallel workgroups), nothing for forward / adjoint / SSOS;
- *   larger power-of-two images (e.g. the reference's 256x256 ACDC slices, helpers/load_data.py:274; row / column FFT
+ *   IPDM_KSPACE_STRIPS sizes (e.g. the reference's 256x256 ACDC slices, helpers/load_data.py:274; row / column FFT
  *   passes): n_coils*B*H*W*8 bytes for every operator except ipdm_sense_forward_c64 (single-coil: n_coils = 1). */
 int64_t ipdm_sense_workspace_bytes(int B, int n_coils, int H, int W);
 /* x[b] = sum_c S_c * ifft2c(mask? mask*s : s)    apply_mask == 0 reproduces SENSE.conj_op; workspace: see above
@@ -208,7 +221,7 @@ int ipdm_ald_sense_step_csm_f32(float* x_re, float* x_im, const float* g_re, con
  *   ahy         optional A^H y, complex64 [B][H][W] (constant over a sampler run); NULL: formed into the workspace
  *   iters_out   optional device int32 [B]: CG iterations each sample ran
  *   work        ipdm_sense_cg_workspace_bytes(B, n_coils, H, W)
- * Sizes as the other SENSE operators (power-of-two sides: up to 128x128 in LDS, up to 2048 by row / column passes),
+ * Sizes as the other SENSE operators (ipdm_kspace_size_class: up to 128x128 in LDS, up to 2048 by row / column passes),
  * anything else IPDM_EUNSUPPORTED.  The launch sequence is fixed by (max_iter, size) alone -- it does not depend on
  * convergence -- and the calls are asynchronous, allocation-free and hipGraph-capturable.  Deterministic (no atomics). */
 int64_t ipdm_sense_cg_workspace_bytes(int B, int n_coils, int H, int W);

@@ -38,6 +38,7 @@ SIGNATURES = {
     "ipdm_fft2c_c64": [P, P, c_int, c_int, c_int, c_int, P, P],
     "ipdm_fft2c_workspace_bytes": [c_int, c_int, c_int],
     "ipdm_mask_layouts": [],
+    "ipdm_kspace_size_class": [c_int, c_int],
     "ipdm_sense_forward_c64": [P, P, P, c_int, P, c_int, c_int, c_int, c_int, P],
     "ipdm_sense_workspace_bytes": [c_int, c_int, c_int, c_int],
     "ipdm_sense_adjoint_c64": [P, P, P, c_int, c_int, P, P, c_int, c_int, c_int, c_int, P],

@@ -7,7 +7,7 @@
 //
 // The fftshift/ifftshift pairs of i2k_complex / k2i_complex (ncsn/linear_transforms/__init__.py:36-57)
 // are folded into (-1)^(r+c) sign flips before and after an ordinary FFT (exact for sizes % 4 == 0);
-// sizes the LDS path cannot take go through a direct centred DFT with an exact integer phase index.
+// sizes without an FFT kernel (ipdm_kspace_size_class) go through a direct centred DFT with an exact integer phase index.
 #include "kspace_fft.h"
 
 namespace {
@@ -15,9 +15,11 @@ namespace {
 using namespace ipdm_kspace;
 
 // ---------------------------------------------------------------------------------------------
+// MIXED (every FFT kernel here): sides with factors 3 or 5, kspace_fft.h; chosen at launch by fft_dispatch
+template <bool MIXED>
 __global__ __launch_bounds__(FFT_THREADS) void fft2c_lds_kernel(const float2* in, float2* out,
                                                                 int H, int W, int inverse) {
-  FFT_LDS_SETUP(H, W)
+  FFT_LDS_SETUP(H, W, MIXED)
   const int HW = H * W;
   const float2* src = in + (size_t)blockIdx.x * HW;
   float2* dst = out + (size_t)blockIdx.x * HW;
@@ -28,7 +30,7 @@ __global__ __launch_bounds__(FFT_THREADS) void fft2c_lds_kernel(const float2* in
     L.buf[e] = make_float2(v.x * s, v.y * s);
   }
   __syncthreads();
-  fft2_lds(L, H, W, inverse != 0);
+  fft2_lds<MIXED>(L, H, W, inverse != 0);
   const float scale = rsqrtf((float)HW);
   for (int e = threadIdx.x; e < HW; e += FFT_THREADS) {
     int r = e / W, c = e - r * W;
@@ -75,12 +77,12 @@ __global__ __launch_bounds__(256) void dft_rows_transposed_kernel(const float2* 
 
 // SensT (here and below): the coil maps' element type, float or float2 (interleaved complex64); the products are
 // sens_mul / sens_mul_conj of kspace_fft.h
-template <typename SensT>
+template <typename SensT, bool MIXED>
 __global__ __launch_bounds__(FFT_THREADS) void sense_forward_kernel(const float2* __restrict__ x,
                                                                     const SensT* __restrict__ sens,
                                                                     const uint8_t* __restrict__ mask, int mask_t,
                                                                     float2* __restrict__ y, int B, int H, int W) {
-  FFT_LDS_SETUP(H, W)
+  FFT_LDS_SETUP(H, W, MIXED)
   const int HW = H * W;
   const int b = blockIdx.x, coil = blockIdx.y;
   const float2* src = x + (size_t)b * HW;
@@ -92,7 +94,7 @@ __global__ __launch_bounds__(FFT_THREADS) void sense_forward_kernel(const float2
     L.buf[e] = sm ? sens_mul(v, s, sm[e]) : make_float2(v.x * s, v.y * s);
   }
   __syncthreads();
-  fft2_lds(L, H, W, false);
+  fft2_lds<MIXED>(L, H, W, false);
   const float scale = rsqrtf((float)HW);
   float2* dst = y + ((size_t)coil * B + b) * HW;
   for (int e = threadIdx.x; e < HW; e += FFT_THREADS) {
@@ -106,13 +108,13 @@ __global__ __launch_bounds__(FFT_THREADS) void sense_forward_kernel(const float2
 // s [n_coils][B][H][W] -> out[b] = sum_c S_c * ifft2c(s[c][b])  (or root-sum-of-squares for SSOS).
 // The coil sum is accumulated in the (L2-resident) output image, coil by coil in index order, like the
 // reference's `X_out += ...` loop: no accumulator registers live across the FFT, deterministic.
-template <bool SSOS, typename SensT>
+template <bool SSOS, typename SensT, bool MIXED>
 __global__ __launch_bounds__(FFT_THREADS) void sense_adjoint_kernel(const float2* __restrict__ s,
                                                                     const SensT* __restrict__ sens,
                                                                     const uint8_t* __restrict__ mask, int mask_t,
                                                                     int apply_mask, float* out, int B,
                                                                     int n_coils, int H, int W) {
-  FFT_LDS_SETUP(H, W)
+  FFT_LDS_SETUP(H, W, MIXED)
   const int HW = H * W;
   const int b = blockIdx.x;
   const float scale = rsqrtf((float)HW);
@@ -126,7 +128,7 @@ __global__ __launch_bounds__(FFT_THREADS) void sense_adjoint_kernel(const float2
       L.buf[e] = make_float2(v.x * sg, v.y * sg);
     }
     __syncthreads();
-    fft2_lds(L, H, W, true);
+    fft2_lds<MIXED>(L, H, W, true);
     const bool last = coil == n_coils - 1;
     for (int e = threadIdx.x; e < HW; e += FFT_THREADS) {
       float2 v = L.buf[e];
@@ -166,14 +168,14 @@ __device__ __forceinline__ void langevin_phase(float* xr, float* xi, const Lange
 //   per coil: LDS = S_c z ; FFT ; residual on sampled columns ; IFFT ; work += S_c * (.)
 //   final:   x = z - coef * work
 // `work` ([B][H][W] c64) carries the coil sum so that no accumulator registers live across the FFTs.
-template <bool LANGEVIN, typename SensT>
+template <bool LANGEVIN, typename SensT, bool MIXED>
 __global__ __launch_bounds__(FFT_THREADS) void ald_sense_step_kernel(float* x_re, float* x_im, LangevinArgs lg,
                                                                      const SenseProblem<SensT> pb, float coef, float2* work) {
   const int B = pb.B, n_coils = pb.n_coils, H = pb.H, W = pb.W, mask_t = pb.mask_t;
   const float2* __restrict__ y = pb.y;
   const SensT* __restrict__ sens = pb.sens;
   const uint8_t* __restrict__ mask = pb.mask;
-  FFT_LDS_SETUP(H, W)
+  FFT_LDS_SETUP(H, W, MIXED)
   coef = sched_override(lg, coef);
   const int HW = H * W;
   const int b = blockIdx.x;
@@ -195,7 +197,7 @@ __global__ __launch_bounds__(FFT_THREADS) void ald_sense_step_kernel(float* x_re
       }
     }
     __syncthreads();
-    fft2_lds(L, H, W, inv);
+    fft2_lds<MIXED>(L, H, W, inv);
     if (!inv) {
       const float2* yc = y + ((size_t)coil * B + b) * HW;
       for (int e = threadIdx.x; e < HW; e += FFT_THREADS) {
@@ -233,7 +235,7 @@ __global__ __launch_bounds__(FFT_THREADS) void ald_sense_step_kernel(float* x_re
 // pure function of (seed, sample, step, element)), does ITS coil's transform pair and writes
 // r_c = conj(S_c) F^-1[M (F S_c v - y_c)] to planes[b][coil]: 56 workgroups instead of 14, one transform pair deep instead
 // of four.
-template <int MODE, typename SensT>
+template <int MODE, typename SensT, bool MIXED>
 __global__ __launch_bounds__(FFT_THREADS) void sense_normal_coil_kernel(const float* x_re, const float* x_im, LangevinArgs lg,
                                                                         float coef, const float2* __restrict__ p,
                                                                         const CgState* __restrict__ state,
@@ -248,7 +250,7 @@ __global__ __launch_bounds__(FFT_THREADS) void sense_normal_coil_kernel(const fl
     // the tail's combine pass then only applies the Langevin update; the CG init pass leaves x = z and freezes the sample
     if (sched_override(lg, coef) == 0.f) return;
   }
-  FFT_LDS_SETUP(H, W)
+  FFT_LDS_SETUP(H, W, MIXED)
   const int HW = H * W;
   const float scale = rsqrtf((float)HW);
   const SensT* sm = sens + (size_t)coil * HW;
@@ -266,7 +268,7 @@ __global__ __launch_bounds__(FFT_THREADS) void sense_normal_coil_kernel(const fl
     L.buf[e] = sens_mul(v, sign_rc(r, c), sm[e]);
   }
   __syncthreads();
-  fft2_lds(L, H, W, false);
+  fft2_lds<MIXED>(L, H, W, false);
   const float2* __restrict__ yc = MODE == 0 ? nullptr : pb.y + ((size_t)coil * B + b) * HW;
   for (int e = threadIdx.x; e < HW; e += FFT_THREADS) {
     const int r = e / W, c = e - r * W;
@@ -275,7 +277,7 @@ __global__ __launch_bounds__(FFT_THREADS) void sense_normal_coil_kernel(const fl
                                MODE == 0 ? nullptr : yc + e);
   }
   __syncthreads();
-  fft2_lds(L, H, W, true);
+  fft2_lds<MIXED>(L, H, W, true);
   float2* wk = planes + ((size_t)b * n_coils + coil) * HW;
   for (int e = threadIdx.x; e < HW; e += FFT_THREADS) {
     const int r = e / W, c = e - r * W;
@@ -311,13 +313,13 @@ __global__ __launch_bounds__(256) void ald_sense_combine_kernel(float* x_re, flo
 //   mode 1  SingleCoil  x = F^-1[ (F z + coef*y) / (1 + coef*M) ]          (proximal_op.py:72-94, coef = alpha/lamda)
 //   mode 2  projection  x = F^-1[ coef*y + (1-coef) M F z + (1-M) F z ]   (undersampling_fourier.py:89-97, coef = lamda)
 // The image stays in LDS between the two transforms; z is re-read from x (L2-resident) for mode 0.  pb.sens is not used.
-template <bool LANGEVIN>
+template <bool LANGEVIN, bool MIXED>
 __global__ __launch_bounds__(FFT_THREADS) void ald_singlecoil_step_kernel(float* x_re, float* x_im, LangevinArgs lg,
                                                                           const SenseProblem<float> pb, float coef, int mode) {
   const int H = pb.H, W = pb.W, mask_t = pb.mask_t;
   const float2* __restrict__ y = pb.y;
   const uint8_t* __restrict__ mask = pb.mask;
-  FFT_LDS_SETUP(H, W)
+  FFT_LDS_SETUP(H, W, MIXED)
   coef = sched_override(lg, coef);
   const int HW = H * W;
   const int b = blockIdx.x;
@@ -332,7 +334,7 @@ __global__ __launch_bounds__(FFT_THREADS) void ald_singlecoil_step_kernel(float*
     L.buf[e] = make_float2(xr[e] * sg, xi[e] * sg);
   }
   __syncthreads();
-  fft2_lds(L, H, W, false);
+  fft2_lds<MIXED>(L, H, W, false);
   // k-space value K = sg*scale*v; the inverse transform wants sg*K' -> every formula is written on scale*v and sg*y
   const float2* yb = y + (size_t)b * HW;
   for (int e = threadIdx.x; e < HW; e += FFT_THREADS) {
@@ -358,7 +360,7 @@ __global__ __launch_bounds__(FFT_THREADS) void ald_singlecoil_step_kernel(float*
     L.buf[e] = o;
   }
   __syncthreads();
-  fft2_lds(L, H, W, true);
+  fft2_lds<MIXED>(L, H, W, true);
   for (int e = threadIdx.x; e < HW; e += FFT_THREADS) {
     int r = e / W, c = e - r * W;
     float2 v = L.buf[e];
@@ -377,11 +379,14 @@ template <int MODE, typename SensT>
 static int launch_normal_coils_mode(const float* x_re, const float* x_im, const LangevinArgs& lg, float coef, const float2* p,
                                     const CgState* state, const SenseProblem<SensT>& pb, float2* planes, hipStream_t st) {
   const size_t lds = lds_bytes(pb.H, pb.W);
-  const int rc = set_lds_limit(sense_normal_coil_kernel<MODE, SensT>, lds);
-  if (rc) return rc;
-  hipLaunchKernelGGL((sense_normal_coil_kernel<MODE, SensT>), dim3(pb.n_coils, pb.B), dim3(FFT_THREADS), lds, st, x_re, x_im, lg,
-                     coef, p, state, pb, planes);
-  return ipdm_launch_status();
+  return fft_dispatch(fft_mixed(pb.H, pb.W), [&](auto mixed) {
+    constexpr bool MIXED = decltype(mixed)::value;
+    const int rc = set_lds_limit(sense_normal_coil_kernel<MODE, SensT, MIXED>, lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL((sense_normal_coil_kernel<MODE, SensT, MIXED>), dim3(pb.n_coils, pb.B), dim3(FFT_THREADS), lds, st, x_re,
+                       x_im, lg, coef, p, state, pb, planes);
+    return ipdm_launch_status();
+  });
 }
 
 // the coil-parallel iteration tail: normal operator per coil, then the combine pass
@@ -416,6 +421,12 @@ template int ipdm_kspace::launch_normal_coils(int, const float*, const float*, c
 template int ipdm_kspace::launch_normal_coils(int, const float*, const float*, const LangevinArgs&, float, const float2*,
                                               const CgState*, const SenseProblem<float2>&, float2*, hipStream_t);
 
+extern "C" int ipdm_kspace_size_class(int H, int W) {
+  if (H <= 0 || W <= 0) return IPDM_KSPACE_NONE;
+  if (lds_fft_ok(H, W)) return IPDM_KSPACE_LDS;
+  return ipdm_kspace_large::large_ok(H, W) ? IPDM_KSPACE_STRIPS : IPDM_KSPACE_NONE;
+}
+
 extern "C" int64_t ipdm_fft2c_workspace_bytes(int batch, int H, int W) {
   if (batch <= 0 || H <= 0 || W <= 0) return 0;
   return (lds_fft_ok(H, W) || ipdm_kspace_large::large_ok(H, W)) ? 0 : (int64_t)batch * H * W * 8;
@@ -445,11 +456,14 @@ extern "C" int ipdm_fft2c_c64(const float* in, float* out, int batch, int H, int
   hipStream_t s = ipdm_stream(stream);
   if (lds_fft_ok(H, W)) {
     size_t lds = lds_bytes(H, W);
-    int rc = set_lds_limit(fft2c_lds_kernel, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL(fft2c_lds_kernel, dim3(batch), dim3(FFT_THREADS), lds, s, reinterpret_cast<const float2*>(in),
-                       reinterpret_cast<float2*>(out), H, W, inverse);
-    return ipdm_launch_status();
+    return fft_dispatch(fft_mixed(H, W), [&](auto mixed) {
+      constexpr bool MIXED = decltype(mixed)::value;
+      int rc = set_lds_limit(fft2c_lds_kernel<MIXED>, lds);
+      if (rc) return rc;
+      hipLaunchKernelGGL(fft2c_lds_kernel<MIXED>, dim3(batch), dim3(FFT_THREADS), lds, s, reinterpret_cast<const float2*>(in),
+                         reinterpret_cast<float2*>(out), H, W, inverse);
+      return ipdm_launch_status();
+    });
   }
   if (ipdm_kspace_large::large_ok(H, W))
     return ipdm_kspace_large::fft2c(reinterpret_cast<const float2*>(in), reinterpret_cast<float2*>(out), batch, H, W,
@@ -473,12 +487,15 @@ static int sense_forward_impl(const float* x, const SenseProblem<SensT>& pb, flo
                                             ipdm_stream(stream));
   if (!lds_fft_ok(pb.H, pb.W)) return IPDM_EUNSUPPORTED;
   size_t lds = lds_bytes(pb.H, pb.W);
-  int rc = set_lds_limit(sense_forward_kernel<SensT>, lds);
-  if (rc) return rc;
-  hipLaunchKernelGGL(sense_forward_kernel<SensT>, dim3(pb.B, pb.n_coils), dim3(FFT_THREADS), lds, ipdm_stream(stream),
-                     reinterpret_cast<const float2*>(x), pb.sens, pb.mask, pb.mask_t, reinterpret_cast<float2*>(y), pb.B, pb.H,
-                     pb.W);
-  return ipdm_launch_status();
+  return fft_dispatch(fft_mixed(pb.H, pb.W), [&](auto mixed) {
+    constexpr bool MIXED = decltype(mixed)::value;
+    int rc = set_lds_limit(sense_forward_kernel<SensT, MIXED>, lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL((sense_forward_kernel<SensT, MIXED>), dim3(pb.B, pb.n_coils), dim3(FFT_THREADS), lds, ipdm_stream(stream),
+                       reinterpret_cast<const float2*>(x), pb.sens, pb.mask, pb.mask_t, reinterpret_cast<float2*>(y), pb.B, pb.H,
+                       pb.W);
+    return ipdm_launch_status();
+  });
 }
 
 // pb.y: the coil images s; pb.mask_t is looked at only with apply_mask
@@ -496,11 +513,14 @@ static int sense_adjoint_impl(SenseProblem<SensT> pb, int apply_mask, float* x, 
   }
   if (!lds_fft_ok(pb.H, pb.W)) return IPDM_EUNSUPPORTED;
   size_t lds = lds_bytes(pb.H, pb.W);
-  int rc = set_lds_limit(sense_adjoint_kernel<false, SensT>, lds);
-  if (rc) return rc;
-  hipLaunchKernelGGL((sense_adjoint_kernel<false, SensT>), dim3(pb.B), dim3(FFT_THREADS), lds, ipdm_stream(stream), pb.y, pb.sens,
-                     pb.mask, pb.mask_t, apply_mask, x, pb.B, pb.n_coils, pb.H, pb.W);
-  return ipdm_launch_status();
+  return fft_dispatch(fft_mixed(pb.H, pb.W), [&](auto mixed) {
+    constexpr bool MIXED = decltype(mixed)::value;
+    int rc = set_lds_limit(sense_adjoint_kernel<false, SensT, MIXED>, lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL((sense_adjoint_kernel<false, SensT, MIXED>), dim3(pb.B), dim3(FFT_THREADS), lds, ipdm_stream(stream), pb.y,
+                       pb.sens, pb.mask, pb.mask_t, apply_mask, x, pb.B, pb.n_coils, pb.H, pb.W);
+    return ipdm_launch_status();
+  });
 }
 
 extern "C" int ipdm_sense_forward_c64(const float* x, const float* sens, const uint8_t* mask, int mask_t, float* y,
@@ -538,11 +558,15 @@ extern "C" int ipdm_sense_ssos_c64(const float* s, float* out, float* workspace,
   }
   if (!lds_fft_ok(H, W)) return IPDM_EUNSUPPORTED;
   size_t lds = lds_bytes(H, W);
-  int rc = set_lds_limit(sense_adjoint_kernel<true, float>, lds);
-  if (rc) return rc;
-  hipLaunchKernelGGL((sense_adjoint_kernel<true, float>), dim3(B), dim3(FFT_THREADS), lds, ipdm_stream(stream),
-                     reinterpret_cast<const float2*>(s), static_cast<const float*>(nullptr), nullptr, 1, 0, out, B, n_coils, H, W);
-  return ipdm_launch_status();
+  return fft_dispatch(fft_mixed(H, W), [&](auto mixed) {
+    constexpr bool MIXED = decltype(mixed)::value;
+    int rc = set_lds_limit(sense_adjoint_kernel<true, float, MIXED>, lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL((sense_adjoint_kernel<true, float, MIXED>), dim3(B), dim3(FFT_THREADS), lds, ipdm_stream(stream),
+                       reinterpret_cast<const float2*>(s), static_cast<const float*>(nullptr), nullptr, 1, 0, out, B, n_coils, H,
+                       W);
+    return ipdm_launch_status();
+  });
 }
 
 // x_re / x_im hold z (Langevin pending when lg.g_re) and receive the proximal
@@ -554,16 +578,21 @@ static int sense_step(float* x_re, float* x_im, const LangevinArgs& lg, const Se
   if (!lds_fft_ok(pb.H, pb.W)) return IPDM_EUNSUPPORTED;
   if (sense_coil_parallel()) return launch_sense_step_coils(x_re, x_im, lg, pb, coef, wk, st);
   const size_t lds = lds_bytes(pb.H, pb.W);
-  if (lg.g_re) {
-    int rc = set_lds_limit(ald_sense_step_kernel<true, SensT>, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL((ald_sense_step_kernel<true, SensT>), dim3(pb.B), dim3(FFT_THREADS), lds, st, x_re, x_im, lg, pb, coef, wk);
-  } else {
-    int rc = set_lds_limit(ald_sense_step_kernel<false, SensT>, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL((ald_sense_step_kernel<false, SensT>), dim3(pb.B), dim3(FFT_THREADS), lds, st, x_re, x_im, lg, pb, coef, wk);
-  }
-  return ipdm_launch_status();
+  return fft_dispatch(fft_mixed(pb.H, pb.W), [&](auto mixed) {
+    constexpr bool MIXED = decltype(mixed)::value;
+    if (lg.g_re) {
+      int rc = set_lds_limit(ald_sense_step_kernel<true, SensT, MIXED>, lds);
+      if (rc) return rc;
+      hipLaunchKernelGGL((ald_sense_step_kernel<true, SensT, MIXED>), dim3(pb.B), dim3(FFT_THREADS), lds, st, x_re, x_im, lg, pb,
+                         coef, wk);
+    } else {
+      int rc = set_lds_limit(ald_sense_step_kernel<false, SensT, MIXED>, lds);
+      if (rc) return rc;
+      hipLaunchKernelGGL((ald_sense_step_kernel<false, SensT, MIXED>), dim3(pb.B), dim3(FFT_THREADS), lds, st, x_re, x_im, lg, pb,
+                         coef, wk);
+    }
+    return ipdm_launch_status();
+  });
 }
 
 template <typename SensT>
@@ -629,16 +658,21 @@ static int singlecoil_step(float* x_re, float* x_im, const LangevinArgs& lg, con
   }
   if (!lds_fft_ok(pb.H, pb.W)) return IPDM_EUNSUPPORTED;
   const size_t lds = lds_bytes(pb.H, pb.W);
-  if (lg.g_re) {
-    int rc = set_lds_limit(ald_singlecoil_step_kernel<true>, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL(ald_singlecoil_step_kernel<true>, dim3(pb.B), dim3(FFT_THREADS), lds, st, x_re, x_im, lg, pb, coef, mode);
-  } else {
-    int rc = set_lds_limit(ald_singlecoil_step_kernel<false>, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL(ald_singlecoil_step_kernel<false>, dim3(pb.B), dim3(FFT_THREADS), lds, st, x_re, x_im, lg, pb, coef, mode);
-  }
-  return ipdm_launch_status();
+  return fft_dispatch(fft_mixed(pb.H, pb.W), [&](auto mixed) {
+    constexpr bool MIXED = decltype(mixed)::value;
+    if (lg.g_re) {
+      int rc = set_lds_limit(ald_singlecoil_step_kernel<true, MIXED>, lds);
+      if (rc) return rc;
+      hipLaunchKernelGGL((ald_singlecoil_step_kernel<true, MIXED>), dim3(pb.B), dim3(FFT_THREADS), lds, st, x_re, x_im, lg, pb, coef,
+                         mode);
+    } else {
+      int rc = set_lds_limit(ald_singlecoil_step_kernel<false, MIXED>, lds);
+      if (rc) return rc;
+      hipLaunchKernelGGL((ald_singlecoil_step_kernel<false, MIXED>), dim3(pb.B), dim3(FFT_THREADS), lds, st, x_re, x_im, lg, pb, coef,
+                         mode);
+    }
+    return ipdm_launch_status();
+  });
 }
 
 extern "C" int ipdm_singlecoil_prox_f32(const float* z_re, const float* z_im, const float* y, const uint8_t* mask,

@@ -1,6 +1,8 @@
 // Shared device code of the k-space kernels (kspace.hip: whole image in one CU's LDS; kspace_large.hip: row / column
-// passes for images beyond the LDS): radix-4/2 Stockham FFT over lines held in LDS, sign and mask helpers.
+// passes for images beyond the LDS): mixed-radix (4/2, then 3, then 5) Stockham FFT over lines held in LDS, the served
+// sizes, sign and mask helpers.
 #pragma once
+#include <type_traits>
 #include "ipdm_common.h"
 
 namespace ipdm_kspace {
@@ -13,7 +15,10 @@ __device__ __forceinline__ float2 cmul(float2 a, float2 b) {
   return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
 }
 
-// LDS image + twiddle table.  tw[q] = exp(-2*pi*i*q/twN), twN = max(H, W).
+// LDS image + twiddle table.  tw[q] = exp(-2*pi*i*q/twN); twN is a common multiple of every line length transformed with
+// the table: lcm(H, W) for a whole image (max(H, W) when one side divides the other, as with powers of two), the line
+// length for a strip.  A stage's phase k*t/(Ns*R) is then the exact table index k*t*twN/(Ns*R): Ns*R divides the line
+// length, and k < Ns, t < R keeps the index below twN.
 struct FftLds {
   float2* buf;
   float2* tw;
@@ -31,7 +36,10 @@ __device__ __forceinline__ void fft_make_twiddles(const FftLds& L) {
 // One in-place Stockham stage of radix R over `nlines` lines of length N.
 //   element (line, n) lives at buf[line*ls + n*es];  lines_fast: consecutive threads -> consecutive lines.
 // Every thread reads all its butterflies, the workgroup barriers, then everyone writes.
-template <int R>
+// MIXED (here and below): the line length may hold factors 3 and 5.  It is a template flag, chosen at launch, because the
+// power-of-two kernels must keep their code: with the radix-3 / 5 stages behind a run-time branch they took 6 to 10 more
+// VGPRs and the kernels at the 128-VGPR cap three times the scratch.  MIXED = false is the code they always had.
+template <int R, bool MIXED>
 __device__ __forceinline__ void fft_stage(const FftLds& L, int N, int Ns, int es, int ls, int nlines, bool lines_fast,
                                           bool inverse) {
   constexpr int BPT = FFT_EPT / R;             // butterflies per thread at the largest image
@@ -48,13 +56,16 @@ __device__ __forceinline__ void fft_stage(const FftLds& L, int N, int Ns, int es
       int line, j;
       if (lines_fast) { j = i / nlines; line = i - j * nlines; }
       else { line = i / nb; j = i - line * nb; }
-      int k = j & (Ns - 1);
+      int k;                                     // j mod Ns; Ns is a power of two while the radix-4 / 2 stages run
+      if constexpr (R == 2 || R == 4) k = j & (Ns - 1);
+      else k = j % Ns;
+      const int kt = k * twstep;                 // MIXED: the phase index of t = 1; k < Ns, so kt * t < twN (not a power of two)
       int base = line * ls;
 #pragma unroll
       for (int t = 0; t < R; ++t) {
         float2 x = L.buf[base + (j + t * nb) * es];
         if (t > 0) {
-          float2 w = L.tw[(k * t * twstep) & (L.twN - 1)];
+          float2 w = L.tw[MIXED ? kt * t : (k * t * twstep) & (L.twN - 1)];
           if (inverse) w.y = -w.y;
           x = cmul(x, w);
         }
@@ -65,6 +76,38 @@ __device__ __forceinline__ void fft_stage(const FftLds& L, int N, int Ns, int es
         float2 a = v[u][0], b = v[u][1];
         v[u][0] = make_float2(a.x + b.x, a.y + b.y);
         v[u][1] = make_float2(a.x - b.x, a.y - b.y);
+      } else if constexpr (R == 3) {
+        // X0 = a + (b + c);  X1, X2 = a - (b + c)/2 -+ i*sin(2pi/3)*(b - c)   (forward; the inverse swaps the two)
+        constexpr float S3 = 0.86602540378443864676f;            // sqrt(3)/2
+        float2 a = v[u][0], b = v[u][1], c = v[u][2];
+        float2 t1 = make_float2(b.x + c.x, b.y + c.y);
+        float2 t2 = make_float2(a.x - 0.5f * t1.x, a.y - 0.5f * t1.y);
+        float2 t3 = make_float2(S3 * (b.x - c.x), S3 * (b.y - c.y));
+        // forward: -i*t3 = (t3.y, -t3.x); inverse: +i*t3
+        float2 jt = inverse ? make_float2(-t3.y, t3.x) : make_float2(t3.y, -t3.x);
+        v[u][0] = make_float2(a.x + t1.x, a.y + t1.y);
+        v[u][1] = make_float2(t2.x + jt.x, t2.y + jt.y);
+        v[u][2] = make_float2(t2.x - jt.x, t2.y - jt.y);
+      } else if constexpr (R == 5) {
+        // with w = exp(-2pi*i/5):  X1, X4 = m1 -+ i*n1,  X2, X3 = m2 -+ i*n2   (forward; the inverse swaps each pair)
+        constexpr float C1 = 0.30901699437494742410f;            // cos(2pi/5)
+        constexpr float C2 = -0.80901699437494742410f;           // cos(4pi/5)
+        constexpr float S1 = 0.95105651629515357212f;            // sin(2pi/5)
+        constexpr float S2 = 0.58778525229247312917f;            // sin(4pi/5)
+        float2 a = v[u][0], b = v[u][1], c = v[u][2], d = v[u][3], e = v[u][4];
+        float2 t1 = make_float2(b.x + e.x, b.y + e.y), t3 = make_float2(b.x - e.x, b.y - e.y);
+        float2 t2 = make_float2(c.x + d.x, c.y + d.y), t4 = make_float2(c.x - d.x, c.y - d.y);
+        float2 m1 = make_float2(a.x + C1 * t1.x + C2 * t2.x, a.y + C1 * t1.y + C2 * t2.y);
+        float2 m2 = make_float2(a.x + C2 * t1.x + C1 * t2.x, a.y + C2 * t1.y + C1 * t2.y);
+        float2 n1 = make_float2(S1 * t3.x + S2 * t4.x, S1 * t3.y + S2 * t4.y);
+        float2 n2 = make_float2(S2 * t3.x - S1 * t4.x, S2 * t3.y - S1 * t4.y);
+        float2 j1 = inverse ? make_float2(-n1.y, n1.x) : make_float2(n1.y, -n1.x);
+        float2 j2 = inverse ? make_float2(-n2.y, n2.x) : make_float2(n2.y, -n2.x);
+        v[u][0] = make_float2(a.x + t1.x + t2.x, a.y + t1.y + t2.y);
+        v[u][1] = make_float2(m1.x + j1.x, m1.y + j1.y);
+        v[u][2] = make_float2(m2.x + j2.x, m2.y + j2.y);
+        v[u][3] = make_float2(m2.x - j2.x, m2.y - j2.y);
+        v[u][4] = make_float2(m1.x - j1.x, m1.y - j1.y);
       } else {
         float2 a = v[u][0], b = v[u][1], c = v[u][2], d = v[u][3];
         float2 apc = make_float2(a.x + c.x, a.y + c.y), amc = make_float2(a.x - c.x, a.y - c.y);
@@ -89,20 +132,44 @@ __device__ __forceinline__ void fft_stage(const FftLds& L, int N, int Ns, int es
   __syncthreads();
 }
 
+template <bool MIXED>
 __device__ __forceinline__ void fft_lines(const FftLds& L, int N, int es, int ls, int nlines, bool lines_fast,
                                           bool inverse) {
   int Ns = 1;
-  while (Ns * 4 <= N) {
-    fft_stage<4>(L, N, Ns, es, ls, nlines, lines_fast, inverse);
-    Ns *= 4;
+  if constexpr (!MIXED) {
+    while (Ns * 4 <= N) {
+      fft_stage<4, false>(L, N, Ns, es, ls, nlines, lines_fast, inverse);
+      Ns *= 4;
+    }
+    if (Ns < N) fft_stage<2, false>(L, N, Ns, es, ls, nlines, lines_fast, inverse);
+  } else {
+    // N = 2^a 3^b 5^c, factored here.  The radix-4 / 2 stages run first, so Ns is a power of two for all of them and their
+    // index arithmetic is that of a power-of-two line; the radix-3 and radix-5 stages follow with Ns = 2^a 3^i (5^j).
+    const int p2 = N & -N;                       // 2^a
+    while (Ns * 4 <= p2) {
+      fft_stage<4, true>(L, N, Ns, es, ls, nlines, lines_fast, inverse);
+      Ns *= 4;
+    }
+    if (Ns < p2) {
+      fft_stage<2, true>(L, N, Ns, es, ls, nlines, lines_fast, inverse);
+      Ns *= 2;
+    }
+    while ((N / Ns) % 3 == 0) {
+      fft_stage<3, true>(L, N, Ns, es, ls, nlines, lines_fast, inverse);
+      Ns *= 3;
+    }
+    while (Ns < N) {
+      fft_stage<5, true>(L, N, Ns, es, ls, nlines, lines_fast, inverse);
+      Ns *= 5;
+    }
   }
-  if (Ns < N) fft_stage<2>(L, N, Ns, es, ls, nlines, lines_fast, inverse);
 }
 
 // plain (uncentred, unnormalised) 2-D FFT of buf[H][W]; caller applies the (-1)^(r+c) flips and 1/sqrt(HW).
+template <bool MIXED>
 __device__ __forceinline__ void fft2_lds(const FftLds& L, int H, int W, bool inverse) {
-  fft_lines(L, W, 1, W, H, false, inverse);   // along rows
-  fft_lines(L, H, W, 1, W, true, inverse);    // along columns
+  fft_lines<MIXED>(L, W, 1, W, H, false, inverse);   // along rows
+  fft_lines<MIXED>(L, H, W, 1, W, true, inverse);    // along columns
 }
 
 __device__ __forceinline__ float sign_rc(int r, int c) { return ((r + c) & 1) ? -1.f : 1.f; }
@@ -133,10 +200,50 @@ __device__ __forceinline__ float2 sens_mul_conj(float2 v, float g, float2 s) {
 }
 
 __host__ __device__ __forceinline__ bool is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
-static inline bool lds_fft_ok(int H, int W) {
-  return is_pow2(H) && is_pow2(W) && H >= 4 && W >= 4 && (int64_t)H * W <= FFT_MAX_ELEMS;
+// A side the FFT serves: a power of two from 4, or 2^a 3^b 5^c with a >= 4 (a multiple of 16: the (-1)^(r+c) folding of
+// fftshift needs a multiple of 4, the score networks halve the image three times) between 16 and FFT_MAX_SIDE.
+constexpr int FFT_MAX_SIDE = 2048;
+__host__ __device__ __forceinline__ bool fft_side_ok(int n) {
+  if (n < 4) return false;
+  if (is_pow2(n)) return true;
+  if (n % 16 != 0 || n > FFT_MAX_SIDE) return false;
+  while (n % 2 == 0) n /= 2;
+  while (n % 3 == 0) n /= 3;
+  while (n % 5 == 0) n /= 5;
+  return n == 1;
 }
-static inline size_t lds_bytes(int H, int W) { return ((size_t)H * W + (size_t)(H > W ? H : W)) * sizeof(float2); }
+// length of the whole-image twiddle table: lcm(H, W)
+__host__ __device__ __forceinline__ int fft_tw_len(int H, int W) {
+  int a = H, b = W;
+  while (b) {
+    const int t = a % b;
+    a = b;
+    b = t;
+  }
+  return H / a * W;
+}
+// fft_stage<R> gives a thread FFT_EPT / R butterflies, rounded down: 4 of radix 4, 8 of radix 2, 5 of radix 3, 3 of radix 5,
+// i.e. 16384 elements per stage for the radix-4 / 2 stages and 15360 for the radix-3 / 5 ones.  An image of two sides that
+// are multiples of 16 and that runs a radix-3 or radix-5 stage has H*W = 256 * m with m <= 64 holding a factor 3 or 5, so
+// m <= 60 and H*W <= 15360: covered, with nothing to spare at 96x160.  A power-of-two side of 4 or 8 beside a mixed side
+// escapes that argument in one pair, 8x2000 / 2000x8 (16000 pixels): lds_fft_ok refuses it, and as it is no larger than
+// 16384 pixels large_ok does too -- the one pair of served sides without a kernel.  (A strip of the row / column path
+// holds at most 8192 elements.)
+constexpr int FFT_MAX_ELEMS_R35 = (FFT_EPT / 3) * 3 * FFT_THREADS;
+static_assert(FFT_MAX_ELEMS_R35 == (FFT_EPT / 5) * 5 * FFT_THREADS && FFT_MAX_ELEMS_R35 == 15360, "radix-3 / 5 stage capacity");
+// launch-time choice of the MIXED instantiation: f(std::false_type) for power-of-two lines, f(std::true_type) otherwise
+template <class Fn>
+static inline int fft_dispatch(bool mixed, Fn&& f) {
+  return mixed ? f(std::true_type{}) : f(std::false_type{});
+}
+static inline bool fft_mixed(int H, int W) { return !(is_pow2(H) && is_pow2(W)); }
+static inline size_t lds_bytes(int H, int W) { return ((size_t)H * W + (size_t)fft_tw_len(H, W)) * sizeof(float2); }
+static inline bool lds_fft_ok(int H, int W) {
+  if (!fft_side_ok(H) || !fft_side_ok(W) || (int64_t)H * W > FFT_MAX_ELEMS) return false;
+  if (is_pow2(H) && is_pow2(W)) return true;
+  // the first fails for 8x2000 / 2000x8 alone; the second holds for every pair (the most: 8x1920, 15360 + 1920 values, 135 KiB)
+  return H * W <= FFT_MAX_ELEMS_R35 && lds_bytes(H, W) <= 160 * 1024;
+}
 
 
 // Sampling mask at k-space point (r, c) of image b, the only place the two layouts are told apart:
@@ -152,12 +259,12 @@ __device__ __forceinline__ bool mask_at(const uint8_t* mask, int mask_t, int b, 
 }
 
 // whole-image LDS kernels (kspace.hip, kspace_cg.hip): the image followed by the twiddle table in dynamic LDS
-#define FFT_LDS_SETUP(H, W)                                   \
+#define FFT_LDS_SETUP(H, W, MIXED)                            \
   extern __shared__ __align__(16) unsigned char smem_raw[];  \
   FftLds L;                                                   \
   L.buf = reinterpret_cast<float2*>(smem_raw);               \
   L.tw = L.buf + (size_t)(H) * (W);                          \
-  L.twN = (H) > (W) ? (H) : (W);                             \
+  L.twN = (MIXED) ? fft_tw_len((H), (W)) : ((H) > (W) ? (H) : (W)); \
   fft_make_twiddles(L);
 
 // ---- argument bundles, passed to kernels by value (like ConvArgs and the strip functors) ----------------------------------
@@ -299,7 +406,7 @@ static inline int set_lds_limit(K kernel, size_t bytes) {
 
 }  // namespace ipdm_kspace
 
-// row / column-pass operators for power-of-two images beyond the LDS (kspace_large.hip)
+// row / column-pass operators for images of served sides beyond the LDS (kspace_large.hip)
 namespace ipdm_kspace_large {
 bool large_ok(int H, int W);
 int64_t workspace_bytes(int B, int n_coils, int H, int W);

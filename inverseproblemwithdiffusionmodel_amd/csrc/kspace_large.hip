@@ -1,4 +1,4 @@
-// k-space operators for images that do not fit one CU's LDS (power-of-two sizes above 128x128, e.g. the 256x256 ACDC
+// k-space operators for images that do not fit one CU's LDS (served sides, kspace_fft.h, above 16384 pixels, e.g. the 256x256 ACDC
 // slices of the reference's real-data front end, helpers/load_data.py:274): the centred 2-D FFT runs as a ROW pass and a
 // COLUMN pass over 64 KiB strips held in LDS, with the operator's elementwise work fused into the loads / stores of the
 // passes and -- for the proximal operators -- the forward and the inverse column transform of a strip back to back in
@@ -18,7 +18,19 @@ constexpr int STRIP_ELEMS = 8192;                    // complex elements per wor
 constexpr int EPT = STRIP_ELEMS / FFT_THREADS;       // 8 elements per thread
 
 bool large_ok(int H, int W) {
-  return is_pow2(H) && is_pow2(W) && H >= 4 && W >= 4 && H <= 2048 && W <= 2048 && (int64_t)H * W > FFT_MAX_ELEMS;
+  return fft_side_ok(H) && fft_side_ok(W) && H <= FFT_MAX_SIDE && W <= FFT_MAX_SIDE && (int64_t)H * W > FFT_MAX_ELEMS;
+}
+// Lines per strip: the largest divisor of `lines` with at most STRIP_ELEMS elements, so every strip is full and the grid is
+// lines / strip_lines exactly (no ragged last strip).  Powers of two: min(lines, STRIP_ELEMS / len), which divides.  Other
+// served sides are multiples of 16 and len <= 2048, so a divisor >= 4 always fits (80x240: 20 rows of 34 that would fit;
+// 48x512: 128 columns of 170).  The kernels and their launches both call this; MIXED = false (both sides powers of two)
+// leaves the search out of the kernels that never need it.
+template <bool MIXED = true>
+__host__ __device__ __forceinline__ int strip_lines(int lines, int len) {
+  int s = lines < STRIP_ELEMS / len ? lines : STRIP_ELEMS / len;
+  if constexpr (MIXED)
+    while (lines % s) --s;
+  return s;
 }
 static inline size_t strip_lds_bytes(int n) { return ((size_t)STRIP_ELEMS + (size_t)n) * sizeof(float2); }
 
@@ -32,10 +44,11 @@ static inline size_t strip_lds_bytes(int n) { return ((size_t)STRIP_ELEMS + (siz
 
 // ---- generic passes ---------------------------------------------------------------------------------------------
 // F: load(b, coil, r, c) -> float2 and store(b, coil, r, c, v); rows [r0, r0 + RS) of image (b, coil)
-template <class F>
+// MIXED (all three strip kernels): a side with factors 3 or 5, kspace_fft.h; chosen at launch by fft_dispatch
+template <class F, bool MIXED>
 __global__ __launch_bounds__(FFT_THREADS) void rows_kernel(F f, int H, int W, int inverse) {
   STRIP_LDS_SETUP(W)
-  const int RS = min(H, STRIP_ELEMS / W);
+  const int RS = strip_lines<MIXED>(H, W);
   const int r0 = blockIdx.x * RS, b = blockIdx.y, coil = blockIdx.z;
   const int n = RS * W;
   for (int e = threadIdx.x; e < n; e += FFT_THREADS) {
@@ -43,7 +56,7 @@ __global__ __launch_bounds__(FFT_THREADS) void rows_kernel(F f, int H, int W, in
     L.buf[e] = f.load(b, coil, r0 + lr, c);
   }
   __syncthreads();
-  fft_lines(L, W, 1, W, RS, false, inverse != 0);
+  fft_lines<MIXED>(L, W, 1, W, RS, false, inverse != 0);
   for (int e = threadIdx.x; e < n; e += FFT_THREADS) {
     const int lr = e / W, c = e - lr * W;
     f.store(b, coil, r0 + lr, c, L.buf[e]);
@@ -53,10 +66,10 @@ __global__ __launch_bounds__(FFT_THREADS) void rows_kernel(F f, int H, int W, in
 // columns [c0, c0 + CS) of image (b, coil); LDS layout buf[r * CS + lc].  With TWO_WAY the strip is transformed forward,
 // F::mid is applied in place, and it is transformed back (inverse) before the store; F::skip lets a strip whose mid()
 // is identically zero bypass both transforms.
-template <class F, bool TWO_WAY>
+template <class F, bool TWO_WAY, bool MIXED>
 __global__ __launch_bounds__(FFT_THREADS) void cols_kernel(F f, int H, int W, int inverse) {
   STRIP_LDS_SETUP(H)
-  const int CS = min(W, STRIP_ELEMS / H);
+  const int CS = strip_lines<MIXED>(W, H);
   const int c0 = blockIdx.x * CS, b = blockIdx.y, coil = blockIdx.z;
   const int n = H * CS;
   if constexpr (TWO_WAY) {
@@ -73,14 +86,14 @@ __global__ __launch_bounds__(FFT_THREADS) void cols_kernel(F f, int H, int W, in
     L.buf[e] = f.load(b, coil, r, c0 + lc);
   }
   __syncthreads();
-  fft_lines(L, H, CS, 1, CS, true, TWO_WAY ? false : inverse != 0);
+  fft_lines<MIXED>(L, H, CS, 1, CS, true, TWO_WAY ? false : inverse != 0);
   if constexpr (TWO_WAY) {
     for (int e = threadIdx.x; e < n; e += FFT_THREADS) {
       const int r = e / CS, lc = e - r * CS;
       L.buf[e] = f.mid(b, coil, r, c0 + lc, L.buf[e]);
     }
     __syncthreads();
-    fft_lines(L, H, CS, 1, CS, true, true);
+    fft_lines<MIXED>(L, H, CS, 1, CS, true, true);
   }
   for (int e = threadIdx.x; e < n; e += FFT_THREADS) {
     const int r = e / CS, lc = e - r * CS;
@@ -206,7 +219,7 @@ enum { FIN_ADJOINT = 0, FIN_SSOS = 1, FIN_L2 = 2, FIN_REPLACE = 3 };
 // tmp[coil][b] rows -> inverse row FFT -> acc += sign*scale*S_c * v  (coil order) ->
 //   FIN_ADJOINT: out_c[b] = acc        FIN_SSOS: out_f[b] = sqrt(sum |scale*v|^2)
 //   FIN_L2: x = x - coef*acc (planar, in place)      FIN_REPLACE: x = acc (planar)
-template <int FIN, typename SensT>
+template <int FIN, typename SensT, bool MIXED>
 __global__ __launch_bounds__(FFT_THREADS) void rows_inv_accum_kernel(const float2* __restrict__ tmp,
                                                                      const SensT* __restrict__ sens, float2* out_c,
                                                                      float* out_f, float* x_re, float* x_im,
@@ -215,7 +228,7 @@ __global__ __launch_bounds__(FFT_THREADS) void rows_inv_accum_kernel(const float
   STRIP_LDS_SETUP(W)
   coef = sched_coef(sched, coef);
   const ImgGeo g{B, H, W};
-  const int RS = min(H, STRIP_ELEMS / W);
+  const int RS = strip_lines<MIXED>(H, W);
   const int r0 = blockIdx.x * RS, b = blockIdx.y;
   const int n = RS * W;
   const float scale = rsqrtf((float)H * (float)W);
@@ -232,7 +245,7 @@ __global__ __launch_bounds__(FFT_THREADS) void rows_inv_accum_kernel(const float
       }
     }
     __syncthreads();
-    fft_lines(L, W, 1, W, RS, false, true);
+    fft_lines<MIXED>(L, W, 1, W, RS, false, true);
 #pragma unroll
     for (int k = 0; k < EPT; ++k) {
       const int e = threadIdx.x + k * FFT_THREADS;
@@ -280,7 +293,7 @@ __global__ __launch_bounds__(256) void langevin_planes_kernel(float* x_re, float
   const float* __restrict__ n_re = lg.n_re;
   const float* __restrict__ n_im = lg.n_im;
   const int b = blockIdx.y;
-  const int quads = HW / 4;                                    // HW is a multiple of 4 (power-of-two images)
+  const int quads = HW / 4;                                    // HW is a multiple of 4 (of 16, for every served size)
   // float4 access only where all the caller's planes sit on 16-byte boundaries; otherwise element by element (same
   // arithmetic, same Philox quad per four elements)
   const bool aligned = ((reinterpret_cast<uintptr_t>(x_re) | reinterpret_cast<uintptr_t>(x_im) | reinterpret_cast<uintptr_t>(g_re) |
@@ -333,21 +346,27 @@ static int set_lds(K kernel, size_t bytes) {
 template <class F>
 static int launch_rows(const F& f, int B, int coils, int H, int W, int inverse, hipStream_t s) {
   const size_t lds = strip_lds_bytes(W);
-  int rc = set_lds(rows_kernel<F>, lds);
-  if (rc) return rc;
-  const int RS = H < STRIP_ELEMS / W ? H : STRIP_ELEMS / W;
-  hipLaunchKernelGGL(rows_kernel<F>, dim3(H / RS, B, coils), dim3(FFT_THREADS), lds, s, f, H, W, inverse);
-  return ipdm_launch_status();
+  const int RS = strip_lines(H, W);
+  return fft_dispatch(fft_mixed(H, W), [&](auto mixed) {
+    constexpr bool MIXED = decltype(mixed)::value;
+    int rc = set_lds(rows_kernel<F, MIXED>, lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL((rows_kernel<F, MIXED>), dim3(H / RS, B, coils), dim3(FFT_THREADS), lds, s, f, H, W, inverse);
+    return ipdm_launch_status();
+  });
 }
 
 template <class F, bool TWO_WAY>
 static int launch_cols(const F& f, int B, int coils, int H, int W, int inverse, hipStream_t s) {
   const size_t lds = strip_lds_bytes(H);
-  int rc = set_lds(cols_kernel<F, TWO_WAY>, lds);
-  if (rc) return rc;
-  const int CS = W < STRIP_ELEMS / H ? W : STRIP_ELEMS / H;
-  hipLaunchKernelGGL((cols_kernel<F, TWO_WAY>), dim3(W / CS, B, coils), dim3(FFT_THREADS), lds, s, f, H, W, inverse);
-  return ipdm_launch_status();
+  const int CS = strip_lines(W, H);
+  return fft_dispatch(fft_mixed(H, W), [&](auto mixed) {
+    constexpr bool MIXED = decltype(mixed)::value;
+    int rc = set_lds((cols_kernel<F, TWO_WAY, MIXED>), lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL((cols_kernel<F, TWO_WAY, MIXED>), dim3(W / CS, B, coils), dim3(FFT_THREADS), lds, s, f, H, W, inverse);
+    return ipdm_launch_status();
+  });
 }
 
 // tmp: pb.n_coils * pb.B column-transformed images; the coil sum weighted by pb.sens (NULL: unweighted)
@@ -355,12 +374,15 @@ template <int FIN, typename SensT>
 static int launch_accum(const float2* tmp, const SenseProblem<SensT>& pb, float2* out_c, float* out_f, float* x_re, float* x_im,
                         const ipdm_sched_t* sched, float coef, hipStream_t s) {
   const size_t lds = strip_lds_bytes(pb.W);
-  int rc = set_lds(rows_inv_accum_kernel<FIN, SensT>, lds);
-  if (rc) return rc;
-  const int RS = pb.H < STRIP_ELEMS / pb.W ? pb.H : STRIP_ELEMS / pb.W;
-  hipLaunchKernelGGL((rows_inv_accum_kernel<FIN, SensT>), dim3(pb.H / RS, pb.B), dim3(FFT_THREADS), lds, s, tmp, pb.sens, out_c,
-                     out_f, x_re, x_im, sched, coef, pb.B, pb.n_coils, pb.H, pb.W);
-  return ipdm_launch_status();
+  const int RS = strip_lines(pb.H, pb.W);
+  return fft_dispatch(fft_mixed(pb.H, pb.W), [&](auto mixed) {
+    constexpr bool MIXED = decltype(mixed)::value;
+    int rc = set_lds((rows_inv_accum_kernel<FIN, SensT, MIXED>), lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL((rows_inv_accum_kernel<FIN, SensT, MIXED>), dim3(pb.H / RS, pb.B), dim3(FFT_THREADS), lds, s, tmp, pb.sens,
+                       out_c, out_f, x_re, x_im, sched, coef, pb.B, pb.n_coils, pb.H, pb.W);
+    return ipdm_launch_status();
+  });
 }
 
 int64_t workspace_bytes(int B, int n_coils, int H, int W) {

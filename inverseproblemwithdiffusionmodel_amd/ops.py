@@ -130,6 +130,18 @@ def fused_bias_act_raw(x, bias, ref, act, grad, alpha, scale):
 
 
 # ---- k-space --------------------------------------------------------------------------------
+KSPACE_NONE, KSPACE_LDS, KSPACE_STRIPS = 0, 1, 2
+KSPACE_SIZE_RULE = ("each side a power of two from 4, or a multiple of 16 of the form 2^a 3^b 5^c between 16 and 2048 "
+                    "(e.g. 48, 80, 96, 144, 160, 192, 240, 288, 320, 384)")
+
+
+def kspace_size_class(H, W):
+    """which k-space kernels serve an H x W image (KSPACE_SIZE_RULE): KSPACE_NONE (0) no kernel -- the SENSE, single-coil
+    and CG operators raise IpdmUnsupported --, KSPACE_LDS (1) whole image in LDS (H*W <= 16384), KSPACE_STRIPS (2) row /
+    column strips.  Needs no GPU."""
+    return int(_lib.lib.ipdm_kspace_size_class(int(H), int(W)))
+
+
 def fft2c(x, inverse=False):
     x = _gpu(x, name="input")
     if x.dtype != torch.complex64:

@@ -40,7 +40,10 @@ if __name__ == '__main__':
     parser.add_argument("--ds_idx", type=int, default=0)
     parser.add_argument("--save_dir", default="../outputs")
     # extras
-    parser.add_argument("--image_size", type=int, default=128)
+    parser.add_argument("--image_size", type=int, default=128, help="image height (and width, without --image_width)")
+    parser.add_argument("--image_width", type=int, default=None,
+                        help="image width (default: --image_size); sides: powers of two, or multiples of 16 of the form "
+                             "2^a 3^b 5^c up to 2048, e.g. 96, 144, 160, 192, 240, 288, 320, 384")
     parser.add_argument("--ckpt", default=None, help="Lightning .ckpt of the reference (EMA weights); default: synthetic")
     parser.add_argument("--n_levels", type=int, default=None, help="run only the first n noise levels")
     parser.add_argument("--seg_ckpt", default=None, help="Lightning TrainSeg .ckpt (MONAI UNet weights) for the guidance")
@@ -60,11 +63,15 @@ if __name__ == '__main__':
               "(guidance off); pass --seg_synthetic to exercise the path with random weights")
         args_dict["seg_start_time"] = 1.
 
+    H = args_dict["image_size"]
+    W = args_dict["image_width"] if args_dict["image_width"] is not None else H
+    from inverseproblemwithdiffusionmodel_amd import ops
+    if ops.kspace_size_class(H, W) == ops.KSPACE_NONE:                    # before any allocation
+        sys.exit(f"--image_size {H} --image_width {W}: no k-space kernel for {H}x{W}; {ops.KSPACE_SIZE_RULE}")
     from inverseproblemwithdiffusionmodel_amd import engine, sharding
     world, rank, device = sharding.init_distributed()
     from inverseproblemwithdiffusionmodel_amd.helpers.load_model import load_scorenet_weights
 
-    H = args_dict["image_size"]
     total = args_dict["num_samples"]
     lo, hi = sharding.shard_range(total, world, rank)
     n_local = max(hi - lo, 1)                 # a rank without samples still runs one (discarded) to keep collectives aligned
@@ -80,10 +87,10 @@ if __name__ == '__main__':
         args_dict["num_sens"] = sens_maps.shape[0]
     elif args_dict["sens_phase"]:
         from inverseproblemwithdiffusionmodel_amd.synthetic import complex_coil_maps
-        sens_maps = complex_coil_maps(args_dict["num_sens"], H, H, args_dict["seed"])
+        sens_maps = complex_coil_maps(args_dict["num_sens"], H, W, args_dict["seed"])
     from inverseproblemwithdiffusionmodel_amd.helpers.load_data import driver_mask
-    mask = driver_mask(args_dict["mask"], args_dict["mask_2d"], H, H, args_dict["R"], args_dict["seed"])
-    prob = engine.build_problem(device, n_local, R=args_dict["R"], H=H, W=H, num_sens=args_dict["num_sens"],
+    mask = driver_mask(args_dict["mask"], args_dict["mask_2d"], H, W, args_dict["R"], args_dict["seed"])
+    prob = engine.build_problem(device, n_local, R=args_dict["R"], H=H, W=W, num_sens=args_dict["num_sens"],
                                 seed=args_dict["seed"], scorenet=scorenet, cfg=cfg, lr_scaled=args_dict["lr_scaled"],
                                 sens_maps=sens_maps, mask=mask, proximal=args_dict["proximal_type"],
                                 proximal_kwargs=(dict(max_iter=args_dict["cg_iters"], tol=args_dict["cg_tol"])

@@ -39,7 +39,10 @@ if __name__ == '__main__':
     parser.add_argument("--lamda_T", type=float, default=10.)
     parser.add_argument("--if_random_shift", action="store_true")
     parser.add_argument("--save_dir", default="../outputs")
-    parser.add_argument("--image_size", type=int, default=128)
+    parser.add_argument("--image_size", type=int, default=128, help="image height (and width, without --image_width)")
+    parser.add_argument("--image_width", type=int, default=None,
+                        help="image width (default: --image_size); sides: powers of two, or multiples of 16 of the form "
+                             "2^a 3^b 5^c up to 2048, e.g. 96, 144, 160, 192, 240, 288, 320, 384")
     parser.add_argument("--T", type=int, default=24)
     parser.add_argument("--n_levels", type=int, default=None)
     parser.add_argument("--start_level", type=int, default=0, help="first noise level (with --n_levels: a slice of the schedule)")
@@ -53,6 +56,10 @@ if __name__ == '__main__':
     parser.add_argument("--mask_2d", action="store_true",
                         help="synthetic variable-density 2-D (ky, kz) sampling mask at --R instead of the line mask")
     a = parser.parse_args()
+    H, W = a.image_size, a.image_size if a.image_width is None else a.image_width
+    from inverseproblemwithdiffusionmodel_amd import ops
+    if ops.kspace_size_class(H, W) == ops.KSPACE_NONE:                    # before any allocation
+        sys.exit(f"--image_size {H} --image_width {W}: no k-space kernel for {H}x{W}; {ops.KSPACE_SIZE_RULE}")
     from inverseproblemwithdiffusionmodel_amd.helpers.load_model import reload_model
     from inverseproblemwithdiffusionmodel_amd.ncsn.models import get_sigmas
     from inverseproblemwithdiffusionmodel_amd.ncsn.models.ALD_optimizers import ALD2DTime
@@ -65,7 +72,6 @@ if __name__ == '__main__':
     lo, hi = sharding.shard_range(a.num_samples, world, rank)
     n_local = max(hi - lo, 1)                 # a rank without samples still runs one (discarded): collectives stay aligned
     np.random.seed(a.seed)                    # if_random_shift: one shift per step for the whole batch, on every rank
-    H = W = a.image_size
     scorenet = reload_model("Diffusion", "CINE127", device=device)
     scorenet_T = reload_model(a.temporal_type, "CINE127", device=device)
     sigmas = get_sigmas(scorenet.config, "recons")
