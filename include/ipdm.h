@@ -27,6 +27,7 @@
 #ifndef IPDM_H
 #define IPDM_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -250,6 +251,31 @@ int ipdm_ald_sense_cg_step_csm_f32(float* x_re, float* x_im, const float* g_re, 
                                    const ipdm_sched_t* dev_sched, const float* y, const float* sens, const uint8_t* mask,
                                    int mask_t, float coef, float* work, const float* ahy, int max_iter, float tol,
                                    int32_t* iters_out, int B, int n_coils, int H, int W, void* stream);
+
+/* Coil sensitivity maps estimated from the fully sampled calibration region of the measurement itself (Walsh's adaptive
+ * estimator on low-resolution calibration images; the reference only synthesises maps, undersampling_fourier.py:124-138).
+ *   y [n_coils][B][H][W] c64, the measurement layout of the SENSE operators (centred, orthonormal scale)
+ *   (ah, aw)   half-widths of the calibration box [H/2-ah, H/2+ah] x [W/2-aw, W/2+aw], inside the image
+ *   calibration images  c_j = ifft2c(w_H (x) w_W . y_j),  w(k) = 0.5 + 0.5 cos(pi (k - N/2) / (a + 1)) in the box, 0 outside
+ *   support    rss(x) = sqrt(sum_j |c_j(x)|^2) > thresh * rss_max[b]   (strict; rss_max[b] the maximum over image b)
+ *   maps       the dominant eigenvector of R(x) = sum over the (2 radius + 1)^2 neighbourhood of c(x') c(x')^H (neighbours
+ *              outside the image contribute zero), by power iteration from v0 = normalise(R(x) 1) and power_iters further
+ *              applications v <- normalise(R(x) v); normalise divides by the 2-norm over the coils (by 1 where it is 0);
+ *              then rotated so that coil 0 is real and non-negative; 0 outside the support.
+ * radius 1..4, n_coils 1..32, sizes of ipdm_kspace_size_class LDS / STRIPS with sides up to 1024 (ipdm_fft2c_c64's limit)
+ * and n_coils * B <= 65535; otherwise IPDM_EUNSUPPORTED (ipdm_csm_supported tells, without a GPU).  IPDM_EINVAL: a box
+ * outside the image, radius outside 1..4, power_iters < 0, thresh negative or NaN, a NULL tensor.  fp32 arithmetic;
+ * asynchronous, allocation-free and hipGraph-capturable (rss_max is zeroed by a memset node of the call, then raised by one
+ * atomic max per wave on the bit pattern: exact, order-independent); an image's maps do not depend on its batch.  Every
+ * tensor may sit on any 8-byte boundary (rss, rss_max: 4). */
+size_t ipdm_csm_workspace_bytes(int B, int n_coils, int H, int W);   /* calibration images + rss plane; 0 when unserved */
+int ipdm_csm_supported(int n_coils, int radius, int H, int W);       /* 1 / 0, no GPU needed */
+/* the calibration images alone: calib [n_coils][B][H][W] c64, must not alias y */
+int ipdm_csm_calib_images_c64(const float* y, int ah, int aw, float* calib, int B, int n_coils, int H, int W, void* stream);
+int ipdm_csm_walsh_c64(const float* y, int ah, int aw, int radius, int power_iters, float thresh,
+                       float* maps /* [n_coils][B][H][W] c64 */, float* rss /* [B][H][W] or NULL */,
+                       float* rss_max /* [B] */, float* work /* ipdm_csm_workspace_bytes(B, n_coils, H, W) */, int B,
+                       int n_coils, int H, int W, void* stream);
 
 /* Single-coil data-consistency operators (A = M F, RandomUndersamplingFourier, no coil maps) on planar real/imag
  * float32 [B][H][W], y [B][H][W] complex64; out may alias z.  mode:

@@ -58,6 +58,10 @@ SIGNATURES = {
                                    P, P, P, c_int, c_float, P, P, c_int, c_float, P, c_int, c_int, c_int, c_int, P],
     "ipdm_ald_sense_cg_step_csm_f32": [P, P, P, P, P, P, c_float, c_float, c_uint64, c_int64, c_int64, P,
                                        P, P, P, c_int, c_float, P, P, c_int, c_float, P, c_int, c_int, c_int, c_int, P],
+    "ipdm_csm_workspace_bytes": [c_int, c_int, c_int, c_int],
+    "ipdm_csm_supported": [c_int, c_int, c_int, c_int],
+    "ipdm_csm_calib_images_c64": [P, c_int, c_int, P, c_int, c_int, c_int, c_int, P],
+    "ipdm_csm_walsh_c64": [P, c_int, c_int, c_int, c_int, c_float, P, P, P, P, c_int, c_int, c_int, c_int, P],
     "ipdm_singlecoil_prox_f32": [P, P, P, P, c_int, c_float, c_int, P, P, P, c_int, c_int, c_int, P],
     "ipdm_ald_singlecoil_step_f32": [P, P, P, P, P, P, c_float, c_float, c_uint64, c_int64, c_int64, P,
                                      P, P, c_int, c_float, c_int, P, c_int, c_int, c_int, P],
@@ -158,7 +162,7 @@ _RESTYPES = {"ipdm_build_arch": c_char_p, "ipdm_fft2c_workspace_bytes": c_int64,
              "ipdm_conv_bx3_weight_bytes": c_int64,
              "ipdm_conv_wino_bx3_weight_bytes": c_int64, "ipdm_conv_hx2_weight_bytes": c_int64,
              "ipdm_conv_wino_hx2_weight_bytes": c_int64, "ipdm_conv_wino1d_weight_bytes": c_int64, "ipdm_conv_wino1d_weight_bytes3d": c_int64,
-             "ipdm_conv1d_hx2_weight_bytes": c_int64}
+             "ipdm_conv1d_hx2_weight_bytes": c_int64, "ipdm_csm_workspace_bytes": ctypes.c_size_t}
 
 IPDM_EINVAL = -1
 IPDM_EUNSUPPORTED = -2

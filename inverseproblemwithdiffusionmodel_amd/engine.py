@@ -12,7 +12,7 @@ import torch
 from . import ops as ops_mod
 
 from .helpers.load_data import load_config
-from .ncsn.linear_transforms.undersampling_fourier import SENSE
+from .ncsn.linear_transforms.undersampling_fourier import SENSE, calibration_region
 from .ncsn.models import get_sigmas
 from .ncsn.models.ALD_optimizers import ALDInvSegProximalRealImag, SCHED_DTYPE, step_schedule
 from .ncsn.models.ncsnv2 import NCSNv2Deepest
@@ -56,29 +56,74 @@ def build_scorenet(cfg, seed=0):
 
 
 def build_problem(device, n_samples, R=40, H=128, W=128, num_sens=4, seed=0, scorenet=None, cfg=None, lr_scaled=1.0,
-                  sens_maps=None, proximal="L2Penalty", proximal_kwargs=None, mask=None):
+                  sens_maps=None, proximal="L2Penalty", proximal_kwargs=None, mask=None, estimate_maps=False, measurement=None,
+                  calib_max=12, kspace_scale=None):
     """-> Namespace(sampler, scorenet, sigmas, op, image, measurement, call_kwargs); sens_maps: measured coil maps
     (num_sens, H, W), real or complex, instead of the synthetic "exp" maps (RSS-normalised where non-zero); proximal: a
     get_proximal name ("L2PenaltyCG": the exact proximal, proximal_kwargs = dict(max_iter=, tol=)); mask: the sampling mask
-    of an acquisition, a line or 2-D mask (SENSE mask_mode="custom"), instead of the generated line mask at R"""
+    of an acquisition, a line or 2-D mask (SENSE mask_mode="custom"), instead of the generated line mask at R.
+    estimate_maps: the sampler runs on coil maps estimated from the measurement's calibration region
+    (SENSE.estimate_sens_maps, calib_max); without `measurement` the measurement is still simulated with the true maps.
+    measurement: measured k-space (n, H, W) instead of the simulated one: no phantom (image is None), maps from
+    sens_maps or estimated, the data multiplied by kspace_scale -- None: 1 / rss_max of its calibration image, since the
+    score prior expects magnitudes in [0, 1].  The Namespace then carries kspace_scale; estimated_maps is True when the
+    operator's maps were estimated."""
     prox_cls = get_proximal(proximal)                        # an unknown name fails here, before any GPU work
+    kspace_scale = None if kspace_scale is None else float(kspace_scale)
+    region = None
+    if measurement is not None:                              # host-side checks: all fail before any GPU work
+        if mask is None:
+            raise ValueError("build_problem(measurement=...): pass mask=, the sampling mask of the acquisition")
+        if (sens_maps is None) != bool(estimate_maps):
+            raise ValueError("build_problem(measurement=...): the coil maps come from sens_maps= or from estimate_maps=True")
+        measurement = torch.as_tensor(measurement)
+        if measurement.dim() != 3 or not measurement.is_complex() or tuple(measurement.shape[-2:]) != (H, W):
+            raise ValueError(f"build_problem: measurement {tuple(measurement.shape)} {measurement.dtype}; complex "
+                             f"(n_coils, {H}, {W}) expected")
+        num_sens = measurement.shape[0]
+        if estimate_maps or kspace_scale is None:
+            region = calibration_region(mask, H, W, calib_max)
     cfg = acdc_config(device, H) if cfg is None else cfg
     scorenet = build_scorenet(cfg, seed) if scorenet is None else scorenet
     sigmas = get_sigmas(cfg, "recons")
     mk = {} if mask is None else dict(mask_mode="custom", mask=mask)
-    if sens_maps is None:
-        op = SENSE("exp", num_sens, R, 0.04, (1, H, W), seed=seed, mask_T=1, **mk)
+    if measurement is not None:
+        img = None
+        y = measurement.to(torch.complex64).to(device).contiguous()
+        if region is not None:
+            # one call serves both uses: the maps (kept only with estimate_maps) and rss_max for the automatic scale; with
+            # sens_maps= given and no kspace_scale the maps are computed and dropped (a fraction of a millisecond, once)
+            maps, _, rss_max = ops_mod.estimate_sens_maps(y, *region, return_rss=True)
+            if kspace_scale is None:
+                peak = float(rss_max[0])
+                if not peak > 0.0:
+                    raise ValueError("build_problem: the measurement's calibration region holds no signal")
+                kspace_scale = 1.0 / peak
+        if estimate_maps:
+            op = SENSE("custom", num_sens, R, 0.04, (1, H, W), seed=seed, mask_T=1, sens_maps=maps.cpu(), normalize=False, **mk)
+        else:
+            op = SENSE("custom", num_sens, R, 0.04, (1, H, W), seed=seed, mask_T=1, sens_maps=sens_maps, **mk)
+        meas1 = (y * kspace_scale).reshape(num_sens, 1, 1, H, W)
     else:
-        op = SENSE("custom", num_sens, R, 0.04, (1, H, W), seed=seed, mask_T=1, sens_maps=sens_maps, **mk)
-    img = phantom_image(H, W, seed=seed).to(device)
-    meas = op(img).repeat(1, n_samples, 1, 1, 1).contiguous()
+        if sens_maps is None:
+            op = SENSE("exp", num_sens, R, 0.04, (1, H, W), seed=seed, mask_T=1, **mk)
+        else:
+            op = SENSE("custom", num_sens, R, 0.04, (1, H, W), seed=seed, mask_T=1, sens_maps=sens_maps, **mk)
+        if estimate_maps:                                    # host only: an unusable centre fails before the forward model runs
+            calibration_region(op.random_under_fourier.mask, H, W, calib_max)
+        img = phantom_image(H, W, seed=seed).to(device)
+        meas1 = op(img)
+        if estimate_maps:                                    # simulated with the true maps, reconstructed with the estimated ones
+            op = SENSE.from_measurement(meas1, op.random_under_fourier.mask, R=R, seed=seed, calib_max=calib_max)
+    meas = meas1.repeat(1, n_samples, 1, 1, 1).contiguous()
     params = dict(n_steps_each=cfg.sampling.n_steps_each, step_lr=cfg.sampling.step_lr, denoise=True,
                   final_only=True)
     sampler = ALDInvSegProximalRealImag(prox_cls(op, **(proximal_kwargs or {})), 1.0, "linear", (n_samples, 1, H, W), scorenet,
                                         sigmas, params, cfg, meas, op, seg=None, device=device)
     return Namespace(sampler=sampler, scorenet=scorenet, sigmas=sigmas, op=op, image=img, measurement=meas, cfg=cfg,
                      params=params, call_kwargs=dict(label=None, lamda=0.1, save_dir=None, lr_scaled=lr_scaled,
-                                                     seg_mode="full"))
+                                                     seg_mode="full"),
+                     estimated_maps=bool(estimate_maps), kspace_scale=kspace_scale)
 
 
 class IterationRunner:

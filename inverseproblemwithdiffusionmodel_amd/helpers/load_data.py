@@ -225,6 +225,28 @@ def load_sens_maps(path):
     return maps.to(torch.complex128 if maps.is_complex() else torch.float64)
 
 
+def load_kspace(path):
+    """measured multi-coil k-space (n_coils, H, W) from a ``.npy`` or ``.pt`` file -> host complex64 tensor, centred with
+    orthonormal scale as ``SENSE.__call__`` produces it (``engine.build_problem(measurement=...)``); any other rank or a
+    real dtype is a ValueError"""
+    import numpy as np
+    import torch
+    ext = os.path.splitext(str(path))[1].lower()
+    if ext == ".npy":
+        y = torch.from_numpy(np.load(path, allow_pickle=False))
+    elif ext == ".pt":
+        y = torch.load(path, map_location="cpu")
+        if isinstance(y, np.ndarray):
+            y = torch.from_numpy(y)
+    else:
+        raise ValueError(f"load_kspace: {path!r}: a .npy or .pt file")
+    if not isinstance(y, torch.Tensor) or y.dim() != 3:
+        raise ValueError(f"load_kspace: {path!r} must hold one array of shape (n_coils, H, W)")
+    if not y.is_complex():
+        raise ValueError(f"load_kspace: {path!r} holds {y.dtype}; complex k-space expected")
+    return y.to(torch.complex64).contiguous()
+
+
 def load_mask(path):
     """k-space sampling mask from a ``.npy`` or ``.pt`` file -> host tensor, dtype and shape as stored: a line mask
     ((W,), (1, 1, W), (T, 1, 1, W)) or a 2-D mask ((H, W), (1, 1, H, W), (T, 1, H, W)), bool, integer or real floating

@@ -37,6 +37,45 @@ def _check_gpu(t, what):
         raise RuntimeError(f"{what}: expected a GPU tensor (no CPU fallback in this build)")
 
 
+def calibration_region(mask, H, W, calib_max=12):
+    """-> (ah, aw), the half-widths of the calibration box [H//2-ah, H//2+ah] x [W//2-aw, W//2+aw] the coil-map estimator
+    works from: symmetric about DC, fully sampled in every frame of `mask` (any shape ``ops._mask_u8`` takes; a line mask
+    is fully sampled along H), each half-width at most min(N//2, N-1-N//2, calib_max).  Of the fully sampled candidates
+    the largest area wins; ties go to the smaller |ah - aw|, then to the larger aw.  ValueError, naming the sampled centre
+    it found, when ah < 2 or aw < 2 (the generated R = 40 line mask keeps the two adjacent centre lines W//2 - 1 and
+    W//2, so the box symmetric about W//2 has aw = 0 and the mask is refused this way).  Host only."""
+    if isinstance(calib_max, bool) or int(calib_max) != calib_max or calib_max < 0:
+        raise ValueError(f"calibration_region: calib_max must be an integer >= 0, got {calib_max}")
+    m = ops._mask_u8(mask, H, W, "cpu")
+    full = m.bool().all(dim=0)                                  # every frame must have sampled the box
+    if full.dim() == 1:                                         # a line mask [W]: every row is sampled
+        full = full.reshape(1, W).expand(H, W)
+    full = full.numpy()
+    # prefix sums: box (ah, aw) is fully sampled iff its count equals its area
+    cs = np.zeros((H + 1, W + 1), dtype=np.int64)
+    cs[1:, 1:] = np.cumsum(np.cumsum(full, axis=0), axis=1)
+    ch, cw = H // 2, W // 2
+    best = None
+    for ah in range(min(ch, H - 1 - ch, int(calib_max)) + 1):
+        for aw in range(min(cw, W - 1 - cw, int(calib_max)) + 1):
+            r0, r1, c0, c1 = ch - ah, ch + ah + 1, cw - aw, cw + aw + 1
+            area = (r1 - r0) * (c1 - c0)
+            if cs[r1, c1] - cs[r0, c1] - cs[r1, c0] + cs[r0, c0] != area:
+                continue
+            key = (area, -abs(ah - aw), aw)
+            if best is None or key > best[0]:
+                best = (key, ah, aw)
+    if best is None:
+        raise ValueError(f"calibration region: the k-space centre ({ch}, {cw}) of the {H}x{W} mask is not sampled in every "
+                         "frame; coil maps cannot be estimated from this acquisition")
+    _, ah, aw = best
+    if ah < 2 or aw < 2:
+        raise ValueError(f"calibration region: the fully sampled centre of the {H}x{W} mask is {2 * ah + 1} x {2 * aw + 1} "
+                         f"samples (half-widths ah = {ah}, aw = {aw}); the coil-map estimator needs at least 5 x 5 "
+                         "(ah >= 2 and aw >= 2): acquire more centre lines, or pass measured maps (sens_maps=)")
+    return ah, aw
+
+
 class UndersamplingFourier(LinearTransform):
     """every ``num_skip_lines``-th k-space ROW of the centred FFT (reference :10-36): S = P M F x, adjoint F^-1 M^T P^T"""
 
@@ -176,6 +215,35 @@ class SENSE(LinearTransform):
         maps = SENSE._as_host_maps(maps)
         rss = torch.sqrt((torch.abs(maps) ** 2).sum(dim=0))
         return maps / torch.where(rss > 0, rss, torch.ones_like(rss))
+
+    @staticmethod
+    def estimate_sens_maps(y, mask, calib_max=12, **kw):
+        """coil maps from the measurement itself: y (n, H, W) multi-coil k-space (tensor or ndarray; singleton batch /
+        channel dims as in a saved (n, 1, 1, H, W) measurement are dropped), centred with orthonormal scale as this
+        operator produces it, mask its sampling mask.  The calibration box is ``calibration_region(mask, H, W, calib_max)``,
+        the estimator ``ops.estimate_sens_maps`` on the current GPU (kw: radius, power_iters, thresh).
+        -> host complex128 (n, H, W), unit RSS inside the support and zero outside: ready for ``sens_maps=``"""
+        if not isinstance(y, (torch.Tensor, np.ndarray)):
+            raise TypeError(f"estimate_sens_maps: y must be a torch tensor or numpy array, got {type(y).__name__}")
+        y = torch.as_tensor(y).detach()
+        if not y.is_complex():
+            raise TypeError(f"estimate_sens_maps: y must be complex k-space, got {y.dtype}")
+        if y.dim() > 3 and all(s == 1 for s in y.shape[1:-2]):
+            y = y.reshape(y.shape[0], y.shape[-2], y.shape[-1])
+        if y.dim() != 3:
+            raise ValueError(f"estimate_sens_maps: y {tuple(y.shape)}; (n_coils, H, W) expected")
+        H, W = y.shape[-2:]
+        ah, aw = calibration_region(mask, H, W, calib_max)                  # host only: fails before any GPU work
+        yd = y.to(torch.complex64).to(y.device if y.is_cuda else "cuda").contiguous()
+        return ops.estimate_sens_maps(yd, ah, aw, **kw).cpu().to(torch.complex128)
+
+    @classmethod
+    def from_measurement(cls, y, mask, R=1, seed=None, calib_max=12, **kw):
+        """the ``"custom"`` operator of an acquisition: maps estimated from its own measurement y (n, H, W) and sampling
+        mask (estimate_sens_maps; kw goes to the estimator).  R is informational, as for every custom mask."""
+        maps = cls.estimate_sens_maps(y, mask, calib_max=calib_max, **kw)
+        n, H, W = maps.shape
+        return cls("custom", n, R, 0.04, (1, H, W), seed, mask_mode="custom", mask=mask, sens_maps=maps, normalize=False)
 
     @staticmethod
     def _as_host_maps(maps):

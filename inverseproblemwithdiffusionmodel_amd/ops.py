@@ -410,6 +410,80 @@ def ald_sense_cg_step(x_re, x_im, g_re, g_im, y, sens_f32, mask_u8, work, step=0
     return iters_out
 
 
+# ---- coil sensitivity maps from the calibration region (csrc/csm.hip) -----------------------------------------------
+def csm_supported(n_coils, radius, H, W):
+    """whether estimate_sens_maps has a kernel for this coil count (1..32), radius (1..4) and image size.  Needs no GPU."""
+    return bool(_lib.lib.ipdm_csm_supported(int(n_coils), int(radius), int(H), int(W)))
+
+
+def csm_workspace(B, n_coils, H, W, device):
+    """scratch tensor of estimate_sens_maps (calibration images + RSS plane); None for a shape without a kernel"""
+    nbytes = _lib.lib.ipdm_csm_workspace_bytes(B, n_coils, H, W)
+    return torch.empty(nbytes // 4, dtype=torch.float32, device=device) if nbytes else None
+
+
+def _csm_measurement(y, what):
+    """-> (n_coils, B, H, W) of a measurement (n, H, W), (n, B, H, W) or (n, B, 1, H, W): complex64, contiguous, on the GPU;
+    read through a raw pointer, so never converted"""
+    if not isinstance(y, torch.Tensor) or not y.is_cuda:
+        raise RuntimeError(f"ipdm {what}: y must be a GPU tensor (the HIP path has no CPU fallback)")
+    if y.dtype != torch.complex64:
+        raise TypeError(f"ipdm {what}: y must be complex64, got {y.dtype}")
+    if not y.is_contiguous():
+        raise TypeError(f"ipdm {what}: y must be contiguous (call .contiguous() and keep the result)")
+    shape = tuple(y.shape)
+    if len(shape) == 3:
+        return shape[0], 1, shape[1], shape[2]
+    if len(shape) == 4 or (len(shape) == 5 and shape[2] == 1):
+        return shape[0], shape[1], shape[-2], shape[-1]
+    raise ValueError(f"ipdm {what}: y {shape} is none of (n, H, W), (n, B, H, W), (n, B, 1, H, W)")
+
+
+def _csm_box(ah, aw):
+    if any(isinstance(a, bool) or int(a) != a for a in (ah, aw)):
+        raise ValueError(f"calibration half-widths must be integers, got ({ah}, {aw})")
+    return int(ah), int(aw)
+
+
+def csm_calib_images(y, ah, aw):
+    """the estimator's low-resolution calibration images: ifft2c of y inside the box [H//2-ah, H//2+ah] x [W//2-aw, W//2+aw]
+    under a separable raised-cosine window, zero outside it.  -> complex64 of y's shape"""
+    n, B, H, W = _csm_measurement(y, "csm_calib_images")
+    ah, aw = _csm_box(ah, aw)
+    out = torch.empty_like(y)
+    call("ipdm_csm_calib_images_c64", _ptr(y), ah, aw, _ptr(out), B, n, H, W, _stream())
+    return out
+
+
+def estimate_sens_maps(y, ah, aw, radius=2, power_iters=3, thresh=0.02, return_rss=False, *, out=None, work=None):
+    """coil sensitivity maps from the fully sampled calibration box of multi-coil k-space y ((n, H, W), (n, B, H, W) or
+    (n, B, 1, H, W) complex64; (ah, aw): SENSE's calibration_region): Walsh's adaptive estimator (ipdm.h,
+    ipdm_csm_walsh_c64) -> maps of y's shape: unit RSS over the coils and coil 0 real and non-negative inside the support
+    rss > thresh * rss_max, zero outside.  return_rss: -> (maps, rss (B, H, W) float32, rss_max (B,) float32) of the
+    calibration images.  Asynchronous; no host synchronisation."""
+    n, B, H, W = _csm_measurement(y, "estimate_sens_maps")
+    ah, aw = _csm_box(ah, aw)
+    if out is None:
+        out = torch.empty_like(y)
+    else:
+        _inplace_operand(out, torch.complex64, "out")
+        if out.numel() != y.numel():
+            raise ValueError(f"estimate_sens_maps: out {tuple(out.shape)} does not match y {tuple(y.shape)}")
+    need = _lib.lib.ipdm_csm_workspace_bytes(B, n, H, W)
+    if work is None:
+        work = csm_workspace(B, n, H, W, y.device)            # None for a shape without a kernel: the call reports it
+    elif (not isinstance(work, torch.Tensor) or not work.is_cuda or work.dtype != torch.float32 or not work.is_contiguous()
+            or work.numel() * 4 < need):
+        raise ValueError(f"estimate_sens_maps: `work` must be a contiguous float32 GPU tensor of >= {need} bytes "
+                         f"(ops.csm_workspace({B}, {n}, {H}, {W}, device))")
+    rss = torch.empty((B, H, W), dtype=torch.float32, device=y.device) if return_rss else None
+    rss_max = torch.empty(B, dtype=torch.float32, device=y.device)
+    call("ipdm_csm_walsh_c64", _ptr(y), ah, aw, int(radius), int(power_iters), float(thresh), _ptr(out), _ptr(rss),
+         _ptr(rss_max), _ptr(work), B, n, H, W, _stream())
+    _written(out)
+    return (out, rss, rss_max) if return_rss else out
+
+
 SC_L2PENALTY, SC_CLOSED_FORM, SC_PROJECTION = 0, 1, 2
 
 

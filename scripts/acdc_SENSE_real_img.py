@@ -2,8 +2,10 @@
 """Multi-coil ALD reconstruction on synthetic k-space -- the MI355X counterpart of the reference's
 ``scripts/acdc_SENSE_real_img.py`` with the same flags and output artefacts (original.pt, measurement.pt,
 reconstructions.pt, ZF.pt, mask.pt, args_dict.pkl).  Data and weights are synthetic (phantom + seeded weights)
-unless --ckpt points at a Lightning checkpoint of the reference; samples are sharded over the launched ranks
-(torchrun) and rank 0 writes the posterior mean / std next to the reconstructions."""
+unless --ckpt points at a Lightning checkpoint of the reference and --kspace at measured multi-coil k-space (with its
+--mask; no ground truth then: original.pt and the RMSE line are skipped); --estimate_maps takes the coil maps from the
+measurement's own calibration region (sens_maps.pt).  Samples are sharded over the launched ranks (torchrun) and rank 0
+writes the posterior mean / std next to the reconstructions."""
 import argparse
 import os
 import pickle
@@ -55,6 +57,14 @@ if __name__ == '__main__':
                         help=".npy / .pt file with the sampling mask: a line mask (..., W) or a 2-D mask (..., H, W)")
     parser.add_argument("--mask_2d", action="store_true",
                         help="synthetic variable-density 2-D (ky, kz) sampling mask at --R instead of the line mask")
+    parser.add_argument("--kspace", default=None,
+                        help=".npy / .pt file with measured multi-coil k-space (n_coils, H, W), complex, centred with "
+                             "orthonormal scale; needs --mask PATH and either --sens_maps PATH or --estimate_maps")
+    parser.add_argument("--estimate_maps", action="store_true",
+                        help="estimate the coil maps from the fully sampled calibration region of the measurement")
+    parser.add_argument("--calib_max", type=int, default=12, help="--estimate_maps: largest calibration half-width")
+    parser.add_argument("--kspace_scale", default="auto",
+                        help="--kspace: factor on the measurement; auto: 1 / the peak of its calibration image")
     parser.add_argument("--seg_synthetic", action="store_true",
                         help="run the guidance with seeded random UNet weights (exercises the path; not meaningful imaging)")
     args_dict = vars(parser.parse_args())
@@ -65,9 +75,30 @@ if __name__ == '__main__':
 
     H = args_dict["image_size"]
     W = args_dict["image_width"] if args_dict["image_width"] is not None else H
+    kspace = None
+    if args_dict["kspace"]:
+        if not args_dict["mask"]:
+            sys.exit("--kspace PATH needs --mask PATH, the sampling mask of the acquisition")
+        if bool(args_dict["sens_maps"]) == args_dict["estimate_maps"] or args_dict["sens_phase"]:
+            sys.exit("--kspace PATH takes its coil maps from --sens_maps PATH or from --estimate_maps (one of them)")
+        from inverseproblemwithdiffusionmodel_amd.helpers.load_data import load_kspace
+        kspace = load_kspace(args_dict["kspace"])
+        args_dict["num_sens"], H, W = (int(s) for s in kspace.shape)
+    kspace_scale = None if args_dict["kspace_scale"] == "auto" else float(args_dict["kspace_scale"])
     from inverseproblemwithdiffusionmodel_amd import ops
     if ops.kspace_size_class(H, W) == ops.KSPACE_NONE:                    # before any allocation
         sys.exit(f"--image_size {H} --image_width {W}: no k-space kernel for {H}x{W}; {ops.KSPACE_SIZE_RULE}")
+    # the mask, and the calibration region the run depends on, before the score network is built or a GPU is touched
+    from inverseproblemwithdiffusionmodel_amd.helpers.load_data import driver_mask
+    mask = driver_mask(args_dict["mask"], args_dict["mask_2d"], H, W, args_dict["R"], args_dict["seed"])
+    if args_dict["estimate_maps"] or (kspace is not None and kspace_scale is None):
+        from inverseproblemwithdiffusionmodel_amd.ncsn.linear_transforms import undersampling_fourier as uf
+        try:
+            uf.calibration_region(mask if mask is not None else
+                                  uf.RandomUndersamplingFourier(args_dict["R"], 0.04, (1, H, W), args_dict["seed"]).mask,
+                                  H, W, args_dict["calib_max"])
+        except ValueError as e:
+            sys.exit(f"--estimate_maps / --kspace: {e}")
     from inverseproblemwithdiffusionmodel_amd import engine, sharding
     world, rank, device = sharding.init_distributed()
     from inverseproblemwithdiffusionmodel_amd.helpers.load_model import load_scorenet_weights
@@ -88,11 +119,11 @@ if __name__ == '__main__':
     elif args_dict["sens_phase"]:
         from inverseproblemwithdiffusionmodel_amd.synthetic import complex_coil_maps
         sens_maps = complex_coil_maps(args_dict["num_sens"], H, W, args_dict["seed"])
-    from inverseproblemwithdiffusionmodel_amd.helpers.load_data import driver_mask
-    mask = driver_mask(args_dict["mask"], args_dict["mask_2d"], H, W, args_dict["R"], args_dict["seed"])
     prob = engine.build_problem(device, n_local, R=args_dict["R"], H=H, W=W, num_sens=args_dict["num_sens"],
                                 seed=args_dict["seed"], scorenet=scorenet, cfg=cfg, lr_scaled=args_dict["lr_scaled"],
-                                sens_maps=sens_maps, mask=mask, proximal=args_dict["proximal_type"],
+                                sens_maps=sens_maps, mask=mask, estimate_maps=args_dict["estimate_maps"], measurement=kspace,
+                                calib_max=args_dict["calib_max"], kspace_scale=kspace_scale,
+                                proximal=args_dict["proximal_type"],
                                 proximal_kwargs=(dict(max_iter=args_dict["cg_iters"], tol=args_dict["cg_tol"])
                                                  if args_dict["proximal_type"] == "L2PenaltyCG" else None))
     label = None
@@ -101,6 +132,8 @@ if __name__ == '__main__':
         from inverseproblemwithdiffusionmodel_amd.helpers.utils import undersample_seg_mask
         from inverseproblemwithdiffusionmodel_amd.ncsn.models.ALD_optimizers import ALDInvSegProximalRealImag
         seg = reload_model("Seg", "ACDC", ckpt_path=args_dict["seg_ckpt"], device=device)
+        if prob.image is None:
+            sys.exit("--kspace: the synthetic segmentation label needs the phantom; run with --seg_start_time 1")
         label = (prob.image.abs() > 0.5).long()                       # synthetic stand-in for the myocardium label
         label = undersample_seg_mask(label, args_dict["seg_fraction"], seed=args_dict["seed"])
         s0 = prob.sampler
@@ -123,15 +156,20 @@ if __name__ == '__main__':
     if rank == 0:
         resid = prob.op(img_out[:1].to(device)) - prob.measurement[:, :1]
         l2 = torch.sum(torch.abs(resid) ** 2).item()
-        err = torch.sqrt(torch.mean(torch.abs(img_out[:1].to(device) - prob.image) ** 2)).item()
         print(f"reconstruction time: {elapsed:.1f} s for {total} sample(s) on {world} GPU(s)")
-        print(f"data error ||A x - y||^2 = {l2:.4e}; reconstruction error (RMSE vs phantom) = {err:.4e}")
-        torch.save(prob.image.cpu(), os.path.join(save_dir, "original.pt"))
+        if prob.kspace_scale is not None:
+            print(f"k-space scale = {prob.kspace_scale!r}")
+        if prob.image is None:                                        # measured data: no ground truth
+            print(f"data error ||A x - y||^2 = {l2:.4e}")
+        else:
+            err = torch.sqrt(torch.mean(torch.abs(img_out[:1].to(device) - prob.image) ** 2)).item()
+            print(f"data error ||A x - y||^2 = {l2:.4e}; reconstruction error (RMSE vs phantom) = {err:.4e}")
+            torch.save(prob.image.cpu(), os.path.join(save_dir, "original.pt"))
         torch.save(prob.measurement[:, :1].cpu(), os.path.join(save_dir, "measurement.pt"))
         torch.save(img_out.cpu(), os.path.join(save_dir, "reconstructions.pt"))
         torch.save(direct_recons.cpu(), os.path.join(save_dir, "ZF.pt"))
         torch.save(prob.op.random_under_fourier.mask, os.path.join(save_dir, "mask.pt"))
-        if sens_maps is not None:
+        if sens_maps is not None or prob.estimated_maps:
             torch.save(prob.op.sens_maps, os.path.join(save_dir, "sens_maps.pt"))
         if post is not None:
             torch.save({k: v.cpu() for k, v in post.items()}, os.path.join(save_dir, "posterior.pt"))
