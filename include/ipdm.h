@@ -675,6 +675,10 @@ int ipdm_in_prelu_fwd_f32(const float* x, const float* slope, float* xhat, float
 /* input-gradient of ipdm_in_prelu_fwd_f32 */
 int ipdm_in_prelu_bwd_f32(const float* gy, const float* xhat, const float* rstd, const float* slope, float* gx, int planes,
                           int HW, void* stream);
+/* the same with the forward's eps (> 0): at HW = 2, where the gradient is eps rstd^2 of the terms of its formula and the fp32 xhat
+ * no longer holds it, the closed form gx = +-eps rstd^3 (g_h0 - g_h1) / 2 is taken; every other HW is ipdm_in_prelu_bwd_f32 */
+int ipdm_in_prelu_bwd_eps_f32(const float* gy, const float* xhat, const float* rstd, const float* slope, float* gx, int planes,
+                              int HW, float eps, void* stream);
 /* g = d/dlogits sum log softmax(logits)[label]: g[b][c][p] = [c == label[b][p]] - softmax_c; logits [B][C][HW], label int64 */
 int ipdm_seg_loglh_grad_f32(const float* logits, const int64_t* label, float* g, int B, int C, int64_t HW, void* stream);
 /* y += scale * x (* mask[i % mask_period], the "FG" mode); scale = dev_sched->seg_scale when dev_sched is non-NULL */

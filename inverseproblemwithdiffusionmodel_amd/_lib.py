@@ -149,6 +149,7 @@ SIGNATURES = {
     "ipdm_subsample2_f32": [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P],
     "ipdm_in_prelu_fwd_f32": [P, P, P, P, P, c_int, c_int, c_float, P],
     "ipdm_in_prelu_bwd_f32": [P, P, P, P, P, c_int, c_int, P],
+    "ipdm_in_prelu_bwd_eps_f32": [P, P, P, P, P, c_int, c_int, c_float, P],
     "ipdm_seg_loglh_grad_f32": [P, P, P, c_int, c_int, c_int64, P],
     "ipdm_axpy_sched_f32": [P, P, P, c_int64, P, c_float, c_int64, P],
     "ipdm_magnitude_c64": [P, P, c_int64, P],

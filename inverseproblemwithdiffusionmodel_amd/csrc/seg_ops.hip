@@ -52,9 +52,12 @@ __global__ __launch_bounds__(256) void in_prelu_fwd_kernel(const float* __restri
                                                            float* __restrict__ rstd_out, int HW, float eps) {
   __shared__ float scratch[4];
   const float* xp = x + (size_t)blockIdx.x * HW;
+  // mean = x[0] + mean(x - x[0]): a constant plane has exactly its own mean and xhat = 0 (the plain fp32 sum of HW equal
+  // values rounds, and rstd = eps^-1/2 turns an ulp of a mean of 50 into 1e-3 of xhat), an offset plane sums its width only
+  const float x0 = xp[0];
   float s = 0.f;
-  for (int i = threadIdx.x; i < HW; i += 256) s += xp[i];
-  const float mean = block_sum_f(s, scratch) / (float)HW;
+  for (int i = threadIdx.x; i < HW; i += 256) s += xp[i] - x0;
+  const float mean = x0 + block_sum_f(s, scratch) / (float)HW;
   float q = 0.f;
   for (int i = threadIdx.x; i < HW; i += 256) {
     const float d = xp[i] - mean;
@@ -71,12 +74,25 @@ __global__ __launch_bounds__(256) void in_prelu_fwd_kernel(const float* __restri
 }
 
 // input-gradient of the above: g_h = g_y * (xhat > 0 ? 1 : slope) ; g_x = rstd * (g_h - mean(g_h) - xhat * mean(g_h * xhat))
+// Two pixels (eps > 0: the forward's eps is known): xhat = +-sqrt(1 - eps rstd^2) whatever x is and the centred g_h is collinear
+// with it, so the formula is rstd (g_h0 - g_h1) / 2 * (1 - xhat^2) -- terms of order one cancelling to eps rstd^2 of
+// themselves, which the fp32 xhat has already lost.  The remainder is taken in closed form: g_x = +-eps rstd^3 (g_h0 - g_h1) / 2.
 __global__ __launch_bounds__(256) void in_prelu_bwd_kernel(const float* __restrict__ gy, const float* __restrict__ xhat,
                                                            const float* __restrict__ rstd, const float* __restrict__ slope,
-                                                           float* __restrict__ gx, int HW) {
+                                                           float* __restrict__ gx, int HW, float eps) {
   __shared__ float scratch[4];
   const size_t base = (size_t)blockIdx.x * HW;
   const float a = slope ? slope[0] : 1.f;
+  if (HW == 2 && eps > 0.f) {                              // (uniform over the workgroup: no barrier is skipped by a part of it)
+    if (threadIdx.x == 0) {
+      const float g0 = gy[base] * (xhat[base] > 0.f ? 1.f : a), g1 = gy[base + 1] * (xhat[base + 1] > 0.f ? 1.f : a);
+      const float r = rstd[blockIdx.x];
+      const float t = eps * r * r * r * (0.5f * (g0 - g1));
+      gx[base] = t;
+      gx[base + 1] = -t;
+    }
+    return;
+  }
   float s1 = 0.f, s2 = 0.f;
   for (int i = threadIdx.x; i < HW; i += 256) {
     const float h = xhat[base + i];
@@ -156,13 +172,18 @@ extern "C" int ipdm_in_prelu_fwd_f32(const float* x, const float* slope, float* 
   return ipdm_launch_status();
 }
 
-extern "C" int ipdm_in_prelu_bwd_f32(const float* gy, const float* xhat, const float* rstd, const float* slope, float* gx,
-                                     int planes, int HW, void* stream) {
+extern "C" int ipdm_in_prelu_bwd_eps_f32(const float* gy, const float* xhat, const float* rstd, const float* slope, float* gx,
+                                         int planes, int HW, float eps, void* stream) {
   IPDM_REQUIRE(planes >= 0 && HW > 0);
   if (planes == 0) return IPDM_OK;
   IPDM_REQUIRE(gy && xhat && rstd && gx);
-  hipLaunchKernelGGL(in_prelu_bwd_kernel, dim3(planes), dim3(256), 0, ipdm_stream(stream), gy, xhat, rstd, slope, gx, HW);
+  hipLaunchKernelGGL(in_prelu_bwd_kernel, dim3(planes), dim3(256), 0, ipdm_stream(stream), gy, xhat, rstd, slope, gx, HW, eps);
   return ipdm_launch_status();
+}
+
+extern "C" int ipdm_in_prelu_bwd_f32(const float* gy, const float* xhat, const float* rstd, const float* slope, float* gx,
+                                     int planes, int HW, void* stream) {
+  return ipdm_in_prelu_bwd_eps_f32(gy, xhat, rstd, slope, gx, planes, HW, 0.f, stream);       // eps unknown: the plain formula
 }
 
 extern "C" int ipdm_seg_loglh_grad_f32(const float* logits, const int64_t* label, float* g, int B, int C, int64_t HW,

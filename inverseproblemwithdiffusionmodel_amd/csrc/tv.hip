@@ -8,8 +8,9 @@
 
 namespace {
 
+// (hypotf: s(z) has no scale, but the fp32 squares of an ordinary difference underflow below ~1e-19 and overflow above ~1e19)
 __device__ __forceinline__ float2 unit_of(float2 d) {
-  const float n = sqrtf(d.x * d.x + d.y * d.y);
+  const float n = hypotf(d.x, d.y);
   return n > 0.f ? make_float2(d.x / n, d.y / n) : make_float2(0.f, 0.f);
 }
 

@@ -589,12 +589,13 @@ def in_prelu_fwd(x, slope, eps=1e-5):
     return xhat, y, rstd
 
 
-def in_prelu_bwd(gy, xhat, rstd, slope):
+def in_prelu_bwd(gy, xhat, rstd, slope, eps=1e-5):
+    """input-gradient of in_prelu_fwd from what it saved; eps: the forward's (planes of two pixels need it, seg_ops.hip)"""
     gy = _gpu(gy, torch.float32, "gy")
     B, C = gy.shape[:2]
     gx = torch.empty_like(gy)
-    call("ipdm_in_prelu_bwd_f32", _ptr(gy), _ptr(xhat), _ptr(rstd), _ptr(slope), _ptr(gx), B * C, gy.numel() // max(B * C, 1),
-         _stream())
+    call("ipdm_in_prelu_bwd_eps_f32", _ptr(gy), _ptr(xhat), _ptr(rstd), _ptr(slope), _ptr(gx), B * C,
+         gy.numel() // max(B * C, 1), float(eps), _stream())
     return gx
 
 
