@@ -277,6 +277,34 @@ int ipdm_csm_walsh_c64(const float* y, int ah, int aw, int radius, int power_ite
                        float* rss_max /* [B] */, float* work /* ipdm_csm_workspace_bytes(B, n_coils, H, W) */, int B,
                        int n_coils, int H, int W, void* stream);
 
+/* Coil compression and noise prewhitening of a multi-coil measurement (software coil compression by PCA of the calibration
+ * data; not in the reference, which synthesises 4 maps).  y [n_coils][B][H][W] c64 and the calibration box (ah, aw) as above.
+ *   gram    G_b[i][j] = sum over the box of y_i(b,k) conj(y_j(b,k)), no window: [B][n_coils][n_coils] c64, exactly
+ *           Hermitian with a real diagonal (summed in double, rounded once)
+ *   matrix  with noise_cov psi [n_coils][n_coils] c64 (Hermitian positive definite, shared by the batch; NULL: none):
+ *           psi = L L^H, G <- L^-1 G L^-H.  G = U diag(eig) U^H by cyclic Hermitian Jacobi (12 sweeps, fixed: the
+ *           launch never depends on the data), eigenvalues descending, equal ones in their original order.  A_b = U[:, :n_virtual]^H (times
+ *           L^-1), [B][n_virtual][n_coils] c64, each row turned by a unit phase so that A_b[v][0] is real and non-negative
+ *           (left alone where it is exactly zero).  eig [B][n_coils] or NULL.  status [B] int32: 0, or 1 where a Cholesky
+ *           pivot of psi is not positive; that image's A and eig are then zeros, never NaN.
+ *   apply   out_v(b,p) = sum_c A[v][c] y_c(b,p): y [n_coils][B][P], out [n_virtual][B][P] c64 for any pixel count P per
+ *           image (maps [n_coils][1][H*W] compress the same way); A per image ([B][n_virtual][n_coils], per_image != 0) or
+ *           one [n_virtual][n_coils] for the whole batch.  out may not overlap y (IPDM_EINVAL).
+ *   compress  the three in one call, A per image; work: ipdm_coilcomp_workspace_bytes(B, n_coils) bytes (the Gram matrices).
+ * n_coils 1..64, n_virtual 1..min(n_coils, 32), B <= 65535, otherwise IPDM_EUNSUPPORTED (ipdm_coilcomp_supported tells,
+ * without a GPU); IPDM_EINVAL: a box outside the image, a NULL tensor, overlapping y and out.  fp32 arithmetic; asynchronous,
+ * allocation-free, hipGraph-capturable, no atomics: deterministic, an image's results do not depend on its batch.  Every
+ * tensor may sit on any 8-byte boundary (eig, status: 4). */
+int ipdm_coilcomp_supported(int n_coils, int n_virtual);             /* 1 / 0, no GPU needed */
+size_t ipdm_coilcomp_workspace_bytes(int B, int n_coils);            /* 0 when unserved */
+int ipdm_coil_gram_c64(const float* y, int ah, int aw, float* gram, int B, int n_coils, int H, int W, void* stream);
+int ipdm_coilcomp_matrix_c64(const float* gram, const float* noise_cov, int n_virtual, float* A, float* eig, int32_t* status,
+                             int B, int n_coils, void* stream);
+int ipdm_coil_apply_c64(const float* y, const float* A, int per_image, float* out, int B, int n_coils, int n_virtual,
+                        int64_t P, void* stream);
+int ipdm_coil_compress_c64(const float* y, int ah, int aw, int n_virtual, const float* noise_cov, float* A, float* eig,
+                           int32_t* status, float* out, float* work, int B, int n_coils, int H, int W, void* stream);
+
 /* Single-coil data-consistency operators (A = M F, RandomUndersamplingFourier, no coil maps) on planar real/imag
  * float32 [B][H][W], y [B][H][W] complex64; out may alias z.  mode:
  *   0  L2Penalty on a single-coil operator (proximal_op.py:19-51): x = z - coef * F^-1[M (M F z - y)],

@@ -62,6 +62,12 @@ SIGNATURES = {
     "ipdm_csm_supported": [c_int, c_int, c_int, c_int],
     "ipdm_csm_calib_images_c64": [P, c_int, c_int, P, c_int, c_int, c_int, c_int, P],
     "ipdm_csm_walsh_c64": [P, c_int, c_int, c_int, c_int, c_float, P, P, P, P, c_int, c_int, c_int, c_int, P],
+    "ipdm_coilcomp_supported": [c_int, c_int],
+    "ipdm_coilcomp_workspace_bytes": [c_int, c_int],
+    "ipdm_coil_gram_c64": [P, c_int, c_int, P, c_int, c_int, c_int, c_int, P],
+    "ipdm_coilcomp_matrix_c64": [P, P, c_int, P, P, P, c_int, c_int, P],
+    "ipdm_coil_apply_c64": [P, P, c_int, P, c_int, c_int, c_int, c_int64, P],
+    "ipdm_coil_compress_c64": [P, c_int, c_int, c_int, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P],
     "ipdm_singlecoil_prox_f32": [P, P, P, P, c_int, c_float, c_int, P, P, P, c_int, c_int, c_int, P],
     "ipdm_ald_singlecoil_step_f32": [P, P, P, P, P, P, c_float, c_float, c_uint64, c_int64, c_int64, P,
                                      P, P, c_int, c_float, c_int, P, c_int, c_int, c_int, P],
@@ -163,7 +169,8 @@ _RESTYPES = {"ipdm_build_arch": c_char_p, "ipdm_fft2c_workspace_bytes": c_int64,
              "ipdm_conv_bx3_weight_bytes": c_int64,
              "ipdm_conv_wino_bx3_weight_bytes": c_int64, "ipdm_conv_hx2_weight_bytes": c_int64,
              "ipdm_conv_wino_hx2_weight_bytes": c_int64, "ipdm_conv_wino1d_weight_bytes": c_int64, "ipdm_conv_wino1d_weight_bytes3d": c_int64,
-             "ipdm_conv1d_hx2_weight_bytes": c_int64, "ipdm_csm_workspace_bytes": ctypes.c_size_t}
+             "ipdm_conv1d_hx2_weight_bytes": c_int64, "ipdm_csm_workspace_bytes": ctypes.c_size_t,
+             "ipdm_coilcomp_workspace_bytes": ctypes.c_size_t}
 
 IPDM_EINVAL = -1
 IPDM_EUNSUPPORTED = -2

@@ -57,7 +57,7 @@ def build_scorenet(cfg, seed=0):
 
 def build_problem(device, n_samples, R=40, H=128, W=128, num_sens=4, seed=0, scorenet=None, cfg=None, lr_scaled=1.0,
                   sens_maps=None, proximal="L2Penalty", proximal_kwargs=None, mask=None, estimate_maps=False, measurement=None,
-                  calib_max=12, kspace_scale=None):
+                  calib_max=12, kspace_scale=None, coil_compress=None, noise_cov=None):
     """-> Namespace(sampler, scorenet, sigmas, op, image, measurement, call_kwargs); sens_maps: measured coil maps
     (num_sens, H, W), real or complex, instead of the synthetic "exp" maps (RSS-normalised where non-zero); proximal: a
     get_proximal name ("L2PenaltyCG": the exact proximal, proximal_kwargs = dict(max_iter=, tol=)); mask: the sampling mask
@@ -67,10 +67,18 @@ def build_problem(device, n_samples, R=40, H=128, W=128, num_sens=4, seed=0, sco
     measurement: measured k-space (n, H, W) instead of the simulated one: no phantom (image is None), maps from
     sens_maps or estimated, the data multiplied by kspace_scale -- None: 1 / rss_max of its calibration image, since the
     score prior expects magnitudes in [0, 1].  The Namespace then carries kspace_scale; estimated_maps is True when the
-    operator's maps were estimated."""
+    operator's maps were estimated.
+    coil_compress: the measurement (measured or simulated; up to 64 coils) is whitened with noise_cov (the (n, n) coil
+    noise covariance, optional) and compressed to this many virtual coils by PCA of its calibration region
+    (ops.coil_compress) before anything else sees it: the maps are estimated on the virtual coils (estimate_maps=True) or
+    the given / synthetic maps are compressed with the same matrix (ops.coil_apply), the automatic kspace_scale comes from
+    the compressed data, and the operator, the measurement and the sampler have coil_compress coils.  The Namespace
+    carries the matrix as coil_matrix ((coil_compress, n) complex64 on the host; None without compression)."""
     prox_cls = get_proximal(proximal)                        # an unknown name fails here, before any GPU work
     kspace_scale = None if kspace_scale is None else float(kspace_scale)
     region = None
+    if noise_cov is not None and coil_compress is None:
+        raise ValueError("build_problem: noise_cov= goes with coil_compress= (whitening is part of the compression)")
     if measurement is not None:                              # host-side checks: all fail before any GPU work
         if mask is None:
             raise ValueError("build_problem(measurement=...): pass mask=, the sampling mask of the acquisition")
@@ -81,8 +89,13 @@ def build_problem(device, n_samples, R=40, H=128, W=128, num_sens=4, seed=0, sco
             raise ValueError(f"build_problem: measurement {tuple(measurement.shape)} {measurement.dtype}; complex "
                              f"(n_coils, {H}, {W}) expected")
         num_sens = measurement.shape[0]
-        if estimate_maps or kspace_scale is None:
+        if estimate_maps or kspace_scale is None or coil_compress is not None:
             region = calibration_region(mask, H, W, calib_max)
+    if coil_compress is not None:                            # host-side as well
+        coil_compress = ops_mod._coilcomp_counts(num_sens, coil_compress, "build_problem(coil_compress=...)")
+        if noise_cov is not None:
+            noise_cov = ops_mod.check_noise_cov(noise_cov, num_sens, "build_problem: noise_cov")
+    coil_matrix = None
     cfg = acdc_config(device, H) if cfg is None else cfg
     scorenet = build_scorenet(cfg, seed) if scorenet is None else scorenet
     sigmas = get_sigmas(cfg, "recons")
@@ -90,6 +103,12 @@ def build_problem(device, n_samples, R=40, H=128, W=128, num_sens=4, seed=0, sco
     if measurement is not None:
         img = None
         y = measurement.to(torch.complex64).to(device).contiguous()
+        if coil_compress is not None:
+            y, A, _, _ = ops_mod.coil_compress(y, *region, coil_compress, noise_cov, return_matrix=True)
+            coil_matrix = A[0]
+            if sens_maps is not None:
+                sens_maps = _compress_maps(SENSE.rss_normalize(sens_maps), coil_matrix, num_sens, H, W, device)
+            num_sens = coil_compress
         if region is not None:
             # one call serves both uses: the maps (kept only with estimate_maps) and rss_max for the automatic scale; with
             # sens_maps= given and no kspace_scale the maps are computed and dropped (a fraction of a millisecond, once)
@@ -102,17 +121,25 @@ def build_problem(device, n_samples, R=40, H=128, W=128, num_sens=4, seed=0, sco
         if estimate_maps:
             op = SENSE("custom", num_sens, R, 0.04, (1, H, W), seed=seed, mask_T=1, sens_maps=maps.cpu(), normalize=False, **mk)
         else:
-            op = SENSE("custom", num_sens, R, 0.04, (1, H, W), seed=seed, mask_T=1, sens_maps=sens_maps, **mk)
+            op = SENSE("custom", num_sens, R, 0.04, (1, H, W), seed=seed, mask_T=1, sens_maps=sens_maps,
+                       normalize=coil_compress is None, **mk)
         meas1 = (y * kspace_scale).reshape(num_sens, 1, 1, H, W)
     else:
         if sens_maps is None:
             op = SENSE("exp", num_sens, R, 0.04, (1, H, W), seed=seed, mask_T=1, **mk)
         else:
             op = SENSE("custom", num_sens, R, 0.04, (1, H, W), seed=seed, mask_T=1, sens_maps=sens_maps, **mk)
-        if estimate_maps:                                    # host only: an unusable centre fails before the forward model runs
-            calibration_region(op.random_under_fourier.mask, H, W, calib_max)
+        if estimate_maps or coil_compress is not None:       # host only: an unusable centre fails before the forward model runs
+            region = calibration_region(op.random_under_fourier.mask, H, W, calib_max)
         img = phantom_image(H, W, seed=seed).to(device)
         meas1 = op(img)
+        if coil_compress is not None:                        # simulated with the physical coils, compressed like a measured scan
+            meas1, A, _, _ = ops_mod.coil_compress(meas1, *region, coil_compress, noise_cov, return_matrix=True)
+            coil_matrix = A[0]
+            if not estimate_maps:
+                op = SENSE("custom", coil_compress, R, 0.04, (1, H, W), seed=seed, mask_T=1, normalize=False, mask_mode="custom",
+                           mask=op.random_under_fourier.mask,
+                           sens_maps=_compress_maps(op.sens_maps, coil_matrix, num_sens, H, W, device))
         if estimate_maps:                                    # simulated with the true maps, reconstructed with the estimated ones
             op = SENSE.from_measurement(meas1, op.random_under_fourier.mask, R=R, seed=seed, calib_max=calib_max)
     meas = meas1.repeat(1, n_samples, 1, 1, 1).contiguous()
@@ -123,7 +150,18 @@ def build_problem(device, n_samples, R=40, H=128, W=128, num_sens=4, seed=0, sco
     return Namespace(sampler=sampler, scorenet=scorenet, sigmas=sigmas, op=op, image=img, measurement=meas, cfg=cfg,
                      params=params, call_kwargs=dict(label=None, lamda=0.1, save_dir=None, lr_scaled=lr_scaled,
                                                      seg_mode="full"),
-                     estimated_maps=bool(estimate_maps), kspace_scale=kspace_scale)
+                     estimated_maps=bool(estimate_maps), kspace_scale=kspace_scale,
+                     coil_matrix=None if coil_matrix is None else coil_matrix.cpu())
+
+
+def _compress_maps(maps, A, n, H, W, device):
+    """coil maps (n, H, W) of the physical coils -> the (nv, H, W) maps of the virtual coils, host complex128: the same
+    matrix A (nv, n) that compressed the measurement, applied by the streaming kernel"""
+    maps = torch.as_tensor(maps)
+    if tuple(maps.shape) != (n, H, W):
+        raise ValueError(f"build_problem: sens_maps {tuple(maps.shape)}, expected {(n, H, W)}")
+    m = maps.to(torch.complex64).to(device).reshape(n, 1, H, W).contiguous()
+    return ops_mod.coil_apply(m, A.contiguous())[:, 0].cpu().to(torch.complex128)
 
 
 class IterationRunner:

@@ -247,6 +247,28 @@ def load_kspace(path):
     return y.to(torch.complex64).contiguous()
 
 
+def load_noise_cov(path):
+    """coil noise covariance (n_coils, n_coils), real or complex, from a ``.npy`` or ``.pt`` file -> host tensor
+    (float64 / complex128) for ``noise_cov=``; that it is Hermitian positive definite is checked where it is used
+    (``ops.check_noise_cov``)"""
+    import numpy as np
+    import torch
+    ext = os.path.splitext(str(path))[1].lower()
+    if ext == ".npy":
+        psi = torch.from_numpy(np.load(path, allow_pickle=False))
+    elif ext == ".pt":
+        psi = torch.load(path, map_location="cpu")
+        if isinstance(psi, np.ndarray):
+            psi = torch.from_numpy(psi)
+    else:
+        raise ValueError(f"load_noise_cov: {path!r}: a .npy or .pt file")
+    if not isinstance(psi, torch.Tensor) or psi.dim() != 2 or psi.shape[0] != psi.shape[1]:
+        raise ValueError(f"load_noise_cov: {path!r} must hold one square matrix (n_coils, n_coils)")
+    if not (psi.is_complex() or psi.is_floating_point()):
+        raise TypeError(f"load_noise_cov: {path!r} holds {psi.dtype}; a real or complex floating matrix expected")
+    return psi.to(torch.complex128 if psi.is_complex() else torch.float64)
+
+
 def load_mask(path):
     """k-space sampling mask from a ``.npy`` or ``.pt`` file -> host tensor, dtype and shape as stored: a line mask
     ((W,), (1, 1, W), (T, 1, 1, W)) or a 2-D mask ((H, W), (1, 1, H, W), (T, 1, H, W)), bool, integer or real floating

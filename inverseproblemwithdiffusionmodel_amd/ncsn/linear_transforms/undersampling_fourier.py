@@ -237,10 +237,41 @@ class SENSE(LinearTransform):
         yd = y.to(torch.complex64).to(y.device if y.is_cuda else "cuda").contiguous()
         return ops.estimate_sens_maps(yd, ah, aw, **kw).cpu().to(torch.complex128)
 
+    @staticmethod
+    def compress_measurement(y, mask, n_virtual, noise_cov=None, calib_max=12):
+        """whitening and coil compression of a measurement: y (n, H, W) multi-coil k-space as for estimate_sens_maps (up to
+        64 coils), n_virtual 1..min(n, 32) virtual coils by PCA of the calibration box ``calibration_region(mask, H, W,
+        calib_max)``, noise_cov the (n, n) Hermitian positive definite coil noise covariance of the prescan (None: white
+        noise assumed).  ``ops.coil_compress`` on the current GPU.  -> (y' (n_virtual, H, W) complex64 on the GPU,
+        A (n_virtual, n) complex64 on the host).  Every argument is checked on the host before any GPU work."""
+        if not isinstance(y, (torch.Tensor, np.ndarray)):
+            raise TypeError(f"compress_measurement: y must be a torch tensor or numpy array, got {type(y).__name__}")
+        y = torch.as_tensor(y).detach()
+        if not y.is_complex():
+            raise TypeError(f"compress_measurement: y must be complex k-space, got {y.dtype}")
+        if y.dim() > 3 and all(s == 1 for s in y.shape[1:-2]):
+            y = y.reshape(y.shape[0], y.shape[-2], y.shape[-1])
+        if y.dim() != 3:
+            raise ValueError(f"compress_measurement: y {tuple(y.shape)}; (n_coils, H, W) expected")
+        n, H, W = y.shape
+        n_virtual = ops._coilcomp_counts(n, n_virtual, "compress_measurement")
+        if noise_cov is not None:
+            noise_cov = ops.check_noise_cov(noise_cov, n, "compress_measurement: noise_cov")
+        ah, aw = calibration_region(mask, H, W, calib_max)
+        yd = y.to(torch.complex64).to(y.device if y.is_cuda else "cuda").contiguous()
+        out, A, _, _ = ops.coil_compress(yd, ah, aw, n_virtual, noise_cov, return_matrix=True)
+        return out, A[0].cpu()
+
     @classmethod
-    def from_measurement(cls, y, mask, R=1, seed=None, calib_max=12, **kw):
+    def from_measurement(cls, y, mask, R=1, seed=None, calib_max=12, n_virtual=None, noise_cov=None, **kw):
         """the ``"custom"`` operator of an acquisition: maps estimated from its own measurement y (n, H, W) and sampling
-        mask (estimate_sens_maps; kw goes to the estimator).  R is informational, as for every custom mask."""
+        mask (estimate_sens_maps; kw goes to the estimator).  R is informational, as for every custom mask.  n_virtual:
+        the measurement is whitened (noise_cov) and compressed first (compress_measurement) and the maps are those of the
+        virtual coils -- the operator then has n_virtual coils and serves the compressed measurement."""
+        if n_virtual is not None:
+            y, _ = cls.compress_measurement(y, mask, n_virtual, noise_cov=noise_cov, calib_max=calib_max)
+        elif noise_cov is not None:
+            raise ValueError("from_measurement: noise_cov= goes with n_virtual= (whitening is part of the compression)")
         maps = cls.estimate_sens_maps(y, mask, calib_max=calib_max, **kw)
         n, H, W = maps.shape
         return cls("custom", n, R, 0.04, (1, H, W), seed, mask_mode="custom", mask=mask, sens_maps=maps, normalize=False)

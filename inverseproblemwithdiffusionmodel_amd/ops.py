@@ -484,6 +484,163 @@ def estimate_sens_maps(y, ah, aw, radius=2, power_iters=3, thresh=0.02, return_r
     return (out, rss, rss_max) if return_rss else out
 
 
+# ---- coil compression and noise prewhitening (csrc/coilcomp.hip) ------------------------------------------------------
+def coilcomp_supported(n_coils, n_virtual):
+    """whether the coil-compression kernels serve n_coils (1..64) -> n_virtual (1..min(n_coils, 32)).  Needs no GPU."""
+    return bool(_lib.lib.ipdm_coilcomp_supported(int(n_coils), int(n_virtual)))
+
+
+def coilcomp_workspace(B, n_coils, device):
+    """scratch tensor of coil_compress (the Gram matrices); None for a shape without a kernel"""
+    nbytes = _lib.lib.ipdm_coilcomp_workspace_bytes(int(B), int(n_coils))
+    return torch.empty(nbytes // 4, dtype=torch.float32, device=device) if nbytes else None
+
+
+def _coilcomp_counts(n_coils, n_virtual, what):
+    if isinstance(n_virtual, bool) or int(n_virtual) != n_virtual:
+        raise ValueError(f"ipdm {what}: n_virtual must be an integer, got {n_virtual!r}")
+    n_virtual = int(n_virtual)
+    if n_virtual < 1 or n_virtual > n_coils:
+        raise ValueError(f"ipdm {what}: n_virtual = {n_virtual} outside 1..n_coils = {n_coils}")
+    if not coilcomp_supported(n_coils, n_virtual):
+        raise _lib.IpdmUnsupported(f"ipdm {what}: {n_coils} -> {n_virtual} coils; the kernels serve 1..64 physical and "
+                                   "1..32 virtual coils")
+    return n_virtual
+
+
+def check_noise_cov(noise_cov, n_coils, what="noise_cov"):
+    """host-side check of a noise covariance: (n_coils, n_coils), real or complex, Hermitian positive definite (float64
+    Cholesky) -> complex128 host tensor.  TypeError / ValueError before any launch."""
+    import numpy as np
+    if isinstance(noise_cov, torch.Tensor):
+        noise_cov = noise_cov.detach().cpu().numpy()
+    if not isinstance(noise_cov, np.ndarray):
+        raise TypeError(f"{what}: a torch tensor or numpy array, got {type(noise_cov).__name__}")
+    if noise_cov.dtype.kind not in "fc":
+        raise TypeError(f"{what}: a real or complex floating dtype, got {noise_cov.dtype}")
+    if noise_cov.ndim != 2 or noise_cov.shape != (n_coils, n_coils):
+        raise ValueError(f"{what}: shape {noise_cov.shape}, expected ({n_coils}, {n_coils})")
+    psi = noise_cov.astype(np.complex128)
+    if not np.isfinite(psi).all():
+        raise ValueError(f"{what}: not finite")
+    scale = float(np.abs(psi).max())
+    if not scale > 0 or float(np.abs(psi - psi.conj().T).max()) > 1e-5 * scale:
+        raise ValueError(f"{what}: not Hermitian")
+    psi = 0.5 * (psi + psi.conj().T)
+    try:
+        np.linalg.cholesky(psi)
+    except np.linalg.LinAlgError:
+        raise ValueError(f"{what}: not positive definite") from None
+    return torch.from_numpy(psi)
+
+
+def _noise_cov_dev(noise_cov, n_coils, device, what):
+    if noise_cov is None:
+        return None
+    return check_noise_cov(noise_cov, n_coils, f"ipdm {what}: noise_cov").to(torch.complex64).to(device).contiguous()
+
+
+def coil_gram(y, ah, aw, *, out=None):
+    """Gram matrices of the calibration box [H//2-ah, H//2+ah] x [W//2-aw, W//2+aw] of multi-coil k-space y ((n, H, W),
+    (n, B, H, W) or (n, B, 1, H, W) complex64): G_b[i][j] = sum y_i conj(y_j) -> (B, n, n) complex64, exactly Hermitian"""
+    n, B, H, W = _csm_measurement(y, "coil_gram")
+    ah, aw = _csm_box(ah, aw)
+    if out is None:
+        out = torch.empty((B, n, n), dtype=torch.complex64, device=y.device)
+    else:
+        _inplace_operand(out, torch.complex64, "out")
+        if tuple(out.shape) != (B, n, n):
+            raise ValueError(f"coil_gram: out {tuple(out.shape)}, expected {(B, n, n)}")
+    call("ipdm_coil_gram_c64", _ptr(y), ah, aw, _ptr(out), B, n, H, W, _stream())
+    _written(out)
+    return out
+
+
+def _c64_operand(t, name, what):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"ipdm {what}: {name} must be a GPU tensor (the HIP path has no CPU fallback)")
+    if t.dtype != torch.complex64:
+        raise TypeError(f"ipdm {what}: {name} must be complex64, got {t.dtype}")
+    if not t.is_contiguous():
+        raise TypeError(f"ipdm {what}: {name} must be contiguous (call .contiguous() and keep the result)")
+    return t
+
+
+def coilcomp_matrix(gram, n_virtual, noise_cov=None, return_eig=False):
+    """compression matrices from Gram matrices (B, n, n) or (n, n) complex64: with noise_cov psi = L L^H the Gram matrix
+    is whitened (L^-1 G L^-H); A = U[:, :n_virtual]^H (L^-1) from its eigenvectors in descending order of the eigenvalues,
+    every row turned so that its coil-0 entry is real and non-negative.  -> A (B, n_virtual, n) complex64; return_eig:
+    -> (A, eig (B, n) float32 descending, status (B,) int32, 0 = fine).  noise_cov is checked on the host (TypeError /
+    ValueError) before any launch."""
+    _c64_operand(gram, "gram", "coilcomp_matrix")
+    if gram.dim() == 2:
+        gram = gram[None]
+    if gram.dim() != 3 or gram.shape[1] != gram.shape[2]:
+        raise ValueError(f"ipdm coilcomp_matrix: gram {tuple(gram.shape)}; (B, n, n) expected")
+    B, n = gram.shape[0], gram.shape[1]
+    n_virtual = _coilcomp_counts(n, n_virtual, "coilcomp_matrix")
+    psi = _noise_cov_dev(noise_cov, n, gram.device, "coilcomp_matrix")
+    A = torch.empty((B, n_virtual, n), dtype=torch.complex64, device=gram.device)
+    eig = torch.empty((B, n), dtype=torch.float32, device=gram.device)
+    status = torch.empty(B, dtype=torch.int32, device=gram.device)
+    call("ipdm_coilcomp_matrix_c64", _ptr(gram), _ptr(psi), n_virtual, _ptr(A), _ptr(eig), _ptr(status), B, n, _stream())
+    return (A, eig, status) if return_eig else A
+
+
+def _coil_planes(y, what):
+    """-> (n, B, P): y (n, B, ...) complex64 with any trailing pixel dims"""
+    _c64_operand(y, "y", what)
+    if y.dim() < 3:
+        raise ValueError(f"ipdm {what}: y {tuple(y.shape)}; (n_coils, B, pixels...) expected")
+    n, B = y.shape[0], y.shape[1]
+    return n, B, (y.numel() // (n * B) if n * B else 0)
+
+
+def coil_apply(y, A, out=None):
+    """y'_v = sum_c A[v][c] y_c on every pixel: y (n, B, ...) complex64 (k-space, or coil maps (n, 1, H, W)), A
+    (B, nv, n) per image or (nv, n) shared by the batch, complex64 -> (nv, B, ...) complex64.  out may not overlap y."""
+    n, B, Pn = _coil_planes(y, "coil_apply")
+    _c64_operand(A, "A", "coil_apply")
+    if A.dim() not in (2, 3) or A.shape[-1] != n or (A.dim() == 3 and A.shape[0] != B):
+        raise ValueError(f"ipdm coil_apply: A {tuple(A.shape)} does not match y {tuple(y.shape)}; (B, nv, n) or (nv, n) expected")
+    nv = _coilcomp_counts(n, A.shape[-2], "coil_apply")
+    shape = (nv,) + tuple(y.shape[1:])
+    if out is None:
+        out = torch.empty(shape, dtype=torch.complex64, device=y.device)
+    else:
+        _c64_operand(out, "out", "coil_apply")
+        if tuple(out.shape) != shape:
+            raise ValueError(f"ipdm coil_apply: out {tuple(out.shape)}, expected {shape}")
+    call("ipdm_coil_apply_c64", _ptr(y), _ptr(A), int(A.dim() == 3), _ptr(out), B, n, nv, Pn, _stream())
+    _written(out)
+    return out
+
+
+def coil_compress(y, ah, aw, n_virtual, noise_cov=None, return_matrix=False, *, work=None):
+    """whitening and compression of multi-coil k-space y ((n, H, W), (n, B, H, W) or (n, B, 1, H, W) complex64) to
+    n_virtual virtual coils by PCA of its calibration box (ah, aw): Gram matrix, matrix and application in one call
+    (ipdm.h, ipdm_coil_compress_c64) -> y' of y's shape with n_virtual coils; return_matrix: -> (y', A (B, n_virtual, n),
+    eig (B, n), status (B,)).  Asynchronous; no host synchronisation."""
+    n, B, H, W = _csm_measurement(y, "coil_compress")
+    ah, aw = _csm_box(ah, aw)
+    n_virtual = _coilcomp_counts(n, n_virtual, "coil_compress")
+    psi = _noise_cov_dev(noise_cov, n, y.device, "coil_compress")
+    need = _lib.lib.ipdm_coilcomp_workspace_bytes(B, n)
+    if work is None:
+        work = coilcomp_workspace(B, n, y.device)
+    elif (not isinstance(work, torch.Tensor) or not work.is_cuda or work.dtype != torch.float32 or not work.is_contiguous()
+            or work.numel() * 4 < need):
+        raise ValueError(f"coil_compress: `work` must be a contiguous float32 GPU tensor of >= {need} bytes "
+                         f"(ops.coilcomp_workspace({B}, {n}, device))")
+    out = torch.empty((n_virtual,) + tuple(y.shape[1:]), dtype=torch.complex64, device=y.device)
+    A = torch.empty((B, n_virtual, n), dtype=torch.complex64, device=y.device)
+    eig = torch.empty((B, n), dtype=torch.float32, device=y.device)
+    status = torch.empty(B, dtype=torch.int32, device=y.device)
+    call("ipdm_coil_compress_c64", _ptr(y), ah, aw, n_virtual, _ptr(psi), _ptr(A), _ptr(eig), _ptr(status), _ptr(out), _ptr(work),
+         B, n, H, W, _stream())
+    return (out, A, eig, status) if return_matrix else out
+
+
 SC_L2PENALTY, SC_CLOSED_FORM, SC_PROJECTION = 0, 1, 2
 
 

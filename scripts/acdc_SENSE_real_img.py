@@ -4,7 +4,8 @@
 reconstructions.pt, ZF.pt, mask.pt, args_dict.pkl).  Data and weights are synthetic (phantom + seeded weights)
 unless --ckpt points at a Lightning checkpoint of the reference and --kspace at measured multi-coil k-space (with its
 --mask; no ground truth then: original.pt and the RMSE line are skipped); --estimate_maps takes the coil maps from the
-measurement's own calibration region (sens_maps.pt).  Samples are sharded over the launched ranks (torchrun) and rank 0
+measurement's own calibration region (sens_maps.pt); --coil_compress N whitens (--noise_cov PATH) and compresses the
+measurement to N virtual coils first (coil_matrix.pt).  Samples are sharded over the launched ranks (torchrun) and rank 0
 writes the posterior mean / std next to the reconstructions."""
 import argparse
 import os
@@ -63,6 +64,11 @@ if __name__ == '__main__':
     parser.add_argument("--estimate_maps", action="store_true",
                         help="estimate the coil maps from the fully sampled calibration region of the measurement")
     parser.add_argument("--calib_max", type=int, default=12, help="--estimate_maps: largest calibration half-width")
+    parser.add_argument("--coil_compress", type=int, default=None, metavar="N",
+                        help="whiten and compress the measurement (up to 64 coils) to N <= 32 virtual coils by PCA of its "
+                             "calibration region; the maps are estimated on, or compressed to, the virtual coils")
+    parser.add_argument("--noise_cov", default=None,
+                        help="--coil_compress: .npy / .pt file with the (n_coils, n_coils) coil noise covariance of the prescan")
     parser.add_argument("--kspace_scale", default="auto",
                         help="--kspace: factor on the measurement; auto: 1 / the peak of its calibration image")
     parser.add_argument("--seg_synthetic", action="store_true",
@@ -91,14 +97,25 @@ if __name__ == '__main__':
     # the mask, and the calibration region the run depends on, before the score network is built or a GPU is touched
     from inverseproblemwithdiffusionmodel_amd.helpers.load_data import driver_mask
     mask = driver_mask(args_dict["mask"], args_dict["mask_2d"], H, W, args_dict["R"], args_dict["seed"])
-    if args_dict["estimate_maps"] or (kspace is not None and kspace_scale is None):
+    noise_cov = None
+    if args_dict["noise_cov"] and args_dict["coil_compress"] is None:
+        sys.exit("--noise_cov PATH goes with --coil_compress N (whitening is part of the compression)")
+    if args_dict["coil_compress"] is not None:                            # a bad N or a bad covariance fails here
+        from inverseproblemwithdiffusionmodel_amd.helpers.load_data import load_noise_cov
+        try:
+            ops._coilcomp_counts(args_dict["num_sens"], args_dict["coil_compress"], "--coil_compress")
+            if args_dict["noise_cov"]:
+                noise_cov = ops.check_noise_cov(load_noise_cov(args_dict["noise_cov"]), args_dict["num_sens"], "--noise_cov")
+        except (ValueError, TypeError, NotImplementedError) as e:
+            sys.exit(str(e))
+    if args_dict["estimate_maps"] or args_dict["coil_compress"] is not None or (kspace is not None and kspace_scale is None):
         from inverseproblemwithdiffusionmodel_amd.ncsn.linear_transforms import undersampling_fourier as uf
         try:
             uf.calibration_region(mask if mask is not None else
                                   uf.RandomUndersamplingFourier(args_dict["R"], 0.04, (1, H, W), args_dict["seed"]).mask,
                                   H, W, args_dict["calib_max"])
         except ValueError as e:
-            sys.exit(f"--estimate_maps / --kspace: {e}")
+            sys.exit(f"--estimate_maps / --coil_compress / --kspace: {e}")
     from inverseproblemwithdiffusionmodel_amd import engine, sharding
     world, rank, device = sharding.init_distributed()
     from inverseproblemwithdiffusionmodel_amd.helpers.load_model import load_scorenet_weights
@@ -123,6 +140,7 @@ if __name__ == '__main__':
                                 seed=args_dict["seed"], scorenet=scorenet, cfg=cfg, lr_scaled=args_dict["lr_scaled"],
                                 sens_maps=sens_maps, mask=mask, estimate_maps=args_dict["estimate_maps"], measurement=kspace,
                                 calib_max=args_dict["calib_max"], kspace_scale=kspace_scale,
+                                coil_compress=args_dict["coil_compress"], noise_cov=noise_cov,
                                 proximal=args_dict["proximal_type"],
                                 proximal_kwargs=(dict(max_iter=args_dict["cg_iters"], tol=args_dict["cg_tol"])
                                                  if args_dict["proximal_type"] == "L2PenaltyCG" else None))
@@ -169,8 +187,10 @@ if __name__ == '__main__':
         torch.save(img_out.cpu(), os.path.join(save_dir, "reconstructions.pt"))
         torch.save(direct_recons.cpu(), os.path.join(save_dir, "ZF.pt"))
         torch.save(prob.op.random_under_fourier.mask, os.path.join(save_dir, "mask.pt"))
-        if sens_maps is not None or prob.estimated_maps:
+        if sens_maps is not None or prob.estimated_maps or prob.coil_matrix is not None:
             torch.save(prob.op.sens_maps, os.path.join(save_dir, "sens_maps.pt"))
+        if prob.coil_matrix is not None:
+            torch.save(prob.coil_matrix, os.path.join(save_dir, "coil_matrix.pt"))
         if post is not None:
             torch.save({k: v.cpu() for k, v in post.items()}, os.path.join(save_dir, "posterior.pt"))
         with open(os.path.join(save_dir, "args_dict.pkl"), "wb") as wf:
