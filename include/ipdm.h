@@ -305,6 +305,20 @@ int ipdm_coil_apply_c64(const float* y, const float* A, int per_image, float* ou
 int ipdm_coil_compress_c64(const float* y, int ah, int aw, int n_virtual, const float* noise_cov, float* A, float* eig,
                            int32_t* status, float* out, float* work, int B, int n_coils, int H, int W, void* stream);
 
+/* Mask-weighted time average of 2D+time multi-coil k-space: the composite a cine acquisition is calibrated from (its
+ * interleaved per-frame patterns together sample the centre fully; maps and compression matrix come from the composite
+ * and are shared by the frames).  y [n_coils][B][T][H][W] c64 (the cine measurement (n, B, T, 1, H, W)); mask / mask_t as
+ * for the SENSE operators, frame t of image b using plane (b*T + t) % |mask_t| -- what those operators apply to the
+ * flattened (B*T) stack.  count [B][H][W] int32 (or NULL): the number of frames that sampled the pixel; ybar
+ * [n_coils][B][H][W] c64: the sum of y over those frames, in frame order, divided by count -- summed and divided in double,
+ * rounded once -- and exactly 0 where count == 0.  y is read at sampled positions only (a NaN elsewhere never reaches the
+ * output).  Any H, W, n_coils, B >= 1 (B == 0: IPDM_OK, nothing launched; B above 65535 is folded), 1 <= T <= 4096
+ * (above: IPDM_EUNSUPPORTED); IPDM_EINVAL: a non-positive size, mask_t == 0, a NULL y / mask / ybar, ybar overlapping y.
+ * Asynchronous, allocation-free, hipGraph-capturable, no atomics: a pixel's result depends on its own frames alone.  y and
+ * ybar may sit on any 8-byte boundary (count: 4). */
+int ipdm_kspace_tavg_c64(const float* y, const uint8_t* mask, int mask_t, float* ybar, int32_t* count, int B, int T,
+                         int n_coils, int H, int W, void* stream);
+
 /* Single-coil data-consistency operators (A = M F, RandomUndersamplingFourier, no coil maps) on planar real/imag
  * float32 [B][H][W], y [B][H][W] complex64; out may alias z.  mode:
  *   0  L2Penalty on a single-coil operator (proximal_op.py:19-51): x = z - coef * F^-1[M (M F z - y)],

@@ -68,6 +68,7 @@ SIGNATURES = {
     "ipdm_coilcomp_matrix_c64": [P, P, c_int, P, P, P, c_int, c_int, P],
     "ipdm_coil_apply_c64": [P, P, c_int, P, c_int, c_int, c_int, c_int64, P],
     "ipdm_coil_compress_c64": [P, c_int, c_int, c_int, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P],
+    "ipdm_kspace_tavg_c64": [P, P, c_int, P, P, c_int, c_int, c_int, c_int, c_int, P],
     "ipdm_singlecoil_prox_f32": [P, P, P, P, c_int, c_float, c_int, P, P, P, c_int, c_int, c_int, P],
     "ipdm_ald_singlecoil_step_f32": [P, P, P, P, P, P, c_float, c_float, c_uint64, c_int64, c_int64, P,
                                      P, P, c_int, c_float, c_int, P, c_int, c_int, c_int, P],

@@ -225,10 +225,11 @@ def load_sens_maps(path):
     return maps.to(torch.complex128 if maps.is_complex() else torch.float64)
 
 
-def load_kspace(path):
-    """measured multi-coil k-space (n_coils, H, W) from a ``.npy`` or ``.pt`` file -> host complex64 tensor, centred with
-    orthonormal scale as ``SENSE.__call__`` produces it (``engine.build_problem(measurement=...)``); any other rank or a
-    real dtype is a ValueError"""
+def load_kspace(path, cine=False):
+    """measured multi-coil k-space (n_coils, H, W) -- cine=True: 2D+time k-space (n_coils, T, H, W) -- from a ``.npy`` or
+    ``.pt`` file -> host complex64 tensor, centred with orthonormal scale as ``SENSE.__call__`` produces it
+    (``engine.build_problem(measurement=...)``, ``SENSE.from_cine_measurement``); any other rank or a real dtype is a
+    ValueError"""
     import numpy as np
     import torch
     ext = os.path.splitext(str(path))[1].lower()
@@ -240,8 +241,9 @@ def load_kspace(path):
             y = torch.from_numpy(y)
     else:
         raise ValueError(f"load_kspace: {path!r}: a .npy or .pt file")
-    if not isinstance(y, torch.Tensor) or y.dim() != 3:
-        raise ValueError(f"load_kspace: {path!r} must hold one array of shape (n_coils, H, W)")
+    if not isinstance(y, torch.Tensor) or y.dim() != (4 if cine else 3):
+        raise ValueError(f"load_kspace: {path!r} must hold one array of shape "
+                         f"{'(n_coils, T, H, W)' if cine else '(n_coils, H, W)'}")
     if not y.is_complex():
         raise ValueError(f"load_kspace: {path!r} holds {y.dtype}; complex k-space expected")
     return y.to(torch.complex64).contiguous()
@@ -326,3 +328,97 @@ def driver_sens_maps(path, sens_phase, num_sens, H, W, seed):
         from ..synthetic import complex_coil_maps
         return complex_coil_maps(num_sens, H, W, seed), num_sens
     return None, num_sens
+
+
+def add_cine_measurement_args(parser):
+    """the cine drivers' measured-data flags, with the meanings scripts/acdc_SENSE_real_img.py gives them"""
+    parser.add_argument("--kspace", default=None,
+                        help=".npy / .pt file with measured 2D+time multi-coil k-space (n_coils, T, H, W), complex, centred "
+                             "with orthonormal scale; sets T and the coil count, needs --mask PATH and --estimate_maps")
+    parser.add_argument("--estimate_maps", action="store_true",
+                        help="estimate the coil maps from the calibration region of the time-averaged measurement")
+    parser.add_argument("--calib_max", type=int, default=12, help="--estimate_maps: largest calibration half-width")
+    parser.add_argument("--coil_compress", type=int, default=None, metavar="N",
+                        help="whiten and compress the measurement (up to 64 coils) to N <= 32 virtual coils by PCA of the "
+                             "calibration region of its time average: one matrix for all frames; needs --estimate_maps")
+    parser.add_argument("--noise_cov", default=None,
+                        help="--coil_compress: .npy / .pt file with the (n_coils, n_coils) coil noise covariance of the prescan")
+    parser.add_argument("--kspace_scale", default="auto",
+                        help="--kspace: factor on the measurement; auto: 1 / the peak of its composite calibration image")
+
+
+def cine_measurement_requested(a):
+    """whether any of add_cine_measurement_args' flags asks for the calibrated path (a: the parsed Namespace)"""
+    return bool(a.kspace or a.estimate_maps or a.coil_compress is not None or a.noise_cov)
+
+
+def driver_cine_checks(a, H, W, T, num_sens, mask):
+    """host-side part of the cine drivers' calibrated path, run before a score network is built or a GPU touched: flag
+    combinations, the measured file, the compression arguments and the composite calibration region; every failure is a
+    ``sys.exit`` with the message scripts/acdc_SENSE_real_img.py gives.  a: the parsed flags (kspace, mask, sens_maps,
+    sens_phase, estimate_maps, calib_max, coil_compress, noise_cov, kspace_scale, R, seed); mask: what driver_mask
+    returned.  -> Namespace(kspace (n, T, H, W) or None, H, W, T, num_sens, noise_cov, kspace_scale (float or None))"""
+    import sys
+    from argparse import Namespace
+    from .. import ops
+    from ..ncsn.linear_transforms import undersampling_fourier as uf
+    kspace = None
+    if a.kspace:
+        if not a.mask:
+            sys.exit("--kspace PATH needs --mask PATH, the sampling mask of the acquisition")
+        if a.sens_maps or a.sens_phase or not a.estimate_maps:
+            sys.exit("--kspace PATH takes its coil maps from --estimate_maps (the time-averaged calibration region)")
+        try:
+            kspace = load_kspace(a.kspace, cine=True)
+        except (ValueError, TypeError) as e:
+            sys.exit(str(e))
+        num_sens, T, H, W = (int(s) for s in kspace.shape)
+    if a.noise_cov and a.coil_compress is None:
+        sys.exit("--noise_cov PATH goes with --coil_compress N (whitening is part of the compression)")
+    if a.coil_compress is not None and not a.estimate_maps:
+        sys.exit("--coil_compress N needs --estimate_maps (the maps of the virtual coils come from the composite)")
+    if ops.kspace_size_class(H, W) == ops.KSPACE_NONE:
+        sys.exit(f"{H}x{W}: no k-space kernel for this size; {ops.KSPACE_SIZE_RULE}")
+    noise_cov = None
+    if a.coil_compress is not None:                                        # a bad N or a bad covariance fails here
+        try:
+            ops._coilcomp_counts(num_sens, a.coil_compress, "--coil_compress")
+            if a.noise_cov:
+                noise_cov = ops.check_noise_cov(load_noise_cov(a.noise_cov), num_sens, "--noise_cov")
+        except (ValueError, TypeError, NotImplementedError) as e:
+            sys.exit(str(e))
+    if mask is None:
+        mask = uf.RandomUndersamplingFourier(a.R, 0.04, (1, H, W), a.seed, mask_T=24 if T == 24 else 1).mask
+    try:
+        if kspace is not None:
+            uf.SENSE._cine_operands(kspace, mask, "--kspace / --mask")
+        uf.calibration_region(mask, H, W, a.calib_max, composite=True)
+    except (ValueError, TypeError) as e:
+        sys.exit(f"--estimate_maps / --coil_compress / --kspace: {e}")
+    return Namespace(kspace=kspace, H=H, W=W, T=T, num_sens=num_sens, noise_cov=noise_cov,
+                     kspace_scale=None if a.kspace_scale == "auto" else float(a.kspace_scale))
+
+
+def driver_cine_measurement(a, checked, op, frames, device):
+    """GPU part of the cine drivers' calibrated path: the measurement -- the file's, or frames (T, C, H, W) simulated
+    through `op` with its true maps -- calibrated by ``SENSE.from_cine_measurement`` (time-averaged composite, one
+    compression matrix for all frames, maps of the composite).  checked: driver_cine_checks' result.
+    -> (from_cine_measurement's Namespace with `measurement` scaled and `kspace_scale` added (None for simulated data),
+    the operator to reconstruct with)"""
+    from ..ncsn.linear_transforms.undersampling_fourier import SENSE
+    if checked.kspace is not None:
+        y, mask = checked.kspace.to(device), driver_mask(a.mask, False, checked.H, checked.W, a.R, a.seed)
+    else:
+        y = op(frames).reshape(op.num_sens, checked.T, checked.H, checked.W)
+        mask = op.random_under_fourier.mask
+    cal = SENSE.from_cine_measurement(y, mask, R=a.R, seed=a.seed, calib_max=a.calib_max, n_virtual=a.coil_compress,
+                                      noise_cov=checked.noise_cov)
+    cal.kspace_scale = None
+    if checked.kspace is not None:
+        cal.kspace_scale = checked.kspace_scale
+        if cal.kspace_scale is None:
+            if not cal.rss_max > 0.0:
+                raise ValueError("--kspace: the calibration region of the time-averaged measurement holds no signal")
+            cal.kspace_scale = 1.0 / cal.rss_max
+        cal.measurement = cal.measurement * cal.kspace_scale
+    return cal, cal.op

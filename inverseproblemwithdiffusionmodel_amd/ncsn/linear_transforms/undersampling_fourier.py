@@ -37,20 +37,10 @@ def _check_gpu(t, what):
         raise RuntimeError(f"{what}: expected a GPU tensor (no CPU fallback in this build)")
 
 
-def calibration_region(mask, H, W, calib_max=12):
-    """-> (ah, aw), the half-widths of the calibration box [H//2-ah, H//2+ah] x [W//2-aw, W//2+aw] the coil-map estimator
-    works from: symmetric about DC, fully sampled in every frame of `mask` (any shape ``ops._mask_u8`` takes; a line mask
-    is fully sampled along H), each half-width at most min(N//2, N-1-N//2, calib_max).  Of the fully sampled candidates
-    the largest area wins; ties go to the smaller |ah - aw|, then to the larger aw.  ValueError, naming the sampled centre
-    it found, when ah < 2 or aw < 2 (the generated R = 40 line mask keeps the two adjacent centre lines W//2 - 1 and
-    W//2, so the box symmetric about W//2 has aw = 0 and the mask is refused this way).  Host only."""
-    if isinstance(calib_max, bool) or int(calib_max) != calib_max or calib_max < 0:
-        raise ValueError(f"calibration_region: calib_max must be an integer >= 0, got {calib_max}")
-    m = ops._mask_u8(mask, H, W, "cpu")
-    full = m.bool().all(dim=0)                                  # every frame must have sampled the box
-    if full.dim() == 1:                                         # a line mask [W]: every row is sampled
-        full = full.reshape(1, W).expand(H, W)
-    full = full.numpy()
+def _largest_box(full, H, W, calib_max):
+    """-> (ah, aw) of the largest box symmetric about (H//2, W//2) inside which the host bool array `full` (H, W) is True
+    everywhere, each half-width at most min(N//2, N-1-N//2, calib_max); ties go to the smaller |ah - aw|, then to the
+    larger aw.  None when the centre itself is False."""
     # prefix sums: box (ah, aw) is fully sampled iff its count equals its area
     cs = np.zeros((H + 1, W + 1), dtype=np.int64)
     cs[1:, 1:] = np.cumsum(np.cumsum(full, axis=0), axis=1)
@@ -65,15 +55,53 @@ def calibration_region(mask, H, W, calib_max=12):
             key = (area, -abs(ah - aw), aw)
             if best is None or key > best[0]:
                 best = (key, ah, aw)
+    return None if best is None else best[1:]
+
+
+def _sampled_planes(mask, H, W, union):
+    """host bool (H, W): where every plane (union: at least one plane) of the mask sampled; a line mask covers every row"""
+    m = ops._mask_u8(mask, H, W, "cpu").bool()
+    full = m.any(dim=0) if union else m.all(dim=0)
+    if full.dim() == 1:                                         # a line mask [W]: every row is sampled
+        full = full.reshape(1, W).expand(H, W)
+    return full.numpy(), m.shape[0]
+
+
+def calibration_region(mask, H, W, calib_max=12, composite=False):
+    """-> (ah, aw), the half-widths of the calibration box [H//2-ah, H//2+ah] x [W//2-aw, W//2+aw] the coil-map estimator
+    works from: symmetric about DC, fully sampled in every frame of `mask` (any shape ``ops._mask_u8`` takes; a line mask
+    is fully sampled along H), each half-width at most min(N//2, N-1-N//2, calib_max).  Of the fully sampled candidates
+    the largest area wins; ties go to the smaller |ah - aw|, then to the larger aw.  ValueError, naming the sampled centre
+    it found, when ah < 2 or aw < 2 (the generated R = 40 line mask keeps the two adjacent centre lines W//2 - 1 and
+    W//2, so the box symmetric about W//2 has aw = 0 and the mask is refused this way).  composite=True: the box of the
+    time-averaged composite of a cine acquisition (``ops.kspace_time_average``), sampled at every position in AT LEAST ONE
+    frame -- interleaved per-frame patterns share little more than the centre line, their union is what such acquisitions
+    calibrate from.  Host only."""
+    if isinstance(calib_max, bool) or int(calib_max) != calib_max or calib_max < 0:
+        raise ValueError(f"calibration_region: calib_max must be an integer >= 0, got {calib_max}")
+    full, planes = _sampled_planes(mask, H, W, union=bool(composite))
+    best = _largest_box(full, H, W, calib_max)
+    hint = ""
+    if not composite and planes > 1 and (best is None or min(best) < 2):
+        both = _largest_box(_sampled_planes(mask, H, W, union=True)[0], H, W, calib_max)
+        if both is not None and min(both) >= 2:
+            hint = (f"; the union of its {planes} frames is fully sampled on {2 * both[0] + 1} x {2 * both[1] + 1}: for a cine "
+                    "acquisition calibrate from the time-averaged composite (composite=True)")
     if best is None:
-        raise ValueError(f"calibration region: the k-space centre ({ch}, {cw}) of the {H}x{W} mask is not sampled in every "
-                         "frame; coil maps cannot be estimated from this acquisition")
-    _, ah, aw = best
+        raise ValueError(f"calibration region: the k-space centre ({H // 2}, {W // 2}) of the {H}x{W} mask is not sampled in "
+                         f"{'any' if composite else 'every'} frame; coil maps cannot be estimated from this acquisition{hint}")
+    ah, aw = best
     if ah < 2 or aw < 2:
         raise ValueError(f"calibration region: the fully sampled centre of the {H}x{W} mask is {2 * ah + 1} x {2 * aw + 1} "
                          f"samples (half-widths ah = {ah}, aw = {aw}); the coil-map estimator needs at least 5 x 5 "
-                         "(ah >= 2 and aw >= 2): acquire more centre lines, or pass measured maps (sens_maps=)")
+                         f"(ah >= 2 and aw >= 2): acquire more centre lines, or pass measured maps (sens_maps=){hint}")
     return ah, aw
+
+
+def composite_mask(mask, H, W):
+    """-> host bool tensor, (W,) for a line mask and (H, W) for a 2-D mask: the union over the frames of `mask` (any shape
+    ``ops._mask_u8`` takes), where the time-averaged composite of a cine acquisition holds data"""
+    return ops._mask_u8(mask, H, W, "cpu").bool().any(dim=0)
 
 
 class UndersamplingFourier(LinearTransform):
@@ -275,6 +303,77 @@ class SENSE(LinearTransform):
         maps = cls.estimate_sens_maps(y, mask, calib_max=calib_max, **kw)
         n, H, W = maps.shape
         return cls("custom", n, R, 0.04, (1, H, W), seed, mask_mode="custom", mask=mask, sens_maps=maps, normalize=False)
+
+    @staticmethod
+    def _cine_operands(y, mask, what):
+        """host-side normalisation of a cine measurement and its mask -> (y (n, T, H, W) complex tensor, mask as the
+        operator takes it, planes): singleton batch / channel dims of a saved (n, 1, T, 1, H, W) measurement are dropped, a
+        (T, H, W) mask stack becomes (T, 1, H, W), the mask has one plane or one per frame.  TypeError / ValueError."""
+        if not isinstance(y, (torch.Tensor, np.ndarray)):
+            raise TypeError(f"{what}: y must be a torch tensor or numpy array, got {type(y).__name__}")
+        y = torch.as_tensor(y).detach()
+        if not y.is_complex():
+            raise TypeError(f"{what}: y must be complex k-space, got {y.dtype}")
+        if y.dim() == 6 and y.shape[1] == 1 and y.shape[3] == 1:
+            y = y.reshape(y.shape[0], y.shape[2], y.shape[4], y.shape[5])
+        elif y.dim() == 5 and (y.shape[1] == 1 or y.shape[2] == 1):
+            y = y.reshape(y.shape[0], y.shape[2] if y.shape[1] == 1 else y.shape[1], y.shape[3], y.shape[4])
+        if y.dim() != 4 or min(y.shape) < 1:
+            raise ValueError(f"{what}: y {tuple(y.shape)}; (n_coils, T, H, W) expected")
+        n, T, H, W = y.shape
+        if not isinstance(mask, (torch.Tensor, np.ndarray)):
+            raise TypeError(f"{what}: mask must be a torch tensor or numpy array, got {type(mask).__name__}")
+        mask = torch.as_tensor(mask).detach().cpu()
+        if mask.dim() == 3 and tuple(mask.shape[-2:]) == (H, W) and mask.shape[0] != 1:
+            mask = mask[:, None]                                            # per-frame 2-D masks, as driver_mask
+        planes = ops._mask_u8(mask, H, W, "cpu").shape[0]
+        if planes not in (1, T):
+            raise ValueError(f"{what}: the mask has {planes} planes for {T} frames; one plane, or one per frame")
+        return y, mask, planes
+
+    @staticmethod
+    def time_average(y, mask):
+        """the time-averaged composite of a cine measurement: y (n, T, H, W) complex k-space (tensor or ndarray, host or
+        GPU; singleton batch / channel dims dropped), mask its sampling mask with one plane or T (anything ``ops._mask_u8``
+        takes, or (T, H, W)).  ``ops.kspace_time_average`` on the current GPU -> ybar (n, H, W) complex64 on the GPU: the
+        mean over the frames that sampled each position, zero where none did."""
+        y, mask, _ = SENSE._cine_operands(y, mask, "time_average")
+        yd = y.to(torch.complex64).to(y.device if y.is_cuda else "cuda").contiguous()
+        return ops.kspace_time_average(yd, ops._mask_u8(mask, y.shape[-2], y.shape[-1], yd.device))
+
+    @classmethod
+    def from_cine_measurement(cls, y, mask, R=1, seed=None, calib_max=12, n_virtual=None, noise_cov=None, **kw):
+        """the ``"custom"`` operator of a 2D+time acquisition, calibrated from its time-averaged composite: y (n, T, H, W)
+        multi-coil k-space and its per-frame sampling mask, as for ``time_average``.  The calibration box is
+        ``calibration_region(mask, H, W, calib_max, composite=True)``; with n_virtual ONE compression matrix
+        (``ops.coilcomp_matrix`` of the composite's Gram matrix, whitened with noise_cov) is applied to every frame and to
+        the composite; the maps are those of the (virtual) coils of the composite (``ops.estimate_sens_maps``; kw goes to
+        the estimator) and serve every frame.  -> Namespace(op, measurement (n', T, H, W) complex64 on the GPU, sens_maps
+        (n', H, W) complex128 on the host, coil_matrix (n', n) complex64 on the host or None, region (ah, aw), rss_max (the
+        peak of the composite's calibration image), composite (n', H, W) complex64 on the GPU).  Every argument is
+        checked on the host before any GPU work."""
+        from argparse import Namespace
+        y, mask, planes = cls._cine_operands(y, mask, "from_cine_measurement")
+        n, T, H, W = y.shape
+        if n_virtual is not None:
+            n_virtual = ops._coilcomp_counts(n, n_virtual, "from_cine_measurement")
+            if noise_cov is not None:
+                noise_cov = ops.check_noise_cov(noise_cov, n, "from_cine_measurement: noise_cov")
+        elif noise_cov is not None:
+            raise ValueError("from_cine_measurement: noise_cov= goes with n_virtual= (whitening is part of the compression)")
+        ah, aw = calibration_region(mask, H, W, calib_max, composite=True)
+        yd = y.to(torch.complex64).to(y.device if y.is_cuda else "cuda").contiguous()
+        ybar = ops.kspace_time_average(yd, ops._mask_u8(mask, H, W, yd.device))
+        A = None
+        if n_virtual is not None:
+            A = ops.coilcomp_matrix(ops.coil_gram(ybar, ah, aw), n_virtual, noise_cov)[0]
+            yd, ybar = ops.coil_apply(yd, A), ops.coil_apply(ybar, A)
+        maps, _, rss_max = ops.estimate_sens_maps(ybar, ah, aw, return_rss=True, **kw)
+        maps = maps.cpu().to(torch.complex128)
+        op = cls("custom", maps.shape[0], R, 0.04, (1, H, W), seed, mask_T=planes, mask_mode="custom", mask=mask, sens_maps=maps,
+                 normalize=False)
+        return Namespace(op=op, measurement=yd, sens_maps=op.sens_maps, coil_matrix=None if A is None else A.cpu(),
+                         region=(ah, aw), rss_max=float(rss_max[0]), composite=ybar)
 
     @staticmethod
     def _as_host_maps(maps):

@@ -641,6 +641,53 @@ def coil_compress(y, ah, aw, n_virtual, noise_cov=None, return_matrix=False, *, 
     return (out, A, eig, status) if return_matrix else out
 
 
+# ---- mask-weighted time average of 2D+time k-space (csrc/kspace_tavg.hip) ------------------------------------------------
+TAVG_MAX_FRAMES = 4096
+
+
+def _cine_measurement(y, what):
+    """-> (n_coils, B, T, H, W, batched) of a cine measurement (n, T, H, W), (n, B, T, H, W) or (n, B, T, 1, H, W):
+    complex64, contiguous, on the GPU; read through a raw pointer, so never converted"""
+    if not isinstance(y, torch.Tensor) or not y.is_cuda:
+        raise RuntimeError(f"ipdm {what}: y must be a GPU tensor (the HIP path has no CPU fallback)")
+    if y.dtype != torch.complex64:
+        raise TypeError(f"ipdm {what}: y must be complex64, got {y.dtype}")
+    if not y.is_contiguous():
+        raise TypeError(f"ipdm {what}: y must be contiguous (call .contiguous() and keep the result)")
+    shape = tuple(y.shape)
+    if len(shape) == 4:
+        return shape[0], 1, shape[1], shape[2], shape[3], False
+    if len(shape) == 5 or (len(shape) == 6 and shape[3] == 1):
+        return shape[0], shape[1], shape[2], shape[-2], shape[-1], True
+    raise ValueError(f"ipdm {what}: y {shape} is none of (n, T, H, W), (n, B, T, H, W), (n, B, T, 1, H, W)")
+
+
+def kspace_time_average(y, mask_u8, return_count=False, *, out=None):
+    """the time-averaged composite of a cine measurement y ((n, T, H, W), (n, B, T, H, W) or (n, B, T, 1, H, W) complex64)
+    under its per-frame sampling mask (a device table of ops._mask_u8; frame t of image b uses plane (b*T + t) % planes, as
+    the SENSE operators on the flattened (B*T) stack): ybar = (sum of y over the frames that sampled the pixel) / count,
+    exactly 0 where no frame did; y is read at sampled positions only (ipdm.h, ipdm_kspace_tavg_c64).  -> ybar with T
+    dropped, (n, H, W) or (n, B, H, W) complex64; return_count: -> (ybar, count (B, H, W) int32).  Asynchronous; no host
+    synchronisation."""
+    n, B, T, H, W, batched = _cine_measurement(y, "kspace_time_average")
+    mask_t = _mask_t(mask_u8, H, W, "kspace_time_average")
+    if min(n, T, H, W) < 1:
+        raise ValueError(f"ipdm kspace_time_average: y {tuple(y.shape)} has an empty dimension")
+    if T > TAVG_MAX_FRAMES:
+        raise _lib.IpdmUnsupported(f"ipdm kspace_time_average: T = {T} frames; the kernel serves 1..{TAVG_MAX_FRAMES}")
+    shape = (n, B, H, W) if batched else (n, H, W)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.complex64, device=y.device)
+    else:
+        _c64_operand(out, "out", "kspace_time_average")
+        if tuple(out.shape) != shape:
+            raise ValueError(f"ipdm kspace_time_average: out {tuple(out.shape)}, expected {shape}")
+    count = torch.empty((B, H, W), dtype=torch.int32, device=y.device) if return_count else None
+    call("ipdm_kspace_tavg_c64", _ptr(y), _ptr(mask_u8), mask_t, _ptr(out), _ptr(count), B, T, n, H, W, _stream())
+    _written(out)
+    return (out, count) if return_count else out
+
+
 SC_L2PENALTY, SC_CLOSED_FORM, SC_PROJECTION = 0, 1, 2
 
 

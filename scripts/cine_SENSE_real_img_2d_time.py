@@ -2,7 +2,10 @@
 """2D+time ALD reconstruction on synthetic k-space (counterpart of the reference's
 ``scripts/cine_SENSE_real_img_2d_time.py``, BASELINE config 4): spatial NCSNv2Deepest prior + temporal
 NCSN3DShallow prior on 8x8xT patches (`--temporal_type Diffusion1D`: NCSN1D on the same patches as (kx*ky, T) sequences), SENSE with the T=24 mask.  Same flags; prints `reconstruction time` as the
-reference does.  Under torchrun the `--num_samples` posterior samples are block-partitioned over the ranks (Philox noise
+reference does.  --kspace PATH reconstructs measured 2D+time k-space (n, T, H, W) with its --mask PATH (no ground truth: original.pt
+is skipped); --estimate_maps calibrates from the time-averaged composite of the per-frame patterns (sens_maps.pt), --coil_compress N
+whitens (--noise_cov PATH) and compresses all frames with one matrix first (coil_matrix.pt); both also run on the simulated
+measurement.  Under torchrun the `--num_samples` posterior samples are block-partitioned over the ranks (Philox noise
 keyed by the global sample id, the per-step random shift drawn from identically seeded host generators), rank 0 writes the
 artefacts and the posterior mean / std: the result does not depend on the number of ranks."""
 import argparse
@@ -55,9 +58,20 @@ if __name__ == '__main__':
                              "per frame as (T, 1, 1, W), (T, 1, H, W) or (T, H, W)")
     parser.add_argument("--mask_2d", action="store_true",
                         help="synthetic variable-density 2-D (ky, kz) sampling mask at --R instead of the line mask")
+    from inverseproblemwithdiffusionmodel_amd.helpers import load_data
+    load_data.add_cine_measurement_args(parser)
     a = parser.parse_args()
     H, W = a.image_size, a.image_size if a.image_width is None else a.image_width
     from inverseproblemwithdiffusionmodel_amd import ops
+    checked = None
+    if load_data.cine_measurement_requested(a):       # the file, the flags and the calibration region, before any model is built
+        try:
+            cal_mask = load_data.driver_mask(a.mask, a.mask_2d, H, W, a.R, a.seed) if not a.kspace else (
+                load_data.load_mask(a.mask) if a.mask else None)
+        except (ValueError, TypeError) as e:
+            sys.exit(str(e))
+        checked = load_data.driver_cine_checks(a, H, W, a.T, a.num_sens, cal_mask)
+        H, W, a.T, a.num_sens = checked.H, checked.W, checked.T, checked.num_sens
     if ops.kspace_size_class(H, W) == ops.KSPACE_NONE:                    # before any allocation
         sys.exit(f"--image_size {H} --image_width {W}: no k-space kernel for {H}x{W}; {ops.KSPACE_SIZE_RULE}")
     from inverseproblemwithdiffusionmodel_amd.helpers.load_model import reload_model
@@ -76,17 +90,26 @@ if __name__ == '__main__':
     scorenet_T = reload_model(a.temporal_type, "CINE127", device=device)
     sigmas = get_sigmas(scorenet.config, "recons")
     sigmas_T = get_sigmas(scorenet_T.config, "recons")
-    sens_maps, a.num_sens = driver_sens_maps(a.sens_maps, a.sens_phase, a.num_sens, H, W, a.seed)
+    sens_maps = None
+    if checked is None or checked.kspace is None:
+        sens_maps, a.num_sens = driver_sens_maps(a.sens_maps, a.sens_phase, a.num_sens, H, W, a.seed)
     op = SENSE(a.sens_type, a.num_sens, a.R, a.center_lines_frac, (1, H, W), a.seed, mask_T=24 if a.T == 24 else 1)
     if sens_maps is not None:
         op.sens_maps = sens_maps
     mask = driver_mask(a.mask, a.mask_2d, H, W, a.R, a.seed)
     if mask is not None:
         op.random_under_fourier.mask = mask
-    base = phantom_image(H, W, seed=a.seed).to(device)
-    beat = torch.cos(torch.arange(a.T, device=device) * (2 * torch.pi / a.T)).view(a.T, 1, 1, 1)
-    frames = base * (1.0 + 0.1 * beat)                                     # (T, 1, H, W): a slowly pulsating phantom
-    meas = op(frames).reshape(a.num_sens, 1, a.T, 1, H, W).repeat(1, n_local, 1, 1, 1, 1)
+    frames, cal = None, None
+    if checked is None or checked.kspace is None:
+        base = phantom_image(H, W, seed=a.seed).to(device)
+        beat = torch.cos(torch.arange(a.T, device=device) * (2 * torch.pi / a.T)).view(a.T, 1, 1, 1)
+        frames = base * (1.0 + 0.1 * beat)                                 # (T, 1, H, W): a slowly pulsating phantom
+    if checked is None:
+        meas = op(frames).reshape(a.num_sens, 1, a.T, 1, H, W).repeat(1, n_local, 1, 1, 1, 1)
+    else:                                     # simulated with the true maps (or measured), reconstructed with the estimated ones
+        cal, op = load_data.driver_cine_measurement(a, checked, op, frames, device)
+        a.num_sens = op.num_sens
+        meas = cal.measurement.reshape(a.num_sens, 1, a.T, 1, H, W).repeat(1, n_local, 1, 1, 1, 1)
     params = dict(n_steps_each=a.num_steps_each, step_lr=a.step_lr, denoise=False, final_only=True)
     prox_kw = dict(max_iter=a.cg_iters, tol=a.cg_tol) if a.proximal_type == "L2PenaltyCG" else {}
     sampler = ALD2DTime(get_proximal(a.proximal_type)(op, **prox_kw), scorenet_T, sigmas_T, (n_local, a.T, 1, H, W), scorenet,
@@ -98,6 +121,8 @@ if __name__ == '__main__':
     torch.cuda.synchronize()
     if rank == 0:
         print(f"reconstruction time: {time.time() - t0}")
+        if cal is not None and cal.kspace_scale is not None:
+            print(f"k-space scale = {cal.kspace_scale!r}")
     B, T = out.shape[:2]
     flat = out.to(device).reshape(out.shape[0], -1, H, W)                  # (n_local, T, H, W): frames as "channels"
     post = sharding.all_reduce_posterior(flat, a.num_samples) if a.num_samples > 1 else None
@@ -105,10 +130,15 @@ if __name__ == '__main__':
     if rank == 0:
         os.makedirs(a.save_dir, exist_ok=True)
         torch.save(out, os.path.join(a.save_dir, "reconstructions.pt"))
-        torch.save(frames.cpu(), os.path.join(a.save_dir, "original.pt"))
+        if frames is not None:                                             # measured data: no ground truth
+            torch.save(frames.cpu(), os.path.join(a.save_dir, "original.pt"))
         torch.save(op.random_under_fourier.mask, os.path.join(a.save_dir, "mask.pt"))
-        if sens_maps is not None:
+        if sens_maps is not None or cal is not None:
             torch.save(op.sens_maps, os.path.join(a.save_dir, "sens_maps.pt"))
+        if cal is not None:
+            torch.save(cal.measurement.cpu(), os.path.join(a.save_dir, "measurement.pt"))
+            if cal.coil_matrix is not None:
+                torch.save(cal.coil_matrix, os.path.join(a.save_dir, "coil_matrix.pt"))
         if post is not None:
             torch.save({k: v.cpu() for k, v in post.items()}, os.path.join(a.save_dir, "posterior.pt"))
         with open(os.path.join(a.save_dir, "args_dict.pkl"), "wb") as wf:
