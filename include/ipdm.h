@@ -252,6 +252,42 @@ int ipdm_ald_sense_cg_step_csm_f32(float* x_re, float* x_im, const float* g_re, 
                                    int mask_t, float coef, float* work, const float* ahy, int max_iter, float tol,
                                    int32_t* iters_out, int B, int n_coils, int H, int W, void* stream);
 
+/* One set of coil maps per slice: a stack of slices reconstructed in one batch.
+ *   sens          [sens_sets][n_coils][H][W], float32 (sens_complex == 0) or interleaved complex64 (sens_complex != 0)
+ *   image b       reads set b % sens_sets -- the rule mask planes follow (b % T).  The two indices are independent:
+ *                 sens_sets = 2 with a 3-plane mask is legal and means (set b % 2, plane b % 3).
+ * A batch that holds n samples of each of S slices is laid out sample-major, b = sample * S + slice; y stays
+ * [n_coils][B][H][W] and the Philox key stays sample_offset + b.  Every other argument, the arithmetic, the return codes
+ * and the workspace sizes (ipdm_sense_workspace_bytes, ipdm_sense_cg_workspace_bytes) are those of the entry points
+ * above, which are the sens_sets == 1 case of the same kernels: one set gives their results bit for bit, and rows
+ * b % S == s of a multi-set call equal the single-set call on those rows with set s.  sens_sets < 1 or sens == NULL:
+ * IPDM_EINVAL (there is no single-coil shortcut here).  B need not be a multiple of sens_sets. */
+int ipdm_sense_forward_sets_c64(const float* x, const float* sens, int sens_complex, int sens_sets, const uint8_t* mask,
+                                int mask_t, float* y, int B, int n_coils, int H, int W, void* stream);
+int ipdm_sense_adjoint_sets_c64(const float* s, const float* sens, int sens_complex, int sens_sets, const uint8_t* mask,
+                                int mask_t, int apply_mask, float* x, float* workspace, int B, int n_coils, int H, int W,
+                                void* stream);
+int ipdm_sense_l2prox_sets_f32(const float* z_re, const float* z_im, const float* y, const float* sens, int sens_complex,
+                               int sens_sets, const uint8_t* mask, int mask_t, float coef, float* out_re, float* out_im,
+                               float* work, int B, int n_coils, int H, int W, void* stream);
+int ipdm_ald_sense_step_sets_f32(float* x_re, float* x_im, const float* g_re, const float* g_im,
+                                 const float* noise_re, const float* noise_im,
+                                 float step, float noise_scale, uint64_t seed, int64_t sample_offset, int64_t step_id,
+                                 const ipdm_sched_t* dev_sched, const float* y, const float* sens, int sens_complex,
+                                 int sens_sets, const uint8_t* mask, int mask_t, float coef, float* work, int B, int n_coils,
+                                 int H, int W, void* stream);
+int ipdm_sense_cgprox_sets_f32(const float* z_re, const float* z_im, const float* y, const float* sens, int sens_complex,
+                               int sens_sets, const uint8_t* mask, int mask_t, float a, const float* ahy, int max_iter,
+                               float tol, float* out_re, float* out_im, float* work, int32_t* iters_out, int B, int n_coils,
+                               int H, int W, void* stream);
+int ipdm_ald_sense_cg_step_sets_f32(float* x_re, float* x_im, const float* g_re, const float* g_im,
+                                    const float* noise_re, const float* noise_im,
+                                    float step, float noise_scale, uint64_t seed, int64_t sample_offset, int64_t step_id,
+                                    const ipdm_sched_t* dev_sched, const float* y, const float* sens, int sens_complex,
+                                    int sens_sets, const uint8_t* mask, int mask_t, float coef, float* work,
+                                    const float* ahy, int max_iter, float tol, int32_t* iters_out, int B, int n_coils,
+                                    int H, int W, void* stream);
+
 /* Coil sensitivity maps estimated from the fully sampled calibration region of the measurement itself (Walsh's adaptive
  * estimator on low-resolution calibration images; the reference only synthesises maps, undersampling_fourier.py:124-138).
  *   y [n_coils][B][H][W] c64, the measurement layout of the SENSE operators (centred, orthonormal scale)

@@ -58,6 +58,17 @@ SIGNATURES = {
                                    P, P, P, c_int, c_float, P, P, c_int, c_float, P, c_int, c_int, c_int, c_int, P],
     "ipdm_ald_sense_cg_step_csm_f32": [P, P, P, P, P, P, c_float, c_float, c_uint64, c_int64, c_int64, P,
                                        P, P, P, c_int, c_float, P, P, c_int, c_float, P, c_int, c_int, c_int, c_int, P],
+    # one map set per slice: (sens_complex, sens_sets) directly after sens
+    "ipdm_sense_forward_sets_c64": [P, P, c_int, c_int, P, c_int, P, c_int, c_int, c_int, c_int, P],
+    "ipdm_sense_adjoint_sets_c64": [P, P, c_int, c_int, P, c_int, c_int, P, P, c_int, c_int, c_int, c_int, P],
+    "ipdm_sense_l2prox_sets_f32": [P, P, P, P, c_int, c_int, P, c_int, c_float, P, P, P, c_int, c_int, c_int, c_int, P],
+    "ipdm_ald_sense_step_sets_f32": [P, P, P, P, P, P, c_float, c_float, c_uint64, c_int64, c_int64, P,
+                                     P, P, c_int, c_int, P, c_int, c_float, P, c_int, c_int, c_int, c_int, P],
+    "ipdm_sense_cgprox_sets_f32": [P, P, P, P, c_int, c_int, P, c_int, c_float, P, c_int, c_float, P, P, P, P,
+                                   c_int, c_int, c_int, c_int, P],
+    "ipdm_ald_sense_cg_step_sets_f32": [P, P, P, P, P, P, c_float, c_float, c_uint64, c_int64, c_int64, P,
+                                        P, P, c_int, c_int, P, c_int, c_float, P, P, c_int, c_float, P,
+                                        c_int, c_int, c_int, c_int, P],
     "ipdm_csm_workspace_bytes": [c_int, c_int, c_int, c_int],
     "ipdm_csm_supported": [c_int, c_int, c_int, c_int],
     "ipdm_csm_calib_images_c64": [P, c_int, c_int, P, c_int, c_int, c_int, c_int, P],

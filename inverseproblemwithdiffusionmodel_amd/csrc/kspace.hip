@@ -79,14 +79,15 @@ __global__ __launch_bounds__(256) void dft_rows_transposed_kernel(const float2* 
 // sens_mul / sens_mul_conj of kspace_fft.h
 template <typename SensT, bool MIXED>
 __global__ __launch_bounds__(FFT_THREADS) void sense_forward_kernel(const float2* __restrict__ x,
-                                                                    const SensT* __restrict__ sens,
+                                                                    const SensT* __restrict__ sens, int sens_sets,
                                                                     const uint8_t* __restrict__ mask, int mask_t,
                                                                     float2* __restrict__ y, int B, int H, int W) {
   FFT_LDS_SETUP(H, W, MIXED)
   const int HW = H * W;
   const int b = blockIdx.x, coil = blockIdx.y;
   const float2* src = x + (size_t)b * HW;
-  const SensT* sm = sens ? sens + (size_t)coil * HW : nullptr;      // NULL: single coil, S = 1
+  const SensT* set = sens_at(sens, sens_sets, b, (size_t)gridDim.y * HW);      // gridDim.y: n_coils
+  const SensT* sm = set ? set + (size_t)coil * HW : nullptr;        // NULL: single coil, S = 1
   for (int e = threadIdx.x; e < HW; e += FFT_THREADS) {
     int r = e / W, c = e - r * W;
     float s = sign_rc(r, c);
@@ -110,7 +111,7 @@ __global__ __launch_bounds__(FFT_THREADS) void sense_forward_kernel(const float2
 // reference's `X_out += ...` loop: no accumulator registers live across the FFT, deterministic.
 template <bool SSOS, typename SensT, bool MIXED>
 __global__ __launch_bounds__(FFT_THREADS) void sense_adjoint_kernel(const float2* __restrict__ s,
-                                                                    const SensT* __restrict__ sens,
+                                                                    const SensT* __restrict__ sens, int sens_sets,
                                                                     const uint8_t* __restrict__ mask, int mask_t,
                                                                     int apply_mask, float* out, int B,
                                                                     int n_coils, int H, int W) {
@@ -118,6 +119,7 @@ __global__ __launch_bounds__(FFT_THREADS) void sense_adjoint_kernel(const float2
   const int HW = H * W;
   const int b = blockIdx.x;
   const float scale = rsqrtf((float)HW);
+  const SensT* set = sens_at(sens, sens_sets, b, (size_t)n_coils * HW);
   for (int coil = 0; coil < n_coils; ++coil) {
     const float2* src = s + ((size_t)coil * B + b) * HW;
     for (int e = threadIdx.x; e < HW; e += FFT_THREADS) {
@@ -139,7 +141,7 @@ __global__ __launch_bounds__(FFT_THREADS) void sense_adjoint_kernel(const float2
         out[gi] = last ? sqrtf(a) : a;
       } else {
         int r = e / W, c = e - r * W;
-        float2 a = sens_mul_conj(v, sign_rc(r, c) * scale, sens[(size_t)coil * HW + e]);
+        float2 a = sens_mul_conj(v, sign_rc(r, c) * scale, set[(size_t)coil * HW + e]);
         float2* o = reinterpret_cast<float2*>(out) + gi;
         if (coil > 0) {
           float2 prev = *o;
@@ -173,12 +175,12 @@ __global__ __launch_bounds__(FFT_THREADS) void ald_sense_step_kernel(float* x_re
                                                                      const SenseProblem<SensT> pb, float coef, float2* work) {
   const int B = pb.B, n_coils = pb.n_coils, H = pb.H, W = pb.W, mask_t = pb.mask_t;
   const float2* __restrict__ y = pb.y;
-  const SensT* __restrict__ sens = pb.sens;
   const uint8_t* __restrict__ mask = pb.mask;
   FFT_LDS_SETUP(H, W, MIXED)
   coef = sched_override(lg, coef);
   const int HW = H * W;
   const int b = blockIdx.x;
+  const SensT* __restrict__ sens = sens_at(pb.sens, pb.sens_sets, b, (size_t)n_coils * HW);
   const float scale = rsqrtf((float)HW);
   float* xr = x_re + (size_t)b * HW;
   float* xi = x_im + (size_t)b * HW;
@@ -241,7 +243,6 @@ __global__ __launch_bounds__(FFT_THREADS) void sense_normal_coil_kernel(const fl
                                                                         const CgState* __restrict__ state,
                                                                         const SenseProblem<SensT> pb, float2* __restrict__ planes) {
   const int B = pb.B, n_coils = pb.n_coils, H = pb.H, W = pb.W, mask_t = pb.mask_t;
-  const SensT* __restrict__ sens = pb.sens;
   const uint8_t* __restrict__ mask = pb.mask;
   const int coil = blockIdx.x, b = blockIdx.y;
   if constexpr (MODE == 0) {
@@ -253,7 +254,7 @@ __global__ __launch_bounds__(FFT_THREADS) void sense_normal_coil_kernel(const fl
   FFT_LDS_SETUP(H, W, MIXED)
   const int HW = H * W;
   const float scale = rsqrtf((float)HW);
-  const SensT* sm = sens + (size_t)coil * HW;
+  const SensT* __restrict__ sm = sens_at(pb.sens, pb.sens_sets, b, (size_t)n_coils * HW) + (size_t)coil * HW;
   for (int e = threadIdx.x; e < HW; e += FFT_THREADS) {
     float2 v;
     if constexpr (MODE == 0) {
@@ -492,8 +493,8 @@ static int sense_forward_impl(const float* x, const SenseProblem<SensT>& pb, flo
     int rc = set_lds_limit(sense_forward_kernel<SensT, MIXED>, lds);
     if (rc) return rc;
     hipLaunchKernelGGL((sense_forward_kernel<SensT, MIXED>), dim3(pb.B, pb.n_coils), dim3(FFT_THREADS), lds, ipdm_stream(stream),
-                       reinterpret_cast<const float2*>(x), pb.sens, pb.mask, pb.mask_t, reinterpret_cast<float2*>(y), pb.B, pb.H,
-                       pb.W);
+                       reinterpret_cast<const float2*>(x), pb.sens, pb.sens_sets, pb.mask, pb.mask_t, reinterpret_cast<float2*>(y),
+                       pb.B, pb.H, pb.W);
     return ipdm_launch_status();
   });
 }
@@ -501,7 +502,7 @@ static int sense_forward_impl(const float* x, const SenseProblem<SensT>& pb, flo
 // pb.y: the coil images s; pb.mask_t is looked at only with apply_mask
 template <typename SensT>
 static int sense_adjoint_impl(SenseProblem<SensT> pb, int apply_mask, float* x, float* workspace, void* stream) {
-  IPDM_REQUIRE(pb.B >= 0 && pb.n_coils > 0 && pb.H > 0 && pb.W > 0);
+  IPDM_REQUIRE(pb.B >= 0 && pb.n_coils > 0 && pb.H > 0 && pb.W > 0 && pb.sens_sets >= 1);
   if (pb.B == 0) return IPDM_OK;
   IPDM_REQUIRE(pb.y && pb.sens && x);
   if (apply_mask) IPDM_REQUIRE(pb.mask && mask_t_ok(pb.mask_t));
@@ -518,7 +519,7 @@ static int sense_adjoint_impl(SenseProblem<SensT> pb, int apply_mask, float* x, 
     int rc = set_lds_limit(sense_adjoint_kernel<false, SensT, MIXED>, lds);
     if (rc) return rc;
     hipLaunchKernelGGL((sense_adjoint_kernel<false, SensT, MIXED>), dim3(pb.B), dim3(FFT_THREADS), lds, ipdm_stream(stream), pb.y,
-                       pb.sens, pb.mask, pb.mask_t, apply_mask, x, pb.B, pb.n_coils, pb.H, pb.W);
+                       pb.sens, pb.sens_sets, pb.mask, pb.mask_t, apply_mask, x, pb.B, pb.n_coils, pb.H, pb.W);
     return ipdm_launch_status();
   });
 }
@@ -563,8 +564,8 @@ extern "C" int ipdm_sense_ssos_c64(const float* s, float* out, float* workspace,
     int rc = set_lds_limit(sense_adjoint_kernel<true, float, MIXED>, lds);
     if (rc) return rc;
     hipLaunchKernelGGL((sense_adjoint_kernel<true, float, MIXED>), dim3(B), dim3(FFT_THREADS), lds, ipdm_stream(stream),
-                       reinterpret_cast<const float2*>(s), static_cast<const float*>(nullptr), nullptr, 1, 0, out, B, n_coils, H,
-                       W);
+                       reinterpret_cast<const float2*>(s), static_cast<const float*>(nullptr), 1, nullptr, 1, 0, out, B, n_coils,
+                       H, W);
     return ipdm_launch_status();
   });
 }
@@ -647,6 +648,46 @@ extern "C" int ipdm_ald_sense_step_csm_f32(float* x_re, float* x_im, const float
                                            int W, void* stream) {
   return ald_sense_step_impl(x_re, x_im, {g_re, g_im, noise_re, noise_im, step, noise_scale, seed, sample_offset, step_id, dev_sched},
                              sense_problem<float2>(y, sens, mask, mask_t, B, n_coils, H, W), coef, work, stream);
+}
+
+// ---- one map set per slice: sens [sens_sets][n_coils][H][W], image b reads set b % sens_sets (sens_at, kspace_fft.h) --------
+// The entry points above are the sens_sets = 1 case of the same implementations.
+extern "C" int ipdm_sense_forward_sets_c64(const float* x, const float* sens, int sens_complex, int sens_sets,
+                                           const uint8_t* mask, int mask_t, float* y, int B, int n_coils, int H, int W,
+                                           void* stream) {
+  IPDM_REQUIRE(sens && sens_sets >= 1);
+  return sens_dispatch(sens_complex, nullptr, sens, mask, mask_t, B, n_coils, H, W, sens_sets,
+                       [&](const auto& pb) { return sense_forward_impl(x, pb, y, stream); });
+}
+
+extern "C" int ipdm_sense_adjoint_sets_c64(const float* s, const float* sens, int sens_complex, int sens_sets,
+                                           const uint8_t* mask, int mask_t, int apply_mask, float* x, float* workspace, int B,
+                                           int n_coils, int H, int W, void* stream) {
+  IPDM_REQUIRE(sens && sens_sets >= 1);
+  return sens_dispatch(sens_complex, s, sens, mask, mask_t, B, n_coils, H, W, sens_sets,
+                       [&](const auto& pb) { return sense_adjoint_impl(pb, apply_mask, x, workspace, stream); });
+}
+
+extern "C" int ipdm_sense_l2prox_sets_f32(const float* z_re, const float* z_im, const float* y, const float* sens,
+                                          int sens_complex, int sens_sets, const uint8_t* mask, int mask_t, float coef,
+                                          float* out_re, float* out_im, float* work, int B, int n_coils, int H, int W,
+                                          void* stream) {
+  IPDM_REQUIRE(sens && sens_sets >= 1);
+  return sens_dispatch(sens_complex, y, sens, mask, mask_t, B, n_coils, H, W, sens_sets, [&](const auto& pb) {
+    return sense_l2prox_impl(z_re, z_im, pb, coef, out_re, out_im, work, stream);
+  });
+}
+
+extern "C" int ipdm_ald_sense_step_sets_f32(float* x_re, float* x_im, const float* g_re, const float* g_im,
+                                            const float* noise_re, const float* noise_im, float step, float noise_scale,
+                                            uint64_t seed, int64_t sample_offset, int64_t step_id,
+                                            const ipdm_sched_t* dev_sched, const float* y, const float* sens, int sens_complex,
+                                            int sens_sets, const uint8_t* mask, int mask_t, float coef, float* work, int B,
+                                            int n_coils, int H, int W, void* stream) {
+  IPDM_REQUIRE(sens && sens_sets >= 1);
+  const LangevinArgs lg{g_re, g_im, noise_re, noise_im, step, noise_scale, seed, sample_offset, step_id, dev_sched};
+  return sens_dispatch(sens_complex, y, sens, mask, mask_t, B, n_coils, H, W, sens_sets,
+                       [&](const auto& pb) { return ald_sense_step_impl(x_re, x_im, lg, pb, coef, work, stream); });
 }
 
 // x_re / x_im hold z (Langevin pending when lg.g_re) and receive the single-coil operator's result

@@ -199,9 +199,10 @@ static int cg_solve(float* x_re, float* x_im, const LangevinArgs& lg, const Sens
   const bool lang = lg.g_re != nullptr;
   int rc;
   if (!ahy) {                                                  // A^H y = SENSE adjoint of the masked measurement
-    rc = (sizeof(SensT) == sizeof(float2) ? ipdm_sense_adjoint_csm_c64 : ipdm_sense_adjoint_c64)(
-        reinterpret_cast<const float*>(pb.y), reinterpret_cast<const float*>(pb.sens), pb.mask, pb.mask_t, 1,
-        reinterpret_cast<float*>(w.ahy), reinterpret_cast<float*>(w.planes), B, pb.n_coils, H, W, st);
+    rc = ipdm_sense_adjoint_sets_c64(reinterpret_cast<const float*>(pb.y), reinterpret_cast<const float*>(pb.sens),
+                                     sizeof(SensT) == sizeof(float2), pb.sens_sets, pb.mask, pb.mask_t, 1,
+                                     reinterpret_cast<float*>(w.ahy), reinterpret_cast<float*>(w.planes), B, pb.n_coils, H, W,
+                                     st);
     if (rc) return rc;
     ahy = w.ahy;
   }
@@ -317,4 +318,29 @@ extern "C" int ipdm_ald_sense_cg_step_csm_f32(float* x_re, float* x_im, const fl
   return cg_step_impl(x_re, x_im, {g_re, g_im, noise_re, noise_im, step, noise_scale, seed, sample_offset, step_id, dev_sched},
                       sense_problem<float2>(y, sens, mask, mask_t, B, n_coils, H, W), coef, work, ahy, max_iter, tol, iters_out,
                       stream);
+}
+
+// one map set per slice (sens_at, kspace_fft.h); the entry points above are the sens_sets = 1 case
+extern "C" int ipdm_sense_cgprox_sets_f32(const float* z_re, const float* z_im, const float* y, const float* sens,
+                                          int sens_complex, int sens_sets, const uint8_t* mask, int mask_t, float a,
+                                          const float* ahy, int max_iter, float tol, float* out_re, float* out_im, float* work,
+                                          int32_t* iters_out, int B, int n_coils, int H, int W, void* stream) {
+  IPDM_REQUIRE(sens && sens_sets >= 1);
+  return sens_dispatch(sens_complex, y, sens, mask, mask_t, B, n_coils, H, W, sens_sets, [&](const auto& pb) {
+    return cgprox_impl(z_re, z_im, pb, a, ahy, max_iter, tol, out_re, out_im, work, iters_out, stream);
+  });
+}
+
+extern "C" int ipdm_ald_sense_cg_step_sets_f32(float* x_re, float* x_im, const float* g_re, const float* g_im,
+                                               const float* noise_re, const float* noise_im, float step, float noise_scale,
+                                               uint64_t seed, int64_t sample_offset, int64_t step_id,
+                                               const ipdm_sched_t* dev_sched, const float* y, const float* sens,
+                                               int sens_complex, int sens_sets, const uint8_t* mask, int mask_t, float coef,
+                                               float* work, const float* ahy, int max_iter, float tol, int32_t* iters_out,
+                                               int B, int n_coils, int H, int W, void* stream) {
+  IPDM_REQUIRE(sens && sens_sets >= 1);
+  const LangevinArgs lg{g_re, g_im, noise_re, noise_im, step, noise_scale, seed, sample_offset, step_id, dev_sched};
+  return sens_dispatch(sens_complex, y, sens, mask, mask_t, B, n_coils, H, W, sens_sets, [&](const auto& pb) {
+    return cg_step_impl(x_re, x_im, lg, pb, coef, work, ahy, max_iter, tol, iters_out, stream);
+  });
 }

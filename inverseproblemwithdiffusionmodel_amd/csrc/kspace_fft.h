@@ -282,14 +282,31 @@ constexpr LangevinArgs NO_LANGEVIN{};
 template <typename SensT>
 struct SenseProblem {
   const float2* y;                 // k-space data [n_coils][B][H][W]
-  const SensT* sens;               // [n_coils][H][W]
+  const SensT* sens;               // [sens_sets][n_coils][H][W], sens_at()
   const uint8_t* mask;             // mask_at()
   int mask_t, B, n_coils, H, W;
+  int sens_sets;                   // S >= 1 map sets; image b reads set b % S (a stack of slices in one batch)
 };
 template <typename SensT>
 static inline SenseProblem<SensT> sense_problem(const float* y, const float* sens, const uint8_t* mask, int mask_t, int B,
-                                                int n_coils, int H, int W) {
-  return {reinterpret_cast<const float2*>(y), reinterpret_cast<const SensT*>(sens), mask, mask_t, B, n_coils, H, W};
+                                                int n_coils, int H, int W, int sens_sets = 1) {
+  return {reinterpret_cast<const float2*>(y), reinterpret_cast<const SensT*>(sens), mask, mask_t, B, n_coils, H, W, sens_sets};
+}
+// The `_sets_` entry points take the maps' element type as a flag: f(SenseProblem<float2>) for complex64 maps, else <float>.
+template <class Fn>
+static inline int sens_dispatch(int sens_complex, const float* y, const float* sens, const uint8_t* mask, int mask_t, int B,
+                                int n_coils, int H, int W, int sens_sets, Fn&& f) {
+  return sens_complex ? f(sense_problem<float2>(y, sens, mask, mask_t, B, n_coils, H, W, sens_sets))
+                      : f(sense_problem<float>(y, sens, mask, mask_t, B, n_coils, H, W, sens_sets));
+}
+
+// Coil maps of image b, the only place a map set is chosen: set b % sens_sets of [sens_sets][n_coils][H][W], the rule
+// mask_at uses for mask planes (the two indices are independent).  One set serves every image with no modulo and the
+// pointer unchanged.  b is a block index in every kernel, so this is uniform over the workgroup: it is taken once at the
+// top of a kernel, never per element.  set_elems = n_coils * H * W.  sens NULL (single coil) stays NULL.
+template <typename SensT>
+__device__ __forceinline__ const SensT* sens_at(const SensT* sens, int sens_sets, int b, size_t set_elems) {
+  return (sens_sets == 1 || !sens) ? sens : sens + (size_t)(b % sens_sets) * set_elems;
 }
 
 // The device schedule, the only place it is read: the coefficient alone, or with the Langevin scalars as well.
@@ -379,7 +396,7 @@ int launch_normal_coils(int mode, const float* x_re, const float* x_im, const La
 // argument checks shared by the entry points: sizes, then (after the B == 0 exit) the fused tails' pointers
 template <typename SensT>
 static inline bool dims_ok(const SenseProblem<SensT>& pb) {
-  return pb.B >= 0 && pb.n_coils > 0 && pb.H > 0 && pb.W > 0 && mask_t_ok(pb.mask_t);
+  return pb.B >= 0 && pb.n_coils > 0 && pb.H > 0 && pb.W > 0 && mask_t_ok(pb.mask_t) && pb.sens_sets >= 1;
 }
 template <typename SensT>
 static inline bool step_ptrs_ok(const float* x_re, const float* x_im, const LangevinArgs& lg, const SenseProblem<SensT>& pb) {

@@ -46,10 +46,11 @@ static inline size_t strip_lds_bytes(int n) { return ((size_t)STRIP_ELEMS + (siz
 // F: load(b, coil, r, c) -> float2 and store(b, coil, r, c, v); rows [r0, r0 + RS) of image (b, coil)
 // MIXED (all three strip kernels): a side with factors 3 or 5, kspace_fft.h; chosen at launch by fft_dispatch
 template <class F, bool MIXED>
-__global__ __launch_bounds__(FFT_THREADS) void rows_kernel(F f, int H, int W, int inverse) {
+__global__ __launch_bounds__(FFT_THREADS) void rows_kernel(F f0, int H, int W, int inverse) {
   STRIP_LDS_SETUP(W)
   const int RS = strip_lines<MIXED>(H, W);
   const int r0 = blockIdx.x * RS, b = blockIdx.y, coil = blockIdx.z;
+  const F f = f0.for_image(b);
   const int n = RS * W;
   for (int e = threadIdx.x; e < n; e += FFT_THREADS) {
     const int lr = e / W, c = e - lr * W;
@@ -116,8 +117,15 @@ struct RowsFwd {
   ImgGeo g;
   const float2* x;                 // complex input, or NULL ->
   const float *xr, *xi;            // planar input
-  const SensT* sens;
+  const SensT* sens;               // [sens_sets][coils][H][W]; after for_image(): image b's set
   float2* dst;                     // [coil][b][H][W]
+  int sens_sets, n_coils;
+  // the functor of image b's workgroup: the map set is chosen here, once, not in load()
+  __device__ __forceinline__ RowsFwd for_image(int b) const {
+    RowsFwd f = *this;
+    f.sens = sens_at(sens, sens_sets, b, (size_t)n_coils * g.H * g.W);
+    return f;
+  }
   __device__ __forceinline__ float2 load(int b, int coil, int r, int c) const {
     float2 v;
     if (x) v = x[g.at(b, r, c)];
@@ -221,8 +229,8 @@ enum { FIN_ADJOINT = 0, FIN_SSOS = 1, FIN_L2 = 2, FIN_REPLACE = 3 };
 //   FIN_L2: x = x - coef*acc (planar, in place)      FIN_REPLACE: x = acc (planar)
 template <int FIN, typename SensT, bool MIXED>
 __global__ __launch_bounds__(FFT_THREADS) void rows_inv_accum_kernel(const float2* __restrict__ tmp,
-                                                                     const SensT* __restrict__ sens, float2* out_c,
-                                                                     float* out_f, float* x_re, float* x_im,
+                                                                     const SensT* __restrict__ sens_all, int sens_sets,
+                                                                     float2* out_c, float* out_f, float* x_re, float* x_im,
                                                                      const ipdm_sched_t* __restrict__ sched, float coef,
                                                                      int B, int n_coils, int H, int W) {
   STRIP_LDS_SETUP(W)
@@ -230,6 +238,7 @@ __global__ __launch_bounds__(FFT_THREADS) void rows_inv_accum_kernel(const float
   const ImgGeo g{B, H, W};
   const int RS = strip_lines<MIXED>(H, W);
   const int r0 = blockIdx.x * RS, b = blockIdx.y;
+  const SensT* __restrict__ sens = sens_at(sens_all, sens_sets, b, (size_t)n_coils * H * W);
   const int n = RS * W;
   const float scale = rsqrtf((float)H * (float)W);
   float2 acc[EPT];
@@ -380,7 +389,7 @@ static int launch_accum(const float2* tmp, const SenseProblem<SensT>& pb, float2
     int rc = set_lds((rows_inv_accum_kernel<FIN, SensT, MIXED>), lds);
     if (rc) return rc;
     hipLaunchKernelGGL((rows_inv_accum_kernel<FIN, SensT, MIXED>), dim3(pb.H / RS, pb.B), dim3(FFT_THREADS), lds, s, tmp, pb.sens,
-                       out_c, out_f, x_re, x_im, sched, coef, pb.B, pb.n_coils, pb.H, pb.W);
+                       pb.sens_sets, out_c, out_f, x_re, x_im, sched, coef, pb.B, pb.n_coils, pb.H, pb.W);
     return ipdm_launch_status();
   });
 }
@@ -392,7 +401,7 @@ int64_t workspace_bytes(int B, int n_coils, int H, int W) {
 // centred orthonormal 2-D (i)FFT, out may alias in: rows into `out`, columns in place on `out`
 int fft2c(const float2* in, float2* out, int batch, int H, int W, int inverse, hipStream_t s) {
   const ImgGeo g{batch, H, W};
-  RowsFwd<float> rf{g, in, nullptr, nullptr, nullptr, out};
+  RowsFwd<float> rf{g, in, nullptr, nullptr, nullptr, out, 1, 1};
   int rc = launch_rows(rf, batch, 1, H, W, inverse, s);
   if (rc) return rc;
   ColsFwdMask cf{g, out, nullptr, 1, 1.f / sqrtf((float)H * (float)W)};
@@ -403,7 +412,7 @@ template <typename SensT>
 int sense_forward(const float2* x, const SenseProblem<SensT>& pb, float2* y, hipStream_t s) {
   const int B = pb.B, n_coils = pb.n_coils, H = pb.H, W = pb.W;
   const ImgGeo g{B, H, W};
-  RowsFwd<SensT> rf{g, x, nullptr, nullptr, pb.sens, y};
+  RowsFwd<SensT> rf{g, x, nullptr, nullptr, pb.sens, y, pb.sens_sets, n_coils};
   int rc = launch_rows(rf, B, n_coils, H, W, 0, s);
   if (rc) return rc;
   ColsFwdMask cf{g, y, pb.mask, pb.mask_t, 1.f / sqrtf((float)H * (float)W)};
@@ -419,7 +428,7 @@ int sense_adjoint(const SenseProblem<SensT>& pb, int apply_mask, float2* x_out, 
   int rc = launch_cols<ColsInvFromS, false>(ci, pb.B, pb.n_coils, pb.H, pb.W, 1, s);
   if (rc) return rc;
   if (ssos_out) {                                              // no maps in a sum of squares: one kernel for both SensT
-    const SenseProblem<float> np{nullptr, nullptr, nullptr, 1, pb.B, pb.n_coils, pb.H, pb.W};
+    const SenseProblem<float> np{nullptr, nullptr, nullptr, 1, pb.B, pb.n_coils, pb.H, pb.W, 1};
     return launch_accum<FIN_SSOS>(ws, np, nullptr, ssos_out, nullptr, nullptr, nullptr, 0.f, s);
   }
   return launch_accum<FIN_ADJOINT>(ws, pb, x_out, nullptr, nullptr, nullptr, nullptr, 0.f, s);
@@ -439,7 +448,7 @@ template <typename SensT>
 static int rows_cols_prox(const float2* xc, const float* x_re, const float* x_im, const SenseProblem<SensT>& pb, int mode,
                           float coef, const ipdm_sched_t* sched, float2* ws, hipStream_t s) {
   const ImgGeo g{pb.B, pb.H, pb.W};
-  RowsFwd<SensT> rf{g, xc, x_re, x_im, pb.sens, ws};
+  RowsFwd<SensT> rf{g, xc, x_re, x_im, pb.sens, ws, pb.sens_sets, pb.n_coils};
   int rc = launch_rows(rf, pb.B, pb.n_coils, pb.H, pb.W, 0, s);
   if (rc) return rc;
   ColsProx cp{g, ws, pb.y, pb.mask, pb.mask_t, mode, 1.f / sqrtf((float)pb.H * (float)pb.W), coef, sched};

@@ -57,7 +57,7 @@ def build_scorenet(cfg, seed=0):
 
 def build_problem(device, n_samples, R=40, H=128, W=128, num_sens=4, seed=0, scorenet=None, cfg=None, lr_scaled=1.0,
                   sens_maps=None, proximal="L2Penalty", proximal_kwargs=None, mask=None, estimate_maps=False, measurement=None,
-                  calib_max=12, kspace_scale=None, coil_compress=None, noise_cov=None):
+                  calib_max=12, kspace_scale=None, coil_compress=None, noise_cov=None, n_slices=None):
     """-> Namespace(sampler, scorenet, sigmas, op, image, measurement, call_kwargs); sens_maps: measured coil maps
     (num_sens, H, W), real or complex, instead of the synthetic "exp" maps (RSS-normalised where non-zero); proximal: a
     get_proximal name ("L2PenaltyCG": the exact proximal, proximal_kwargs = dict(max_iter=, tol=)); mask: the sampling mask
@@ -73,12 +73,29 @@ def build_problem(device, n_samples, R=40, H=128, W=128, num_sens=4, seed=0, sco
     (ops.coil_compress) before anything else sees it: the maps are estimated on the virtual coils (estimate_maps=True) or
     the given / synthetic maps are compressed with the same matrix (ops.coil_apply), the automatic kspace_scale comes from
     the compressed data, and the operator, the measurement and the sampler have coil_compress coils.  The Namespace
-    carries the matrix as coil_matrix ((coil_compress, n) complex64 on the host; None without compression)."""
+    carries the matrix as coil_matrix ((coil_compress, n) complex64 on the host; None without compression).
+    A stack of S slices in one batch: measurement (S, n, H, W), or n_slices=S without a measurement (not both).  Each
+    slice has its own coil maps -- sens_maps (S, n, H, W), or (n, H, W) shared by the slices, or estimated / compressed per
+    slice (coil_matrix (S, coil_compress, n)) -- and the operator holds them as S map sets (op.n_map_sets).  The sampler's
+    batch is n_samples * S rows, row b = sample b // S of slice b % S, the measurement (n, n_samples * S, 1, H, W) in the
+    same order.  The automatic kspace_scale is ONE number, 1 / the largest rss_max over the slices: the slices of a volume
+    share a grey scale.  A simulated stack draws slice s from phantom seed `seed + s` and, with sens_maps=None, from "exp"
+    maps of seed `seed + s * num_sens` (every coil anchor of the stack its own seed); the mask is the one of `seed`.  The
+    Namespace carries n_slices (1 without a stack); image is then (S, 1, H, W)."""
     prox_cls = get_proximal(proximal)                        # an unknown name fails here, before any GPU work
     kspace_scale = None if kspace_scale is None else float(kspace_scale)
     region = None
     if noise_cov is not None and coil_compress is None:
         raise ValueError("build_problem: noise_cov= goes with coil_compress= (whitening is part of the compression)")
+    if n_slices is not None:
+        if measurement is not None:
+            raise ValueError("build_problem: n_slices= simulates a stack; a measured stack is measurement (S, n_coils, H, W)")
+        if isinstance(n_slices, bool) or int(n_slices) != n_slices or n_slices < 1:
+            raise ValueError(f"build_problem: n_slices must be an integer >= 1, got {n_slices!r}")
+    if n_slices is not None or (measurement is not None and torch.as_tensor(measurement).dim() == 4):
+        return _build_stack(device, n_samples, R, H, W, num_sens, seed, scorenet, cfg, lr_scaled, sens_maps, prox_cls,
+                            proximal_kwargs, mask, estimate_maps, measurement, calib_max, kspace_scale, coil_compress, noise_cov,
+                            None if n_slices is None else int(n_slices))
     if measurement is not None:                              # host-side checks: all fail before any GPU work
         if mask is None:
             raise ValueError("build_problem(measurement=...): pass mask=, the sampling mask of the acquisition")
@@ -87,7 +104,7 @@ def build_problem(device, n_samples, R=40, H=128, W=128, num_sens=4, seed=0, sco
         measurement = torch.as_tensor(measurement)
         if measurement.dim() != 3 or not measurement.is_complex() or tuple(measurement.shape[-2:]) != (H, W):
             raise ValueError(f"build_problem: measurement {tuple(measurement.shape)} {measurement.dtype}; complex "
-                             f"(n_coils, {H}, {W}) expected")
+                             f"(n_coils, {H}, {W}) or, a stack of slices, (S, n_coils, {H}, {W}) expected")
         num_sens = measurement.shape[0]
         if estimate_maps or kspace_scale is None or coil_compress is not None:
             region = calibration_region(mask, H, W, calib_max)
@@ -142,16 +159,114 @@ def build_problem(device, n_samples, R=40, H=128, W=128, num_sens=4, seed=0, sco
                            sens_maps=_compress_maps(op.sens_maps, coil_matrix, num_sens, H, W, device))
         if estimate_maps:                                    # simulated with the true maps, reconstructed with the estimated ones
             op = SENSE.from_measurement(meas1, op.random_under_fourier.mask, R=R, seed=seed, calib_max=calib_max)
+    return _assemble(device, n_samples, 1, H, W, scorenet, cfg, sigmas, op, img, meas1, prox_cls, proximal_kwargs, lr_scaled,
+                     estimate_maps, kspace_scale, coil_matrix)
+
+
+def _assemble(device, n_samples, S, H, W, scorenet, cfg, sigmas, op, img, meas1, prox_cls, proximal_kwargs, lr_scaled,
+              estimate_maps, kspace_scale, coil_matrix):
+    """the sampler on n_samples copies of meas1 (n, S, 1, H, W): repeat along the batch axis gives row sample * S + slice"""
     meas = meas1.repeat(1, n_samples, 1, 1, 1).contiguous()
     params = dict(n_steps_each=cfg.sampling.n_steps_each, step_lr=cfg.sampling.step_lr, denoise=True,
                   final_only=True)
-    sampler = ALDInvSegProximalRealImag(prox_cls(op, **(proximal_kwargs or {})), 1.0, "linear", (n_samples, 1, H, W), scorenet,
-                                        sigmas, params, cfg, meas, op, seg=None, device=device)
+    sampler = ALDInvSegProximalRealImag(prox_cls(op, **(proximal_kwargs or {})), 1.0, "linear", (n_samples * S, 1, H, W),
+                                        scorenet, sigmas, params, cfg, meas, op, seg=None, device=device)
     return Namespace(sampler=sampler, scorenet=scorenet, sigmas=sigmas, op=op, image=img, measurement=meas, cfg=cfg,
                      params=params, call_kwargs=dict(label=None, lamda=0.1, save_dir=None, lr_scaled=lr_scaled,
                                                      seg_mode="full"),
                      estimated_maps=bool(estimate_maps), kspace_scale=kspace_scale,
-                     coil_matrix=None if coil_matrix is None else coil_matrix.cpu())
+                     coil_matrix=None if coil_matrix is None else coil_matrix.cpu(), n_slices=S)
+
+
+def _build_stack(device, n_samples, R, H, W, num_sens, seed, scorenet, cfg, lr_scaled, sens_maps, prox_cls, proximal_kwargs,
+                 mask, estimate_maps, measurement, calib_max, kspace_scale, coil_compress, noise_cov, n_slices):
+    """build_problem for a stack of slices (its docstring): measurement (S, n, H, W), or n_slices simulated ones.  Every
+    shape, mask and calibration-region check runs on the host before the score network is built or the GPU is touched."""
+    region = None
+    if measurement is not None:
+        if mask is None:
+            raise ValueError("build_problem(measurement=...): pass mask=, the sampling mask of the acquisition")
+        if (sens_maps is None) != bool(estimate_maps):
+            raise ValueError("build_problem(measurement=...): the coil maps come from sens_maps= or from estimate_maps=True")
+        measurement = torch.as_tensor(measurement)
+        if (measurement.dim() != 4 or not measurement.is_complex() or tuple(measurement.shape[-2:]) != (H, W)
+                or min(measurement.shape) < 1):
+            raise ValueError(f"build_problem: measurement {tuple(measurement.shape)} {measurement.dtype}; complex "
+                             f"(S, n_coils, {H}, {W}) expected")
+        S, num_sens = measurement.shape[0], measurement.shape[1]
+        if estimate_maps or kspace_scale is None or coil_compress is not None:
+            region = calibration_region(mask, H, W, calib_max)
+    else:
+        S = n_slices
+    if sens_maps is not None:
+        sens_maps = torch.as_tensor(sens_maps)
+        if tuple(sens_maps.shape) not in ((num_sens, H, W), (S, num_sens, H, W)):
+            raise ValueError(f"build_problem: sens_maps {tuple(sens_maps.shape)}, expected {(num_sens, H, W)} (shared by the "
+                             f"slices) or {(S, num_sens, H, W)}")
+        if sens_maps.dim() == 3:
+            sens_maps = sens_maps[None].expand(S, num_sens, H, W)
+    if coil_compress is not None:
+        coil_compress = ops_mod._coilcomp_counts(num_sens, coil_compress, "build_problem(coil_compress=...)")
+        if noise_cov is not None:
+            noise_cov = ops_mod.check_noise_cov(noise_cov, num_sens, "build_problem: noise_cov")
+    mk = {} if mask is None else dict(mask_mode="custom", mask=mask)
+    op = None
+    if measurement is None:
+        # the simulating operator, host only so far: its mask is the one a calibration region has to be found in
+        if sens_maps is None:
+            sens_maps = torch.stack([SENSE("exp", num_sens, R, 0.04, (1, H, W), seed=seed + s * num_sens).sens_maps
+                                     for s in range(S)])
+            op = SENSE("custom", num_sens, R, 0.04, (1, H, W), seed=seed, mask_T=1, sens_maps=sens_maps, normalize=False, **mk)
+        else:
+            op = SENSE("custom", num_sens, R, 0.04, (1, H, W), seed=seed, mask_T=1, sens_maps=sens_maps, **mk)
+        if estimate_maps or coil_compress is not None:
+            region = calibration_region(op.random_under_fourier.mask, H, W, calib_max)
+    coil_matrix = None
+    cfg = acdc_config(device, H) if cfg is None else cfg
+    scorenet = build_scorenet(cfg, seed) if scorenet is None else scorenet
+    sigmas = get_sigmas(cfg, "recons")
+    n_out = num_sens if coil_compress is None else coil_compress
+    if measurement is not None:
+        img = None
+        y = measurement.to(torch.complex64).to(device).transpose(0, 1).contiguous()          # (n, S, H, W): one image per slice
+        if coil_compress is not None:
+            y, coil_matrix, _, _ = ops_mod.coil_compress(y, *region, coil_compress, noise_cov, return_matrix=True)
+            if sens_maps is not None:
+                sens_maps = _compress_map_sets(SENSE.rss_normalize(sens_maps), coil_matrix, device)
+        if region is not None:
+            maps, _, rss_max = ops_mod.estimate_sens_maps(y, *region, return_rss=True)
+            if kspace_scale is None:
+                peak = float(rss_max.max())
+                if not peak > 0.0:
+                    raise ValueError("build_problem: the measurement's calibration region holds no signal")
+                kspace_scale = 1.0 / peak
+        if estimate_maps:
+            op = SENSE("custom", n_out, R, 0.04, (1, H, W), seed=seed, mask_T=1, sens_maps=maps.transpose(0, 1).cpu(),
+                       normalize=False, **mk)
+        else:
+            op = SENSE("custom", n_out, R, 0.04, (1, H, W), seed=seed, mask_T=1, sens_maps=sens_maps,
+                       normalize=coil_compress is None, **mk)
+        meas1 = (y * kspace_scale).reshape(n_out, S, 1, H, W)
+    else:
+        img = torch.cat([phantom_image(H, W, seed=seed + s) for s in range(S)], dim=0).to(device)
+        meas1 = op(img)                                                                       # (n, S, 1, H, W)
+        sim_mask = op.random_under_fourier.mask
+        if coil_compress is not None:
+            meas1, coil_matrix, _, _ = ops_mod.coil_compress(meas1, *region, coil_compress, noise_cov, return_matrix=True)
+            if not estimate_maps:
+                op = SENSE("custom", n_out, R, 0.04, (1, H, W), seed=seed, mask_T=1, normalize=False, mask_mode="custom",
+                           mask=sim_mask, sens_maps=_compress_map_sets(op.sens_maps, coil_matrix, device))
+        if estimate_maps:
+            op = SENSE.from_measurement(meas1[:, :, 0].transpose(0, 1), sim_mask, R=R, seed=seed, calib_max=calib_max)
+    return _assemble(device, n_samples, S, H, W, scorenet, cfg, sigmas, op, img, meas1, prox_cls, proximal_kwargs, lr_scaled,
+                     estimate_maps, kspace_scale, coil_matrix)
+
+
+def _compress_map_sets(maps, A, device):
+    """coil maps (S, n, H, W) of the physical coils -> (S, nv, H, W) of the virtual coils, host complex128: slice s by its own
+    matrix A[s] of A (S, nv, n), one call of the streaming kernel with a matrix per image"""
+    m = torch.as_tensor(maps).to(torch.complex64).to(device).transpose(0, 1).contiguous()    # (n, S, H, W)
+    return ops_mod.coil_apply(m, A.contiguous()).transpose(0, 1).cpu().to(torch.complex128).contiguous()
 
 
 def _compress_maps(maps, A, n, H, W, device):
@@ -188,7 +303,7 @@ class IterationRunner:
         self.levels = lv
         self.table_dev = torch.from_numpy(table.view(np.uint8).reshape(L * n_each, -1).copy()).to(dev)
         self.label_table = torch.arange(L, device=dev)[:, None].repeat(1, 2 * B)
-        cg, work = s._cg_state(B, s.linear_tfm.sens_maps.shape[0], H, W, dev, x0)
+        cg, work = s._cg_state(B, s.linear_tfm.sens_maps.shape[-3], H, W, dev, x0)
         self.st = dict(x=self.x, B=B, y=meas, sc_mode=None, sens=s.linear_tfm.sens_dev(dev), mask=s.linear_tfm.mask_u8(dev),
                        work=work, cg=cg,
                        labels=torch.zeros(2 * B, dtype=torch.long, device=dev), noise_re=None, noise_im=None,

@@ -225,11 +225,13 @@ def load_sens_maps(path):
     return maps.to(torch.complex128 if maps.is_complex() else torch.float64)
 
 
-def load_kspace(path, cine=False):
-    """measured multi-coil k-space (n_coils, H, W) -- cine=True: 2D+time k-space (n_coils, T, H, W) -- from a ``.npy`` or
-    ``.pt`` file -> host complex64 tensor, centred with orthonormal scale as ``SENSE.__call__`` produces it
-    (``engine.build_problem(measurement=...)``, ``SENSE.from_cine_measurement``); any other rank or a real dtype is a
-    ValueError"""
+def load_kspace(path, cine=False, slices=False):
+    """measured multi-coil k-space (n_coils, H, W) -- cine=True: 2D+time k-space (n_coils, T, H, W); slices=True: a stack
+    of slices (S, n_coils, H, W) -- from a ``.npy`` or ``.pt`` file -> host complex64 tensor, centred with orthonormal
+    scale as ``SENSE.__call__`` produces it (``engine.build_problem(measurement=...)``, ``SENSE.from_cine_measurement``);
+    any other rank or a real dtype is a ValueError"""
+    if cine and slices:
+        raise ValueError("load_kspace: cine=True or slices=True, not both (a cine volume is not served)")
     import numpy as np
     import torch
     ext = os.path.splitext(str(path))[1].lower()
@@ -241,9 +243,9 @@ def load_kspace(path, cine=False):
             y = torch.from_numpy(y)
     else:
         raise ValueError(f"load_kspace: {path!r}: a .npy or .pt file")
-    if not isinstance(y, torch.Tensor) or y.dim() != (4 if cine else 3):
+    if not isinstance(y, torch.Tensor) or y.dim() != (4 if cine or slices else 3):
         raise ValueError(f"load_kspace: {path!r} must hold one array of shape "
-                         f"{'(n_coils, T, H, W)' if cine else '(n_coils, H, W)'}")
+                         f"{'(n_coils, T, H, W)' if cine else '(S, n_coils, H, W)' if slices else '(n_coils, H, W)'}")
     if not y.is_complex():
         raise ValueError(f"load_kspace: {path!r} holds {y.dtype}; complex k-space expected")
     return y.to(torch.complex64).contiguous()

@@ -222,7 +222,8 @@ class SENSE(LinearTransform):
         self._dev = {}
         if sens_type == "custom":
             if sens_maps is None:
-                raise ValueError("SENSE('custom', ...) needs sens_maps= (num_sens, H, W), real or complex")
+                raise ValueError("SENSE('custom', ...) needs sens_maps= (num_sens, H, W) or, one set per slice, "
+                                 "(S, num_sens, H, W), real or complex")
             maps = self._as_host_maps(sens_maps)
             self.sens_maps = self.rss_normalize(maps) if normalize else maps
             return
@@ -239,9 +240,11 @@ class SENSE(LinearTransform):
 
     @staticmethod
     def rss_normalize(maps):
-        """maps / root-sum-of-squares over the coils where it is non-zero; zero-support pixels stay zero"""
+        """maps / root-sum-of-squares over the coils where it is non-zero; zero-support pixels stay zero.  (S, n, H, W):
+        each set over its own coil axis"""
         maps = SENSE._as_host_maps(maps)
-        rss = torch.sqrt((torch.abs(maps) ** 2).sum(dim=0))
+        rss = torch.sqrt((torch.abs(maps) ** 2).sum(dim=-3, keepdim=True)) if maps.dim() > 3 else \
+            torch.sqrt((torch.abs(maps) ** 2).sum(dim=0))
         return maps / torch.where(rss > 0, rss, torch.ones_like(rss))
 
     @staticmethod
@@ -250,20 +253,32 @@ class SENSE(LinearTransform):
         channel dims as in a saved (n, 1, 1, H, W) measurement are dropped), centred with orthonormal scale as this
         operator produces it, mask its sampling mask.  The calibration box is ``calibration_region(mask, H, W, calib_max)``,
         the estimator ``ops.estimate_sens_maps`` on the current GPU (kw: radius, power_iters, thresh).
-        -> host complex128 (n, H, W), unit RSS inside the support and zero outside: ready for ``sens_maps=``"""
-        if not isinstance(y, (torch.Tensor, np.ndarray)):
-            raise TypeError(f"estimate_sens_maps: y must be a torch tensor or numpy array, got {type(y).__name__}")
-        y = torch.as_tensor(y).detach()
-        if not y.is_complex():
-            raise TypeError(f"estimate_sens_maps: y must be complex k-space, got {y.dtype}")
-        if y.dim() > 3 and all(s == 1 for s in y.shape[1:-2]):
-            y = y.reshape(y.shape[0], y.shape[-2], y.shape[-1])
-        if y.dim() != 3:
-            raise ValueError(f"estimate_sens_maps: y {tuple(y.shape)}; (n_coils, H, W) expected")
+        -> host complex128 (n, H, W), unit RSS inside the support and zero outside: ready for ``sens_maps=``.
+        y (S, n, H, W), a stack of slices: one batched estimator call, each slice from its own calibration data
+        -> (S, n, H, W)."""
+        y, stack = SENSE._measurement_operand(y, "estimate_sens_maps")
         H, W = y.shape[-2:]
         ah, aw = calibration_region(mask, H, W, calib_max)                  # host only: fails before any GPU work
-        yd = y.to(torch.complex64).to(y.device if y.is_cuda else "cuda").contiguous()
-        return ops.estimate_sens_maps(yd, ah, aw, **kw).cpu().to(torch.complex128)
+        yd = y.to(torch.complex64).to(y.device if y.is_cuda else "cuda")
+        if stack:
+            maps = ops.estimate_sens_maps(yd.transpose(0, 1).contiguous(), ah, aw, **kw)        # (n, S, H, W), one per image
+            return maps.transpose(0, 1).cpu().to(torch.complex128).contiguous()
+        return ops.estimate_sens_maps(yd.contiguous(), ah, aw, **kw).cpu().to(torch.complex128)
+
+    @staticmethod
+    def _measurement_operand(y, what):
+        """-> (y, stack): y a complex tensor (n, H, W), stack False (singleton batch / channel dims of a saved
+        (n, 1, 1, H, W) measurement dropped), or (S, n, H, W), stack True.  TypeError / ValueError."""
+        if not isinstance(y, (torch.Tensor, np.ndarray)):
+            raise TypeError(f"{what}: y must be a torch tensor or numpy array, got {type(y).__name__}")
+        y = torch.as_tensor(y).detach()
+        if not y.is_complex():
+            raise TypeError(f"{what}: y must be complex k-space, got {y.dtype}")
+        if y.dim() > 3 and all(s == 1 for s in y.shape[1:-2]):
+            y = y.reshape(y.shape[0], y.shape[-2], y.shape[-1])
+        if y.dim() not in (3, 4) or min(y.shape) < 1:
+            raise ValueError(f"{what}: y {tuple(y.shape)}; (n_coils, H, W) or, a stack of slices, (S, n_coils, H, W) expected")
+        return y, y.dim() == 4
 
     @staticmethod
     def compress_measurement(y, mask, n_virtual, noise_cov=None, calib_max=12):
@@ -271,23 +286,19 @@ class SENSE(LinearTransform):
         64 coils), n_virtual 1..min(n, 32) virtual coils by PCA of the calibration box ``calibration_region(mask, H, W,
         calib_max)``, noise_cov the (n, n) Hermitian positive definite coil noise covariance of the prescan (None: white
         noise assumed).  ``ops.coil_compress`` on the current GPU.  -> (y' (n_virtual, H, W) complex64 on the GPU,
-        A (n_virtual, n) complex64 on the host).  Every argument is checked on the host before any GPU work."""
-        if not isinstance(y, (torch.Tensor, np.ndarray)):
-            raise TypeError(f"compress_measurement: y must be a torch tensor or numpy array, got {type(y).__name__}")
-        y = torch.as_tensor(y).detach()
-        if not y.is_complex():
-            raise TypeError(f"compress_measurement: y must be complex k-space, got {y.dtype}")
-        if y.dim() > 3 and all(s == 1 for s in y.shape[1:-2]):
-            y = y.reshape(y.shape[0], y.shape[-2], y.shape[-1])
-        if y.dim() != 3:
-            raise ValueError(f"compress_measurement: y {tuple(y.shape)}; (n_coils, H, W) expected")
-        n, H, W = y.shape
+        A (n_virtual, n) complex64 on the host).  y (S, n, H, W), a stack of slices: one batched call, one matrix per slice
+        -> (y' (S, n_virtual, H, W), A (S, n_virtual, n)).  Every argument is checked on the host before any GPU work."""
+        y, stack = SENSE._measurement_operand(y, "compress_measurement")
+        n, H, W = y.shape[-3:]
         n_virtual = ops._coilcomp_counts(n, n_virtual, "compress_measurement")
         if noise_cov is not None:
             noise_cov = ops.check_noise_cov(noise_cov, n, "compress_measurement: noise_cov")
         ah, aw = calibration_region(mask, H, W, calib_max)
-        yd = y.to(torch.complex64).to(y.device if y.is_cuda else "cuda").contiguous()
-        out, A, _, _ = ops.coil_compress(yd, ah, aw, n_virtual, noise_cov, return_matrix=True)
+        yd = y.to(torch.complex64).to(y.device if y.is_cuda else "cuda")
+        if stack:
+            out, A, _, _ = ops.coil_compress(yd.transpose(0, 1).contiguous(), ah, aw, n_virtual, noise_cov, return_matrix=True)
+            return out.transpose(0, 1).contiguous(), A.cpu()
+        out, A, _, _ = ops.coil_compress(yd.contiguous(), ah, aw, n_virtual, noise_cov, return_matrix=True)
         return out, A[0].cpu()
 
     @classmethod
@@ -295,13 +306,14 @@ class SENSE(LinearTransform):
         """the ``"custom"`` operator of an acquisition: maps estimated from its own measurement y (n, H, W) and sampling
         mask (estimate_sens_maps; kw goes to the estimator).  R is informational, as for every custom mask.  n_virtual:
         the measurement is whitened (noise_cov) and compressed first (compress_measurement) and the maps are those of the
-        virtual coils -- the operator then has n_virtual coils and serves the compressed measurement."""
+        virtual coils -- the operator then has n_virtual coils and serves the compressed measurement.  y (S, n, H, W), a
+        stack of slices: the multi-set operator, maps (and compression) per slice (n_map_sets == S)."""
         if n_virtual is not None:
             y, _ = cls.compress_measurement(y, mask, n_virtual, noise_cov=noise_cov, calib_max=calib_max)
         elif noise_cov is not None:
             raise ValueError("from_measurement: noise_cov= goes with n_virtual= (whitening is part of the compression)")
         maps = cls.estimate_sens_maps(y, mask, calib_max=calib_max, **kw)
-        n, H, W = maps.shape
+        n, H, W = maps.shape[-3:]
         return cls("custom", n, R, 0.04, (1, H, W), seed, mask_mode="custom", mask=mask, sens_maps=maps, normalize=False)
 
     @staticmethod
@@ -395,10 +407,17 @@ class SENSE(LinearTransform):
     def sens_maps(self, maps):
         t = self._as_host_maps(maps)
         want = (self.num_sens,) + tuple(self.random_under_fourier.in_shape[-2:])
-        if tuple(t.shape) != want:
-            raise ValueError(f"sens_maps: shape {tuple(t.shape)}, expected (num_sens, H, W) = {want}")
+        if tuple(t.shape[-3:]) != want or t.dim() not in (3, 4) or t.shape[0] < 1:
+            raise ValueError(f"sens_maps: shape {tuple(t.shape)}, expected (num_sens, H, W) = {want} or, one set per slice, "
+                             f"(S,) + {want}")
         self._sens_maps = t.contiguous()
         self._dev = {}                                                      # the device copies belong to the old maps
+
+    @property
+    def n_map_sets(self):
+        """S of (S, num_sens, H, W) maps, one set per slice: batch row b is sample b // S of slice b % S; 1 for
+        (num_sens, H, W) maps"""
+        return self._sens_maps.shape[0] if self._sens_maps.dim() == 4 else 1
 
     def _generate_sens_map(self, sens_type, seed=0, **kwargs):
         """exp(-dist / (2 l)) around a random anchor, l = max(dist) / 2.  The reference builds the pixel list
@@ -432,7 +451,8 @@ class SENSE(LinearTransform):
         return self.random_under_fourier.mask_u8(device)
 
     def __call__(self, X: torch.Tensor) -> torch.Tensor:
-        """X (B, C, H, W) complex -> (num_sens, B, C, H, W) complex64"""
+        """X (B, C, H, W) complex -> (num_sens, B, C, H, W) complex64; with S map sets B is a multiple of S and row b is
+        measured through set b % S"""
         _check_gpu(X, "SENSE")
         X = X.to(torch.complex64)
         return ops.sense_forward(X, self.sens_dev(X.device), self.mask_u8(X.device))

@@ -248,7 +248,7 @@ class ALDInvSegProximalRealImag(ALDOptimizer):
         lv0 = kwargs.get("start_level", 0)
         lv1 = L if kwargs.get("n_levels") is None else min(L, lv0 + kwargs["n_levels"])
 
-        cg, work = self._cg_state(B, lin.sens_maps.shape[0] if sc_mode is None else 1, H, W, dev, ahy)
+        cg, work = self._cg_state(B, lin.sens_maps.shape[-3] if sc_mode is None else 1, H, W, dev, ahy)
         st = dict(x=x, B=B, y=meas, sc_mode=sc_mode, sens=lin.sens_dev(dev) if sc_mode is None else None,
                   mask=lin.mask_u8(dev), work=work, cg=cg,
                   labels=torch.zeros(2 * B, dtype=torch.long, device=dev),
@@ -396,6 +396,10 @@ class ALD2DTime(ALDOptimizer):
 
     def __init__(self, proximal: Proximal, scorenet_T, sigmas_T, *args, **kwargs):
         super(ALD2DTime, self).__init__(*args, **kwargs)
+        if getattr(self.linear_tfm, "n_map_sets", 1) > 1:
+            # the batch here is (B, T) flattened: row % S would pick a map set by frame.  Volume cine is not built.
+            raise ValueError(f"ALD2DTime: the operator holds {self.linear_tfm.n_map_sets} coil-map sets (one per slice); the "
+                             "2D+time sampler takes one set")
         self.proximal = proximal
         self.scorenet_T = scorenet_T
         self.sigmas_T_orig = sigmas_T

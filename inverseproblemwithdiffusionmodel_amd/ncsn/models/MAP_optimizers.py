@@ -61,7 +61,7 @@ class MAPModel:
         sens, mask = tfm.sens_dev(dev), tfm.mask_u8(dev)
         m, v = torch.zeros_like(x), torch.zeros_like(x)
         px = torch.empty_like(x)
-        work = ops.sense_workspace(B, sens.shape[0], H, W, dev)
+        work = ops.sense_workspace(B, sens.shape[-3], H, W, dev)
         for it in range(num_epochs):
             # x - A^H(A x - S): the L2 proximal kernel with unit coefficient; minus x = the descent direction of the data term
             ops.sense_l2prox(x[:B], x[B:], self.S, sens, mask, 1.0, out_re=px[:B], out_im=px[B:], work=work)
@@ -112,7 +112,7 @@ class MAPOptimizer(object):
         sens, mask = tfm.sens_dev(dev), tfm.mask_u8(dev)
         m, v = torch.zeros_like(x), torch.zeros_like(x)
         px = torch.empty_like(x)
-        work = ops.sense_workspace(B, sens.shape[0], H, W, dev)
+        work = ops.sense_workspace(B, sens.shape[-3], H, W, dev)
         labels = torch.ones(2 * B, dtype=torch.long, device=dev)
         n_iters = self.config.MAP.n_iters
         for it in range(n_iters):
@@ -166,6 +166,10 @@ class MAPOptimizer2DTime(object):
         self.scorenet_S, self.scorenet_T = scorenet_S, scorenet_T
         self.win_size = int(np.sqrt(self.scorenet_T.config.data.channels))
         self.linear_tfm = linear_tfm
+        if getattr(linear_tfm, "n_map_sets", 1) > 1:
+            # the batch here is (B, T) flattened: row % S would pick a map set by frame.  Volume cine is not built.
+            raise ValueError(f"MAPOptimizer2DTime: the operator holds {linear_tfm.n_map_sets} coil-map sets (one per slice); "
+                             "the 2D+time optimiser takes one set")
         self.device = params.get("device") or torch.device("cuda")
         self.logger = logger
         self.finite_diff = None
@@ -207,7 +211,7 @@ class MAPOptimizer2DTime(object):
         sens, mask = tfm.sens_dev(dev), tfm.mask_u8(dev)
         m, v = torch.zeros_like(xs), torch.zeros_like(xs)
         px = torch.empty_like(xs)
-        work = ops.sense_workspace(N, sens.shape[0], H, W, dev)
+        work = ops.sense_workspace(N, sens.shape[-3], H, W, dev)
         labels = torch.ones(2 * N, dtype=torch.long, device=dev)
         pw, wS, wT = P["prior_weight"], P["spatial_step_weight"], P["temporal_step_weight"]
         for it in range(P["num_iters"]):

@@ -37,7 +37,7 @@ class Proximal(object):
 class L2Penalty(Proximal):
     def coef(self, alpha, lamda, z_shape):
         if isinstance(self.lin_tfm, SENSE):
-            K = self.lin_tfm.sens_maps.shape[0] * z_shape[-1]
+            K = self.lin_tfm.sens_maps.shape[-3] * z_shape[-1]
         else:
             K = z_shape[0]
         return SGD_LR * (alpha / lamda) / K
@@ -79,7 +79,7 @@ class L2Penalty(Proximal):
         mask = lin.mask_u8(z.device)
         if sense:
             sens = lin.sens_dev(z.device)
-            w_prior, w_data = SGD_LR / B, SGD_LR * a / (sens.shape[0] * z.shape[-1])
+            w_prior, w_data = SGD_LR / B, SGD_LR * a / (sens.shape[-3] * z.shape[-1])
         else:
             w_prior, w_data = SGD_LR / B, SGD_LR * a / B
         zf = torch.view_as_real(z)

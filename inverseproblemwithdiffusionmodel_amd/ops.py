@@ -199,33 +199,48 @@ def _mask_t(mask_u8, H, W, what):
     raise ValueError(f"ipdm {what}: mask {shape} is neither a line mask [mask_t, {W}] nor a 2-D mask [T, {H}, {W}]")
 
 
-def _sens_entry(sens, real_name, csm_name, H, W):
+def _sens_entry(sens, real_name, csm_name, H, W, sets_name=None, B=None):
     """entry point for the coil maps' dtype: contiguous GPU [n, H, W], float32 (real maps) or complex64 (measured maps;
     the *_csm_* kernels).  Anything else -- float64, complex128, a strided view, a CPU tensor -- is refused, never
-    converted: a complex tensor read by a real kernel is interleaved garbage."""
+    converted: a complex tensor read by a real kernel is interleaved garbage.
+    With sets_name the maps may also be [S, n, H, W], one set per slice (image b reads set b % S; ipdm.h): that form
+    takes the *_sets_* entry point, whose extra arguments are _sens_tail(sens), and B must be a multiple of S."""
     if not isinstance(sens, torch.Tensor) or not sens.is_cuda:
         raise RuntimeError("ipdm: coil maps must be a GPU tensor (the HIP path has no CPU fallback)")
     if sens.dtype not in (torch.float32, torch.complex64):
         raise TypeError(f"ipdm: coil maps must be float32 or complex64, got {sens.dtype}")
     if not sens.is_contiguous():
         raise TypeError("ipdm: coil maps must be contiguous (call .contiguous() and keep the result)")
+    if sets_name is not None and sens.dim() == 4:
+        if tuple(sens.shape[-2:]) != (H, W) or sens.shape[0] < 1 or sens.shape[1] < 1:
+            raise ValueError(f"ipdm: coil maps {tuple(sens.shape)} do not match [S, n_coils, {H}, {W}]")
+        if B is not None and B % sens.shape[0]:
+            raise ValueError(f"ipdm: a batch of {B} images is not a whole number of samples of {sens.shape[0]} map sets")
+        return sets_name
     if sens.dim() != 3 or tuple(sens.shape[-2:]) != (H, W):
         raise ValueError(f"ipdm: coil maps {tuple(sens.shape)} do not match [n_coils, {H}, {W}]")
     return csm_name if sens.dtype == torch.complex64 else real_name
 
 
+def _sens_tail(sens):
+    """the arguments that follow `sens` in a *_sets_* entry point, (sens_complex, sens_sets); none for [n, H, W] maps"""
+    return (int(sens.dtype == torch.complex64), sens.shape[0]) if sens.dim() == 4 else ()
+
+
 def sense_forward(x, sens_f32, mask_u8):
-    """sens_f32 None: single coil (S = 1), returns y with a leading axis of length 1; otherwise the coil maps [n, H, W],
-    float32 or complex64"""
+    """sens_f32 None: single coil (S = 1), returns y with a leading axis of length 1; otherwise the coil maps [n, H, W]
+    or [S, n, H, W] (image b reads set b % S), float32 or complex64"""
     x = _gpu(x, torch.complex64, "x")
     B = x.numel() // (x.shape[-1] * x.shape[-2])
     H, W = x.shape[-2:]
-    n = 1 if sens_f32 is None else sens_f32.shape[0]
     fn = "ipdm_sense_forward_c64" if sens_f32 is None else _sens_entry(sens_f32, "ipdm_sense_forward_c64",
-                                                                        "ipdm_sense_forward_csm_c64", H, W)
+                                                                        "ipdm_sense_forward_csm_c64", H, W,
+                                                                        "ipdm_sense_forward_sets_c64", B)
+    n = 1 if sens_f32 is None else sens_f32.shape[-3]
+    tail = () if sens_f32 is None else _sens_tail(sens_f32)
     y = torch.empty((n,) + tuple(x.shape), dtype=torch.complex64, device=x.device)
     mask_t = _mask_t(mask_u8, H, W, "sense_forward")
-    call(fn, _ptr(x), _ptr(sens_f32), _ptr(mask_u8), mask_t, _ptr(y), B, n, H, W,
+    call(fn, _ptr(x), _ptr(sens_f32), *tail, _ptr(mask_u8), mask_t, _ptr(y), B, n, H, W,
          _stream())
     return y
 
@@ -256,13 +271,14 @@ def sense_adjoint(s, sens_f32, mask_u8=None, apply_mask=False):
     n = s.shape[0]
     H, W = s.shape[-2:]
     B = s[0].numel() // (H * W)
-    fn = _sens_entry(sens_f32, "ipdm_sense_adjoint_c64", "ipdm_sense_adjoint_csm_c64", H, W)
-    if sens_f32.shape[0] != n:
-        raise ValueError(f"sense_adjoint: {n} coil images, {sens_f32.shape[0]} coil maps")
+    fn = _sens_entry(sens_f32, "ipdm_sense_adjoint_c64", "ipdm_sense_adjoint_csm_c64", H, W,
+                     "ipdm_sense_adjoint_sets_c64", B)
+    if sens_f32.shape[-3] != n:
+        raise ValueError(f"sense_adjoint: {n} coil images, {sens_f32.shape[-3]} coil maps")
     x = torch.empty(tuple(s.shape[1:]), dtype=torch.complex64, device=s.device)
     ws = sense_workspace(B, n, H, W, s.device) if _large_image(H, W) else None
-    call(fn, _ptr(s), _ptr(sens_f32), _ptr(mask_u8), 1 if mask_u8 is None else _mask_t(mask_u8, H, W, "sense_adjoint"),
-         int(bool(apply_mask)), _ptr(x), _ptr(ws), B, n, H, W, _stream())
+    call(fn, _ptr(s), _ptr(sens_f32), *_sens_tail(sens_f32), _ptr(mask_u8),
+         1 if mask_u8 is None else _mask_t(mask_u8, H, W, "sense_adjoint"), int(bool(apply_mask)), _ptr(x), _ptr(ws), B, n, H, W, _stream())
     return x
 
 
@@ -282,16 +298,17 @@ def sense_l2prox(z_re, z_im, y, sens_f32, mask_u8, coef, out_re=None, out_im=Non
     y = _gpu(y, torch.complex64, "y")
     H, W = z_re.shape[-2:]
     B = z_re.numel() // (H * W)
-    fn = _sens_entry(sens_f32, "ipdm_sense_l2prox_f32", "ipdm_sense_l2prox_csm_f32", H, W)
-    if y.numel() != sens_f32.shape[0] * B * H * W:
+    fn = _sens_entry(sens_f32, "ipdm_sense_l2prox_f32", "ipdm_sense_l2prox_csm_f32", H, W, "ipdm_sense_l2prox_sets_f32", B)
+    n = sens_f32.shape[-3]
+    if y.numel() != n * B * H * W:
         raise ValueError("sense_l2prox: measurement does not match [n_coils, B, H, W]")
     out_re = torch.empty_like(z_re) if out_re is None else out_re
     out_im = torch.empty_like(z_im) if out_im is None else out_im
-    work = sense_workspace(B, sens_f32.shape[0], H, W, z_re.device) if work is None else work
-    _check_work(work, B, sens_f32.shape[0], H, W, "sense_l2prox")
+    work = sense_workspace(B, n, H, W, z_re.device) if work is None else work
+    _check_work(work, B, n, H, W, "sense_l2prox")
     mask_t = _mask_t(mask_u8, H, W, "sense_l2prox")
-    call(fn, _ptr(z_re), _ptr(z_im), _ptr(y), _ptr(sens_f32), _ptr(mask_u8), mask_t,
-         float(coef), _ptr(out_re), _ptr(out_im), _ptr(work), B, sens_f32.shape[0], H, W, _stream())
+    call(fn, _ptr(z_re), _ptr(z_im), _ptr(y), _ptr(sens_f32), *_sens_tail(sens_f32), _ptr(mask_u8), mask_t,
+         float(coef), _ptr(out_re), _ptr(out_im), _ptr(work), B, n, H, W, _stream())
     _written(out_re, out_im)
     return out_re, out_im
 
@@ -299,18 +316,19 @@ def sense_l2prox(z_re, z_im, y, sens_f32, mask_u8, coef, out_re=None, out_im=Non
 def _fused_step(what, x_re, x_im, g_re, g_im, y, noise_re, noise_im, step, noise_scale, seed, sample_offset, step_id,
                 dev_sched, sens=None, entries=None):
     """operand checks of a fused iteration tail, in the wrappers' order, and the 12 leading values of its C signature
-    -> (fn, B, H, W, head).  entries: the (real, complex) entry points of a SENSE step; None: single coil (fn None)"""
+    -> (fn, B, H, W, head).  entries: the (real, complex, map-sets) entry points of a SENSE step; None: single coil
+    (fn None)"""
     for t, n in ((x_re, "x_re"), (x_im, "x_im"), (g_re, "g_re"), (g_im, "g_im")):
         _inplace_operand(t, torch.float32, n)
     H, W = x_re.shape[-2:]
-    fn = _sens_entry(sens, *entries, H, W) if entries else None
-    _inplace_operand(y, torch.complex64, "y")
     B = x_re.numel() // (H * W) if H * W else 0
+    fn = _sens_entry(sens, entries[0], entries[1], H, W, entries[2], B) if entries else None
+    _inplace_operand(y, torch.complex64, "y")
     if entries:
         for t, n in ((noise_re, "noise_re"), (noise_im, "noise_im")):
             if t is not None:
                 _inplace_operand(t, torch.float32, n)
-        if g_re.numel() != x_re.numel() or g_im.numel() != x_im.numel() or y.numel() != sens.shape[0] * B * H * W:
+        if g_re.numel() != x_re.numel() or g_im.numel() != x_im.numel() or y.numel() != sens.shape[-3] * B * H * W:
             raise ValueError(f"{what}: operand sizes do not match the state")
     head = (_ptr(x_re), _ptr(x_im), _ptr(g_re), _ptr(g_im), _ptr(noise_re), _ptr(noise_im), float(step), float(noise_scale),
             int(seed), int(sample_offset), int(step_id), _ptr(dev_sched))
@@ -320,14 +338,16 @@ def _fused_step(what, x_re, x_im, g_re, g_im, y, noise_re, noise_im, step, noise
 def ald_sense_step(x_re, x_im, g_re, g_im, y, sens_f32, mask_u8, work, step=0.0, noise_scale=0.0, coef=0.0,
                    noise_re=None, noise_im=None, seed=0, sample_offset=0, step_id=0, dev_sched=None):
     """in place on x_re / x_im.  dev_sched: uint8/any device tensor holding an ipdm_sched_t.  sens_f32: the coil maps,
-    float32 or complex64."""
+    [n, H, W] or [S, n, H, W] (image b reads set b % S), float32 or complex64."""
     fn, B, H, W, head = _fused_step("ald_sense_step", x_re, x_im, g_re, g_im, y, noise_re, noise_im, step, noise_scale, seed,
                                     sample_offset, step_id, dev_sched, sens_f32,
-                                    ("ipdm_ald_sense_step_f32", "ipdm_ald_sense_step_csm_f32"))
-    _check_work(work, B, sens_f32.shape[0], H, W, "ald_sense_step")
+                                    ("ipdm_ald_sense_step_f32", "ipdm_ald_sense_step_csm_f32",
+                                     "ipdm_ald_sense_step_sets_f32"))
+    n = sens_f32.shape[-3]
+    _check_work(work, B, n, H, W, "ald_sense_step")
     mask_t = _mask_t(mask_u8, H, W, "ald_sense_step")
-    call(fn, *head, _ptr(y), _ptr(sens_f32), _ptr(mask_u8), mask_t, float(coef), _ptr(work), B, sens_f32.shape[0], H, W,
-         _stream())
+    call(fn, *head, _ptr(y), _ptr(sens_f32), *_sens_tail(sens_f32), _ptr(mask_u8), mask_t, float(coef), _ptr(work), B, n,
+         H, W, _stream())
     _written(x_re, x_im)
 
 
@@ -378,15 +398,15 @@ def sense_cgprox(z_re, z_im, y, sens_f32, mask_u8, a, max_iter=10, tol=1e-5, ahy
     y = _gpu(y, torch.complex64, "y")
     H, W = z_re.shape[-2:]
     B = z_re.numel() // (H * W) if H * W else 0
-    fn = _sens_entry(sens_f32, "ipdm_sense_cgprox_f32", "ipdm_sense_cgprox_csm_f32", H, W)
-    n = sens_f32.shape[0]
+    fn = _sens_entry(sens_f32, "ipdm_sense_cgprox_f32", "ipdm_sense_cgprox_csm_f32", H, W, "ipdm_sense_cgprox_sets_f32", B)
+    n = sens_f32.shape[-3]
     if y.numel() != n * B * H * W:
         raise ValueError("sense_cgprox: measurement does not match [n_coils, B, H, W]")
     work, iters_out = _check_cg_args(work, ahy, iters_out, B, n, H, W, z_re.device, "sense_cgprox")
     out_re = torch.empty_like(z_re) if out_re is None else out_re
     out_im = torch.empty_like(z_im) if out_im is None else out_im
     mask_t = _mask_t(mask_u8, H, W, "sense_cgprox")
-    call(fn, _ptr(z_re), _ptr(z_im), _ptr(y), _ptr(sens_f32), _ptr(mask_u8), mask_t, float(a), _ptr(ahy),
+    call(fn, _ptr(z_re), _ptr(z_im), _ptr(y), _ptr(sens_f32), *_sens_tail(sens_f32), _ptr(mask_u8), mask_t, float(a), _ptr(ahy),
          max_iter, tol, _ptr(out_re), _ptr(out_im), _ptr(work), _ptr(iters_out), B, n, H, W, _stream())
     _written(out_re, out_im, iters_out)
     return out_re, out_im, iters_out
@@ -400,11 +420,13 @@ def ald_sense_cg_step(x_re, x_im, g_re, g_im, y, sens_f32, mask_u8, work, step=0
     max_iter, tol = _check_cg_scalars(max_iter, tol, "ald_sense_cg_step")
     fn, B, H, W, head = _fused_step("ald_sense_cg_step", x_re, x_im, g_re, g_im, y, noise_re, noise_im, step, noise_scale, seed,
                                     sample_offset, step_id, dev_sched, sens_f32,
-                                    ("ipdm_ald_sense_cg_step_f32", "ipdm_ald_sense_cg_step_csm_f32"))
-    nc = sens_f32.shape[0]
+                                    ("ipdm_ald_sense_cg_step_f32", "ipdm_ald_sense_cg_step_csm_f32",
+                                     "ipdm_ald_sense_cg_step_sets_f32"))
+    nc = sens_f32.shape[-3]
     work, iters_out = _check_cg_args(work, ahy, iters_out, B, nc, H, W, x_re.device, "ald_sense_cg_step")
     mask_t = _mask_t(mask_u8, H, W, "ald_sense_cg_step")
-    call(fn, *head, _ptr(y), _ptr(sens_f32), _ptr(mask_u8), mask_t, float(coef), _ptr(work), _ptr(ahy), max_iter, tol,
+    call(fn, *head, _ptr(y), _ptr(sens_f32), *_sens_tail(sens_f32), _ptr(mask_u8), mask_t, float(coef), _ptr(work), _ptr(ahy),
+         max_iter, tol,
          _ptr(iters_out), B, nc, H, W, _stream())
     _written(x_re, x_im, iters_out)
     return iters_out
