@@ -524,6 +524,9 @@ int ipdm_conv2d_wino_f32(const float* x, const float* U, const float* bias, cons
 /* tuning aid: when set (device buffer of 4*n_blocks uint64), the Winograd kernel's workgroups write s_memtime stamps
  * (start, loop start, loop end, end); NULL (default) disables it */
 int ipdm_debug_set_stamp_buffer(void* buf);
+/* how many times the library has raised a kernel's dynamic-LDS limit (hipFuncSetAttribute) in this process: once per kernel
+ * instantiation, device and size above what was granted before -- steady-state launches add nothing */
+int64_t ipdm_debug_lds_optin_count(void);
 
 /* 3-D variant for the temporal prior (reference: nn.Conv3d(k=3, padding=dilation, dilation) call sites in
  * ncsn/models/layers3d.py and ncsn/models/ncsn3d.py:137,141): x [B][Cin][D][H][W], weights packed by

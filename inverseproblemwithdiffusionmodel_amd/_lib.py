@@ -115,6 +115,7 @@ SIGNATURES = {
     "ipdm_conv2d_wino_supported": [c_int, c_int, c_int, c_int, c_int],
     "ipdm_conv2d_wino_f32": [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P],
     "ipdm_debug_set_stamp_buffer": [P],
+    "ipdm_debug_lds_optin_count": [],
     "ipdm_conv3d_f32": [P, P, P, P, c_int, P, P, P, c_int] + [c_int] * 8 + [P],
     "ipdm_maxpool3d5_f32": [P, P, c_int, c_int, c_int, c_int, P],
     "ipdm_temporal_taps_f32": [P, P, c_int, c_int, c_int, c_int, c_int, P],
@@ -177,7 +178,7 @@ SIGNATURES = {
     "ipdm_nrmse_f32": [P, P, P, c_int, c_int64, c_int, P],
     "ipdm_ssim_f32": [P, P, P, c_int, c_int, c_int, c_int, ctypes.c_double, P],
 }
-_RESTYPES = {"ipdm_build_arch": c_char_p, "ipdm_fft2c_workspace_bytes": c_int64, "ipdm_sense_workspace_bytes": c_int64, "ipdm_sense_cg_workspace_bytes": c_int64,
+_RESTYPES = {"ipdm_build_arch": c_char_p, "ipdm_debug_lds_optin_count": c_int64, "ipdm_fft2c_workspace_bytes": c_int64, "ipdm_sense_workspace_bytes": c_int64, "ipdm_sense_cg_workspace_bytes": c_int64,
              "ipdm_conv_bx3_weight_bytes": c_int64,
              "ipdm_conv_wino_bx3_weight_bytes": c_int64, "ipdm_conv_hx2_weight_bytes": c_int64,
              "ipdm_conv_wino_hx2_weight_bytes": c_int64, "ipdm_conv_wino1d_weight_bytes": c_int64, "ipdm_conv_wino1d_weight_bytes3d": c_int64,

@@ -7,7 +7,7 @@
 // tests/coilcomp_helpers.py restates operation by operation; coil_apply_kernel<NV> keeps NV complex accumulators per pixel
 // in registers and walks the input coils once, the matrix broadcast from LDS.  No atomics anywhere: an image's results do
 // not depend on its batch.
-#include "ipdm_common.h"
+#include "launch.h"
 
 namespace {
 
@@ -412,14 +412,8 @@ static int gram_launch(const float2* y, int ah, int aw, float2* gram, int B, int
 static int matrix_launch(const float2* gram, const float2* psi, int nv, float2* A, float* eig, int32_t* status, int B, int n,
                          hipStream_t s) {
   const int ld = n | 1;
-  const size_t lds = (size_t)(psi ? 4 : 2) * n * ld * sizeof(float2);
-  if (lds > 64 * 1024) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(coil_eig_kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-  }
-  hipLaunchKernelGGL(coil_eig_kernel, dim3(B), dim3(CC_THREADS), lds, s, gram, psi, A, eig, status, n, nv);
-  return ipdm_launch_status();
+  const size_t lds = (size_t)(psi ? 4 : 2) * n * ld * sizeof(float2);         // 64 coils: 65 KiB, whitened 130 KiB
+  return ipdm_launch_lds(coil_eig_kernel, dim3(B), dim3(CC_THREADS), lds, s, gram, psi, A, eig, status, n, nv);
 }
 
 static int apply_launch(const float2* y, const float2* A, int per_image, float2* out, int B, int n, int nv, int64_t P, hipStream_t s) {

@@ -504,17 +504,7 @@ int launch_bx3(ConvArgs a, hipStream_t s) {
   const int64_t nblk = (int64_t)a.B * ((a.D + ZT - 1) / ZT) * a.tiles_x * a.tiles_y * a.co_tiles * a.ksplit;
   if (nblk > 0x7fffffff || (int64_t)a.D * a.H * a.W >= (1 << 26)) return IPDM_EUNSUPPORTED;   // (32-bit plane offsets in the epilogue)
   auto kern = conv_bx3_kernel<HX, NCT, NPT, WCO, WPX, PW, DMAX, KS, FAST, ZT>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (C::LDS_BYTES > 64 * 1024) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)C::LDS_BYTES);
-      if (e != hipSuccess) return (int)e;
-    }
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(256), C::LDS_BYTES, s, a);
-  return ipdm_launch_status();
+  return ipdm_launch_lds(kern, dim3((unsigned)nblk), dim3(256), C::LDS_BYTES, s, a);
 }
 
 template <bool HX, int NCT, int NPT, int WCO, int WPX, int PW, int DMAX>

@@ -1,6 +1,6 @@
 // Templates of the fp32 MFMA implicit-GEMM convolution; design notes in conv.hip.
 #pragma once
-#include "ipdm_common.h"
+#include "launch.h"
 #include <cstdlib>
 #include <type_traits>
 #include <utility>
@@ -496,17 +496,7 @@ int launch_conv(ConvArgs a, hipStream_t s) {
   const int64_t nblk = (int64_t)a.B * a.D * a.tiles_x * a.tiles_y * a.co_tiles;
   if (nblk > 0x7fffffff) return IPDM_EUNSUPPORTED;
   auto kern = conv_mfma_kernel<NCT, NPT, WCO, WPX, PW, DMAX, KC, KS, FAST, ACT, NORM>;
-  static bool attr_set = false;                 // per instantiation; first set by an eager (non-captured) call
-  if (!attr_set) {
-    if (C::LDS_BYTES > 64 * 1024) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)C::LDS_BYTES);
-      if (e != hipSuccess) return (int)e;
-    }
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(256), C::LDS_BYTES, s, a);
-  return ipdm_launch_status();
+  return ipdm_launch_lds(kern, dim3((unsigned)nblk), dim3(256), C::LDS_BYTES, s, a);
 }
 
 // true when the FAST instantiation of this tile configuration may be used

@@ -372,19 +372,7 @@ int conv_wino_launch(ConvArgs a, hipStream_t s) {
   a.co_tiles = a.Cout / W_CO;
   const int64_t nblk = (int64_t)a.B * a.tiles_x * a.tiles_y * a.co_tiles;
   if (nblk > 0x7fffffff) return IPDM_EUNSUPPORTED;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wino_kernel<false>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)W_LDS_BYTES);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wino_kernel<true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)W_LDS_BYTES);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
-  if (small) hipLaunchKernelGGL(conv_wino_kernel<true>, dim3((unsigned)nblk), dim3(512), W_LDS_BYTES, s, a);
-  else hipLaunchKernelGGL(conv_wino_kernel<false>, dim3((unsigned)nblk), dim3(512), W_LDS_BYTES, s, a);
-  return ipdm_launch_status();
+  return ipdm_launch_lds(small ? conv_wino_kernel<true> : conv_wino_kernel<false>, dim3((unsigned)nblk), dim3(512), W_LDS_BYTES, s, a);
 }
 
 int conv_wino_weights(const float* w, float* U, int Cout, int Cin, hipStream_t s) {

@@ -724,29 +724,11 @@ int conv_wino1d_launch(ConvArgs a, hipStream_t s) {
   if (nblk > 0x7fffffff) return IPDM_EUNSUPPORTED;
   a.phase_step = stagger > 0 && nblk >= (int64_t)st_minpass * 256 ? stagger : 0;
   a.phase_mask = st_groups - 1;
-  static bool attr_set = false;
-  if (!attr_set) {
-#define W1D_K(O, S_, P_) reinterpret_cast<const void*>(conv_wino1d_kernel<O, S_, P_, false>), reinterpret_cast<const void*>(conv_wino1d_kernel<O, S_, P_, true>)
-    const void* kernels[] = {W1D_K(1, false, false), W1D_K(2, false, false), W1D_K(3, false, false), W1D_K(1, true, false), W1D_K(3, true, false),
-                             W1D_K(1, false, true),  W1D_K(2, false, true),  W1D_K(3, false, true),  W1D_K(1, true, true),  W1D_K(3, true, true)};
-#undef W1D_K
-    for (const void* k : kernels) {
-      hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Y_LDS_BYTES);
-      if (e != hipSuccess) return (int)e;
-    }
-    attr_set = true;
-  }
-  int cus = 0, dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8)
-    cus = 256;
-  const int per_xcd = (int)((nblk + 7) / 8);
-  const int S = per_xcd < cus / 8 ? per_xcd : cus / 8;
+  const dim3 grid(ipdm_persistent_grid(nblk));
   const int outs = (a.out ? 1 : 0) | (a.out_act ? 2 : 0);
-#define W1D_LAUNCH(O, S_, P_)                                                                                                    \
-  do {                                                                                                                           \
-    if (a.coef) hipLaunchKernelGGL((conv_wino1d_kernel<O, S_, P_, true>), dim3((unsigned)(8 * S)), dim3(512), Y_LDS_BYTES, s, a, (int)nblk); \
-    else hipLaunchKernelGGL((conv_wino1d_kernel<O, S_, P_, false>), dim3((unsigned)(8 * S)), dim3(512), Y_LDS_BYTES, s, a, (int)nblk);      \
-  } while (0)
+#define W1D_LAUNCH(O, S_, P_)                                                                                            \
+  return a.coef ? ipdm_launch_lds(conv_wino1d_kernel<O, S_, P_, true>, grid, dim3(512), Y_LDS_BYTES, s, a, (int)nblk)   \
+                : ipdm_launch_lds(conv_wino1d_kernel<O, S_, P_, false>, grid, dim3(512), Y_LDS_BYTES, s, a, (int)nblk)
   if (a.pool2) {
     if (a.stats) { if (outs == 3) W1D_LAUNCH(3, true, true); else W1D_LAUNCH(1, true, true); }
     else if (outs == 3) W1D_LAUNCH(3, false, true);
@@ -758,7 +740,6 @@ int conv_wino1d_launch(ConvArgs a, hipStream_t s) {
   else if (outs == 1) W1D_LAUNCH(1, false, false);
   else W1D_LAUNCH(2, false, false);
 #undef W1D_LAUNCH
-  return ipdm_launch_status();
 }
 
 int conv_wino1d_weights(const float* w, void* U, int Cout, int Cin, int npos, hipStream_t s) {
@@ -855,42 +836,16 @@ int conv_wino1d_vol_launch(ConvArgs a, hipStream_t s) {
     compact = e ? atoi(e) : 1;
   }
   const bool nbu3 = compact && a.H % Y_ROWS == 0 && (pack ? a.W == 12 : a.W == 24);     // exactly 12 used pairs in each of 8 rows
-  static bool attr_set = false;
-  if (!attr_set) {
-    const void* kernels[] = {reinterpret_cast<const void*>(conv_wino1d_kernel<1, false, false, false, true>),
-                             reinterpret_cast<const void*>(conv_wino1d_kernel<2, false, false, false, true>),
-                             reinterpret_cast<const void*>(conv_wino1d_kernel<3, false, false, false, true>),
-                             reinterpret_cast<const void*>(conv_wino1d_kernel<1, false, false, false, true, 3>),
-                             reinterpret_cast<const void*>(conv_wino1d_kernel<2, false, false, false, true, 3>),
-                             reinterpret_cast<const void*>(conv_wino1d_kernel<3, false, false, false, true, 3>)};
-    for (const void* k : kernels) {
-      hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Y_LDS_BYTES);
-      if (e != hipSuccess) return (int)e;
-    }
-    attr_set = true;
-  }
-  int cus = 0, dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8)
-    cus = 256;
-  const int per_xcd = (int)((nblk + 7) / 8);
-  const int S = per_xcd < cus / 8 ? per_xcd : cus / 8;
+  const dim3 grid(ipdm_persistent_grid(nblk));
   const int outs = (a.out ? 1 : 0) | (a.out_act ? 2 : 0);
   if (nbu3) {
-    if (outs == 3)
-      hipLaunchKernelGGL((conv_wino1d_kernel<3, false, false, false, true, 3>), dim3((unsigned)(8 * S)), dim3(512), Y_LDS_BYTES, s, a, (int)nblk);
-    else if (outs == 1)
-      hipLaunchKernelGGL((conv_wino1d_kernel<1, false, false, false, true, 3>), dim3((unsigned)(8 * S)), dim3(512), Y_LDS_BYTES, s, a, (int)nblk);
-    else
-      hipLaunchKernelGGL((conv_wino1d_kernel<2, false, false, false, true, 3>), dim3((unsigned)(8 * S)), dim3(512), Y_LDS_BYTES, s, a, (int)nblk);
-    return ipdm_launch_status();
+    if (outs == 3) return ipdm_launch_lds(conv_wino1d_kernel<3, false, false, false, true, 3>, grid, dim3(512), Y_LDS_BYTES, s, a, (int)nblk);
+    if (outs == 1) return ipdm_launch_lds(conv_wino1d_kernel<1, false, false, false, true, 3>, grid, dim3(512), Y_LDS_BYTES, s, a, (int)nblk);
+    return ipdm_launch_lds(conv_wino1d_kernel<2, false, false, false, true, 3>, grid, dim3(512), Y_LDS_BYTES, s, a, (int)nblk);
   }
-  if (outs == 3)
-    hipLaunchKernelGGL((conv_wino1d_kernel<3, false, false, false, true>), dim3((unsigned)(8 * S)), dim3(512), Y_LDS_BYTES, s, a, (int)nblk);
-  else if (outs == 1)
-    hipLaunchKernelGGL((conv_wino1d_kernel<1, false, false, false, true>), dim3((unsigned)(8 * S)), dim3(512), Y_LDS_BYTES, s, a, (int)nblk);
-  else
-    hipLaunchKernelGGL((conv_wino1d_kernel<2, false, false, false, true>), dim3((unsigned)(8 * S)), dim3(512), Y_LDS_BYTES, s, a, (int)nblk);
-  return ipdm_launch_status();
+  if (outs == 3) return ipdm_launch_lds(conv_wino1d_kernel<3, false, false, false, true>, grid, dim3(512), Y_LDS_BYTES, s, a, (int)nblk);
+  if (outs == 1) return ipdm_launch_lds(conv_wino1d_kernel<1, false, false, false, true>, grid, dim3(512), Y_LDS_BYTES, s, a, (int)nblk);
+  return ipdm_launch_lds(conv_wino1d_kernel<2, false, false, false, true>, grid, dim3(512), Y_LDS_BYTES, s, a, (int)nblk);
 }
 }  // namespace ipdm_conv
 

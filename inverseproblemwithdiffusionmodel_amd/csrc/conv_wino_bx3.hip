@@ -1614,16 +1614,6 @@ bool x_half(const ConvArgs& a) {
   return enabled && x_co32(a) && a.W == 16 && a.H == 16;
 }
 
-// hipFuncAttributeMaxDynamicSharedMemorySize is a per-device attribute: set once per (kernel, device)
-template <typename K>
-void set_max_lds_once(K kernel, bool (&done)[64]) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  if (done[dev]) return;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, X_LDS_BYTES);
-  done[dev] = true;
-}
-
 int wino_persist() {                             // IPDM_WBX3_PERSIST=0: one workgroup per tile (tuning / fallback)
   static int persist = -1;
   if (persist < 0) {
@@ -1631,19 +1621,6 @@ int wino_persist() {                             // IPDM_WBX3_PERSIST=0: one wor
     persist = e ? atoi(e) : 1;
   }
   return persist;
-}
-
-int cus_per_xcd() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) == hipSuccess &&
-        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v >= 8)
-      n = v / 8;
-    else
-      n = 32;                                    // MI355X: 256 CUs in 8 XCDs
-  }
-  return n;
 }
 
 }  // namespace
@@ -1675,13 +1652,8 @@ static int conv_wino_bx3_launch_t(ConvArgs a, hipStream_t s) {
     a.tiles_x = a.tiles_y = 1;
     a.co_tiles = a.Cout / X_CO;
     const int64_t nblk = (int64_t)a.B * a.co_tiles;
-    static bool poly_attr[64] = {};
-    set_max_lds_once(conv_wino_bx3_wide_kernel<HXV, 8, 8, true, true, false, false, false, true>, poly_attr);
-    const int per_xcd = (int)((nblk + 7) / 8);
-    const int S = per_xcd < cus_per_xcd() ? per_xcd : cus_per_xcd();
-    hipLaunchKernelGGL((conv_wino_bx3_wide_kernel<HXV, 8, 8, true, true, false, false, false, true>), dim3((unsigned)(8 * S)),
-                       dim3(512), X_LDS_BYTES, s, a, (int)nblk);
-    return ipdm_launch_status();
+    return ipdm_launch_lds(conv_wino_bx3_wide_kernel<HXV, 8, 8, true, true, false, false, false, true>, dim3(ipdm_persistent_grid(nblk)),
+                           dim3(512), X_LDS_BYTES, s, a, (int)nblk);
   }
   const bool small = x_small(a);
   if (HXV && small && wino_persist() && x_co32(a) && (reinterpret_cast<uintptr_t>(a.x) & 15) == 0) {
@@ -1691,26 +1663,16 @@ static int conv_wino_bx3_launch_t(ConvArgs a, hipStream_t s) {
       a.co_tiles = a.Cout / X_CO;
       const int64_t nblk = (int64_t)a.B * 2 * a.co_tiles;
       if (nblk > 0x7fffffff) return IPDM_EUNSUPPORTED;
-      static bool half_attr[64] = {};
-      set_max_lds_once(conv_wino_bx3_wide_kernel<true, 8, 4, true, true, false, false, false, false, false, true>, half_attr);
-      const int per_xcd = (int)((nblk + 7) / 8);
-      const int S = per_xcd < cus_per_xcd() ? per_xcd : cus_per_xcd();
-      hipLaunchKernelGGL((conv_wino_bx3_wide_kernel<true, 8, 4, true, true, false, false, false, false, false, true>), dim3((unsigned)(8 * S)),
-                         dim3(512), X_LDS_BYTES, s, a, (int)nblk);
-      return ipdm_launch_status();
+      return ipdm_launch_lds(conv_wino_bx3_wide_kernel<true, 8, 4, true, true, false, false, false, false, false, true>,
+                             dim3(ipdm_persistent_grid(nblk)), dim3(512), X_LDS_BYTES, s, a, (int)nblk);
     }
     a.tiles_x = (a.W + 15) / 16;
     a.tiles_y = (a.H + 15) / 16;
     a.co_tiles = a.Cout / 32;
     const int64_t nblk = (int64_t)a.B * a.tiles_x * a.tiles_y * a.co_tiles;
     if (nblk > 0x7fffffff) return IPDM_EUNSUPPORTED;
-    static bool co32_attr[64] = {};
-    set_max_lds_once(conv_wino_bx3_wide_kernel<true, 8, 8, true, true, false, false, false, false, true>, co32_attr);
-    const int per_xcd = (int)((nblk + 7) / 8);
-    const int S = per_xcd < cus_per_xcd() ? per_xcd : cus_per_xcd();
-    hipLaunchKernelGGL((conv_wino_bx3_wide_kernel<true, 8, 8, true, true, false, false, false, false, true>), dim3((unsigned)(8 * S)),
-                       dim3(512), X_LDS_BYTES, s, a, (int)nblk);
-    return ipdm_launch_status();
+    return ipdm_launch_lds(conv_wino_bx3_wide_kernel<true, 8, 8, true, true, false, false, false, false, true>,
+                           dim3(ipdm_persistent_grid(nblk)), dim3(512), X_LDS_BYTES, s, a, (int)nblk);
   }
   const bool small_dma = small && wino_persist() && x_small_dma(a);
   // the pooled epilogue lives in the persistent wide kernels only (the ConvMeanPool layers of the score nets are 32..128
@@ -1729,26 +1691,7 @@ static int conv_wino_bx3_launch_t(ConvArgs a, hipStream_t s) {
   a.co_tiles = a.Cout / X_CO;
   const int64_t nblk = (int64_t)a.B * a.tiles_x * a.tiles_y * a.co_tiles;
   if (nblk > 0x7fffffff) return IPDM_EUNSUPPORTED;
-  static bool attr_set = false;
-  if (!attr_set) {
-    const void* kernels[] = {reinterpret_cast<const void*>(conv_wino_bx3_kernel<HXV, false>),
-                             reinterpret_cast<const void*>(conv_wino_bx3_kernel<HXV, true>),
-                             reinterpret_cast<const void*>(conv_wino_bx3_wide_kernel<HXV, 16, 4, false, false>),
-                             reinterpret_cast<const void*>(conv_wino_bx3_wide_kernel<HXV, 8, 8, true, false>),
-                             reinterpret_cast<const void*>(conv_wino_bx3_wide_kernel<HXV, 16, 4, false, true>),
-                             reinterpret_cast<const void*>(conv_wino_bx3_wide_kernel<HXV, 8, 8, true, true>),
-                             reinterpret_cast<const void*>(conv_wino_bx3_wide_kernel<HXV, 16, 4, false, false, true>),
-                             reinterpret_cast<const void*>(conv_wino_bx3_wide_kernel<HXV, 16, 4, false, true, true>),
-                             reinterpret_cast<const void*>(conv_wino_bx3_wide_kernel<HXV, 16, 4, false, true, false, true>),
-                             reinterpret_cast<const void*>(conv_wino_bx3_wide_kernel<HXV, 16, 4, false, true, true, true>)};
-    for (const void* k : kernels) {
-      hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)X_LDS_BYTES);
-      if (e != hipSuccess) return (int)e;
-    }
-    attr_set = true;
-  }
-  const int per_xcd = (int)((nblk + 7) / 8);
-  const int S = per_xcd < cus_per_xcd() ? per_xcd : cus_per_xcd();    // one 128+24 KiB workgroup per CU
+  const dim3 grid(ipdm_persistent_grid(nblk));                         // one 128+24 KiB workgroup per CU
   static int dma4_ok = -1;                       // IPDM_WBX3_DMA4=0: dword LDS-DMA everywhere (tuning / fallback)
   if (dma4_ok < 0) {
     const char* e = getenv("IPDM_WBX3_DMA4");
@@ -1757,33 +1700,24 @@ static int conv_wino_bx3_launch_t(ConvArgs a, hipStream_t s) {
   const bool dma4 = dma4_ok && a.W % 4 == 0 && (reinterpret_cast<uintptr_t>(a.x) & 15) == 0;
   if (a.stats && (small || !wino_persist() || a.Cin < 2 * X_KC)) return IPDM_EUNSUPPORTED;
   if (small_dma) {
-    if (dma4)
-      hipLaunchKernelGGL((conv_wino_bx3_wide_kernel<HXV, 8, 8, true, true>), dim3((unsigned)(8 * S)), dim3(512), X_LDS_BYTES, s, a, (int)nblk);
-    else
-      hipLaunchKernelGGL((conv_wino_bx3_wide_kernel<HXV, 8, 8, true, false>), dim3((unsigned)(8 * S)), dim3(512), X_LDS_BYTES, s, a, (int)nblk);
-  } else if (small) {
-    hipLaunchKernelGGL((conv_wino_bx3_kernel<HXV, true>), dim3((unsigned)nblk), dim3(512), X_LDS_BYTES, s, a);
-  } else if (wino_persist() && a.Cin >= 2 * X_KC) {
-    if (a.stats) {
-      if (!dma4) return IPDM_EUNSUPPORTED;
-      if (a.pool2)
-        hipLaunchKernelGGL((conv_wino_bx3_wide_kernel<HXV, 16, 4, false, true, true, true>), dim3((unsigned)(8 * S)), dim3(512), X_LDS_BYTES, s, a, (int)nblk);
-      else
-        hipLaunchKernelGGL((conv_wino_bx3_wide_kernel<HXV, 16, 4, false, true, false, true>), dim3((unsigned)(8 * S)), dim3(512), X_LDS_BYTES, s, a, (int)nblk);
-      return ipdm_launch_status();
-    }
-    if (a.pool2 && dma4)
-      hipLaunchKernelGGL((conv_wino_bx3_wide_kernel<HXV, 16, 4, false, true, true>), dim3((unsigned)(8 * S)), dim3(512), X_LDS_BYTES, s, a, (int)nblk);
-    else if (a.pool2)
-      hipLaunchKernelGGL((conv_wino_bx3_wide_kernel<HXV, 16, 4, false, false, true>), dim3((unsigned)(8 * S)), dim3(512), X_LDS_BYTES, s, a, (int)nblk);
-    else if (dma4)
-      hipLaunchKernelGGL((conv_wino_bx3_wide_kernel<HXV, 16, 4, false, true>), dim3((unsigned)(8 * S)), dim3(512), X_LDS_BYTES, s, a, (int)nblk);
-    else
-      hipLaunchKernelGGL((conv_wino_bx3_wide_kernel<HXV, 16, 4, false, false>), dim3((unsigned)(8 * S)), dim3(512), X_LDS_BYTES, s, a, (int)nblk);
-  } else {
-    hipLaunchKernelGGL((conv_wino_bx3_kernel<HXV, false>), dim3((unsigned)nblk), dim3(512), X_LDS_BYTES, s, a);
+    if (dma4) return ipdm_launch_lds(conv_wino_bx3_wide_kernel<HXV, 8, 8, true, true>, grid, dim3(512), X_LDS_BYTES, s, a, (int)nblk);
+    return ipdm_launch_lds(conv_wino_bx3_wide_kernel<HXV, 8, 8, true, false>, grid, dim3(512), X_LDS_BYTES, s, a, (int)nblk);
   }
-  return ipdm_launch_status();
+  if (small) return ipdm_launch_lds(conv_wino_bx3_kernel<HXV, true>, dim3((unsigned)nblk), dim3(512), X_LDS_BYTES, s, a);
+  if (!(wino_persist() && a.Cin >= 2 * X_KC))
+    return ipdm_launch_lds(conv_wino_bx3_kernel<HXV, false>, dim3((unsigned)nblk), dim3(512), X_LDS_BYTES, s, a);
+  if (a.stats) {
+    if (!dma4) return IPDM_EUNSUPPORTED;
+    if (a.pool2)
+      return ipdm_launch_lds(conv_wino_bx3_wide_kernel<HXV, 16, 4, false, true, true, true>, grid, dim3(512), X_LDS_BYTES, s, a, (int)nblk);
+    return ipdm_launch_lds(conv_wino_bx3_wide_kernel<HXV, 16, 4, false, true, false, true>, grid, dim3(512), X_LDS_BYTES, s, a, (int)nblk);
+  }
+  if (a.pool2 && dma4)
+    return ipdm_launch_lds(conv_wino_bx3_wide_kernel<HXV, 16, 4, false, true, true>, grid, dim3(512), X_LDS_BYTES, s, a, (int)nblk);
+  if (a.pool2)
+    return ipdm_launch_lds(conv_wino_bx3_wide_kernel<HXV, 16, 4, false, false, true>, grid, dim3(512), X_LDS_BYTES, s, a, (int)nblk);
+  if (dma4) return ipdm_launch_lds(conv_wino_bx3_wide_kernel<HXV, 16, 4, false, true>, grid, dim3(512), X_LDS_BYTES, s, a, (int)nblk);
+  return ipdm_launch_lds(conv_wino_bx3_wide_kernel<HXV, 16, 4, false, false>, grid, dim3(512), X_LDS_BYTES, s, a, (int)nblk);
 }
 
 int conv_wino_bx3_launch(ConvArgs a, hipStream_t s) {
@@ -1827,16 +1761,9 @@ static int conv_wino_bx3_launch_ksplit_t(ConvArgs a, int ksplit, float* work, hi
   a.out_scale = 1.f;                              // the parts are raw sums: bias / residual / scale belong to the reduce pass
   const int64_t nblk = (int64_t)a.B * a.tiles_x * a.tiles_y * a.co_tiles * ksplit;
   if (nblk > 0x7fffffff) return IPDM_EUNSUPPORTED;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wino_bx3_wide_kernel<HXV, 8, 8, true, true, false, false, true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, X_LDS_BYTES);
-    attr_set = true;
-  }
-  const int per_xcd = (int)((nblk + 7) / 8);
-  const int S = per_xcd < cus_per_xcd() ? per_xcd : cus_per_xcd();
-  hipLaunchKernelGGL((conv_wino_bx3_wide_kernel<HXV, 8, 8, true, true, false, false, true>), dim3((unsigned)(8 * S)), dim3(512),
-                     X_LDS_BYTES, s, a, (int)nblk);
+  const int rc = ipdm_launch_lds(conv_wino_bx3_wide_kernel<HXV, 8, 8, true, true, false, false, true>, dim3(ipdm_persistent_grid(nblk)),
+                                 dim3(512), X_LDS_BYTES, s, a, (int)nblk);
+  if (rc != IPDM_OK) return rc;
   const int64_t plane = (int64_t)a.H * a.W, total = (int64_t)a.B * a.Cout * plane;
   hipLaunchKernelGGL(bx3_splitk_reduce_kernel, splitk_reduce_grid(a.B, (int64_t)a.Cout * plane, amax_out || amax_act), dim3(256), 0, s, work, ksplit, bias, residual,
                      out, out_act, a.act_out, a.Cout, plane, total, a.bias_bstride, out_scale, amax_out, amax_act, res_second);

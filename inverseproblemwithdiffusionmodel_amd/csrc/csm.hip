@@ -164,7 +164,7 @@ static int launch_walsh(const float2* calib, const float* rss, const float* rss_
   const int TP = CSM_TILE + 2 * radius;
   const size_t lds = (size_t)NC * TP * TP * sizeof(float2);
   if (lds > CSM_LDS_MAX) return IPDM_EUNSUPPORTED;
-  const int rc = set_lds_limit(csm_walsh_kernel<NC>, lds);
+  const int rc = ipdm_lds_optin(csm_walsh_kernel<NC>, lds);
   if (rc) return rc;
   const int tiles_h = (H + CSM_TILE - 1) / CSM_TILE, tiles_w = (W + CSM_TILE - 1) / CSM_TILE;
   hipLaunchKernelGGL(csm_walsh_kernel<NC>, dim3(tiles_h * tiles_w, B), dim3(CSM_TILE * CSM_TILE), lds, s, calib, rss, rss_max, maps, B,

@@ -382,7 +382,7 @@ static int launch_normal_coils_mode(const float* x_re, const float* x_im, const 
   const size_t lds = lds_bytes(pb.H, pb.W);
   return fft_dispatch(fft_mixed(pb.H, pb.W), [&](auto mixed) {
     constexpr bool MIXED = decltype(mixed)::value;
-    const int rc = set_lds_limit(sense_normal_coil_kernel<MODE, SensT, MIXED>, lds);
+    const int rc = ipdm_lds_optin(sense_normal_coil_kernel<MODE, SensT, MIXED>, lds);
     if (rc) return rc;
     hipLaunchKernelGGL((sense_normal_coil_kernel<MODE, SensT, MIXED>), dim3(pb.n_coils, pb.B), dim3(FFT_THREADS), lds, st, x_re,
                        x_im, lg, coef, p, state, pb, planes);
@@ -459,7 +459,7 @@ extern "C" int ipdm_fft2c_c64(const float* in, float* out, int batch, int H, int
     size_t lds = lds_bytes(H, W);
     return fft_dispatch(fft_mixed(H, W), [&](auto mixed) {
       constexpr bool MIXED = decltype(mixed)::value;
-      int rc = set_lds_limit(fft2c_lds_kernel<MIXED>, lds);
+      int rc = ipdm_lds_optin(fft2c_lds_kernel<MIXED>, lds);
       if (rc) return rc;
       hipLaunchKernelGGL(fft2c_lds_kernel<MIXED>, dim3(batch), dim3(FFT_THREADS), lds, s, reinterpret_cast<const float2*>(in),
                          reinterpret_cast<float2*>(out), H, W, inverse);
@@ -490,7 +490,7 @@ static int sense_forward_impl(const float* x, const SenseProblem<SensT>& pb, flo
   size_t lds = lds_bytes(pb.H, pb.W);
   return fft_dispatch(fft_mixed(pb.H, pb.W), [&](auto mixed) {
     constexpr bool MIXED = decltype(mixed)::value;
-    int rc = set_lds_limit(sense_forward_kernel<SensT, MIXED>, lds);
+    int rc = ipdm_lds_optin(sense_forward_kernel<SensT, MIXED>, lds);
     if (rc) return rc;
     hipLaunchKernelGGL((sense_forward_kernel<SensT, MIXED>), dim3(pb.B, pb.n_coils), dim3(FFT_THREADS), lds, ipdm_stream(stream),
                        reinterpret_cast<const float2*>(x), pb.sens, pb.sens_sets, pb.mask, pb.mask_t, reinterpret_cast<float2*>(y),
@@ -516,7 +516,7 @@ static int sense_adjoint_impl(SenseProblem<SensT> pb, int apply_mask, float* x, 
   size_t lds = lds_bytes(pb.H, pb.W);
   return fft_dispatch(fft_mixed(pb.H, pb.W), [&](auto mixed) {
     constexpr bool MIXED = decltype(mixed)::value;
-    int rc = set_lds_limit(sense_adjoint_kernel<false, SensT, MIXED>, lds);
+    int rc = ipdm_lds_optin(sense_adjoint_kernel<false, SensT, MIXED>, lds);
     if (rc) return rc;
     hipLaunchKernelGGL((sense_adjoint_kernel<false, SensT, MIXED>), dim3(pb.B), dim3(FFT_THREADS), lds, ipdm_stream(stream), pb.y,
                        pb.sens, pb.sens_sets, pb.mask, pb.mask_t, apply_mask, x, pb.B, pb.n_coils, pb.H, pb.W);
@@ -561,7 +561,7 @@ extern "C" int ipdm_sense_ssos_c64(const float* s, float* out, float* workspace,
   size_t lds = lds_bytes(H, W);
   return fft_dispatch(fft_mixed(H, W), [&](auto mixed) {
     constexpr bool MIXED = decltype(mixed)::value;
-    int rc = set_lds_limit(sense_adjoint_kernel<true, float, MIXED>, lds);
+    int rc = ipdm_lds_optin(sense_adjoint_kernel<true, float, MIXED>, lds);
     if (rc) return rc;
     hipLaunchKernelGGL((sense_adjoint_kernel<true, float, MIXED>), dim3(B), dim3(FFT_THREADS), lds, ipdm_stream(stream),
                        reinterpret_cast<const float2*>(s), static_cast<const float*>(nullptr), 1, nullptr, 1, 0, out, B, n_coils,
@@ -582,12 +582,12 @@ static int sense_step(float* x_re, float* x_im, const LangevinArgs& lg, const Se
   return fft_dispatch(fft_mixed(pb.H, pb.W), [&](auto mixed) {
     constexpr bool MIXED = decltype(mixed)::value;
     if (lg.g_re) {
-      int rc = set_lds_limit(ald_sense_step_kernel<true, SensT, MIXED>, lds);
+      int rc = ipdm_lds_optin(ald_sense_step_kernel<true, SensT, MIXED>, lds);
       if (rc) return rc;
       hipLaunchKernelGGL((ald_sense_step_kernel<true, SensT, MIXED>), dim3(pb.B), dim3(FFT_THREADS), lds, st, x_re, x_im, lg, pb,
                          coef, wk);
     } else {
-      int rc = set_lds_limit(ald_sense_step_kernel<false, SensT, MIXED>, lds);
+      int rc = ipdm_lds_optin(ald_sense_step_kernel<false, SensT, MIXED>, lds);
       if (rc) return rc;
       hipLaunchKernelGGL((ald_sense_step_kernel<false, SensT, MIXED>), dim3(pb.B), dim3(FFT_THREADS), lds, st, x_re, x_im, lg, pb,
                          coef, wk);
@@ -702,12 +702,12 @@ static int singlecoil_step(float* x_re, float* x_im, const LangevinArgs& lg, con
   return fft_dispatch(fft_mixed(pb.H, pb.W), [&](auto mixed) {
     constexpr bool MIXED = decltype(mixed)::value;
     if (lg.g_re) {
-      int rc = set_lds_limit(ald_singlecoil_step_kernel<true, MIXED>, lds);
+      int rc = ipdm_lds_optin(ald_singlecoil_step_kernel<true, MIXED>, lds);
       if (rc) return rc;
       hipLaunchKernelGGL((ald_singlecoil_step_kernel<true, MIXED>), dim3(pb.B), dim3(FFT_THREADS), lds, st, x_re, x_im, lg, pb, coef,
                          mode);
     } else {
-      int rc = set_lds_limit(ald_singlecoil_step_kernel<false, MIXED>, lds);
+      int rc = ipdm_lds_optin(ald_singlecoil_step_kernel<false, MIXED>, lds);
       if (rc) return rc;
       hipLaunchKernelGGL((ald_singlecoil_step_kernel<false, MIXED>), dim3(pb.B), dim3(FFT_THREADS), lds, st, x_re, x_im, lg, pb, coef,
                          mode);

@@ -3,7 +3,7 @@
 // sizes, sign and mask helpers.
 #pragma once
 #include <type_traits>
-#include "ipdm_common.h"
+#include "launch.h"
 
 namespace ipdm_kspace {
 
@@ -410,15 +410,6 @@ static inline int copy_planes(float* out_re, float* out_im, const float* z_re, c
   if (out_im != z_im && hipMemcpyAsync(out_im, z_im, n * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
     return (int)hipGetLastError();
   return IPDM_OK;
-}
-
-// raise a kernel's dynamic-LDS limit above the 64 KiB default
-template <typename K>
-static inline int set_lds_limit(K kernel, size_t bytes) {
-  if (bytes <= 64 * 1024) return IPDM_OK;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)bytes);
-  return e == hipSuccess ? IPDM_OK : (int)e;
 }
 
 }  // namespace ipdm_kspace

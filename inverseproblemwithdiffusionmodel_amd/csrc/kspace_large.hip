@@ -339,26 +339,13 @@ __global__ __launch_bounds__(256) void langevin_planes_kernel(float* x_re, float
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------
-// the dynamic-LDS limit is raised ONCE per kernel instantiation, to the largest strip any call can ask for (a static flag per
-// template instance: no host API call on the per-step launch path, none during hipGraph capture after the first use)
-template <typename K>
-static int set_lds(K kernel, size_t bytes) {
-  static bool done = false;                      // one flag per K (per kernel instantiation)
-  if (done || bytes <= 64 * 1024) return IPDM_OK;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)strip_lds_bytes(2048));        // 2048: the largest side large_ok() admits
-  if (e != hipSuccess) return (int)e;
-  done = true;
-  return IPDM_OK;
-}
-
 template <class F>
 static int launch_rows(const F& f, int B, int coils, int H, int W, int inverse, hipStream_t s) {
   const size_t lds = strip_lds_bytes(W);
   const int RS = strip_lines(H, W);
   return fft_dispatch(fft_mixed(H, W), [&](auto mixed) {
     constexpr bool MIXED = decltype(mixed)::value;
-    int rc = set_lds(rows_kernel<F, MIXED>, lds);
+    int rc = ipdm_lds_optin(rows_kernel<F, MIXED>, lds);
     if (rc) return rc;
     hipLaunchKernelGGL((rows_kernel<F, MIXED>), dim3(H / RS, B, coils), dim3(FFT_THREADS), lds, s, f, H, W, inverse);
     return ipdm_launch_status();
@@ -371,7 +358,7 @@ static int launch_cols(const F& f, int B, int coils, int H, int W, int inverse, 
   const int CS = strip_lines(W, H);
   return fft_dispatch(fft_mixed(H, W), [&](auto mixed) {
     constexpr bool MIXED = decltype(mixed)::value;
-    int rc = set_lds((cols_kernel<F, TWO_WAY, MIXED>), lds);
+    int rc = ipdm_lds_optin((cols_kernel<F, TWO_WAY, MIXED>), lds);
     if (rc) return rc;
     hipLaunchKernelGGL((cols_kernel<F, TWO_WAY, MIXED>), dim3(W / CS, B, coils), dim3(FFT_THREADS), lds, s, f, H, W, inverse);
     return ipdm_launch_status();
@@ -386,7 +373,7 @@ static int launch_accum(const float2* tmp, const SenseProblem<SensT>& pb, float2
   const int RS = strip_lines(pb.H, pb.W);
   return fft_dispatch(fft_mixed(pb.H, pb.W), [&](auto mixed) {
     constexpr bool MIXED = decltype(mixed)::value;
-    int rc = set_lds((rows_inv_accum_kernel<FIN, SensT, MIXED>), lds);
+    int rc = ipdm_lds_optin((rows_inv_accum_kernel<FIN, SensT, MIXED>), lds);
     if (rc) return rc;
     hipLaunchKernelGGL((rows_inv_accum_kernel<FIN, SensT, MIXED>), dim3(pb.H / RS, pb.B), dim3(FFT_THREADS), lds, s, tmp, pb.sens,
                        pb.sens_sets, out_c, out_f, x_re, x_im, sched, coef, pb.B, pb.n_coils, pb.H, pb.W);
