@@ -30,11 +30,7 @@ using namespace ipdm_conv;
 namespace {
 
 int forced_cfg() {
-  static int v = -2;
-  if (v == -2) {
-    const char* e = getenv("IPDM_CONV_CFG");
-    v = e ? atoi(e) : -1;
-  }
+  static const int v = ipdm_env_int("IPDM_CONV_CFG", -1);
   return v;
 }
 
@@ -90,11 +86,8 @@ extern "C" int ipdm_conv2d_f32(const float* x, const float* wt, const float* bia
   IPDM_REQUIRE(x && wt && (out || out_act) && x != out && x != out_act);
   if (pool2) return IPDM_EUNSUPPORTED;           // ConvMeanPool epilogue: not fused yet (ipdm_meanpool2_f32)
   if (k == 3 && dilation > 4) return IPDM_EUNSUPPORTED;
-  ConvArgs a;
-  a.x = x; a.wt = wt; a.bias = bias; a.coef = coef; a.residual = residual; a.out = out; a.out_act = out_act; a.act_out = act_out;
-  a.B = B; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W; a.dil = k == 3 ? dilation : 1; a.act = act;
-  a.D = 1; a.kd = 1;
-  a.tiles_x = a.tiles_y = a.co_tiles = 0; a.dbg = nullptr;
+  ConvArgs a = conv_launch_args(x, wt, bias, residual, out, out_act, act_out, B, Cin, Cout, 1, H, W, k, dilation, 0, nullptr, nullptr);
+  a.coef = coef; a.act = act;
   return dispatch_conv(a, k, ipdm_stream(stream));
 }
 
@@ -105,11 +98,9 @@ extern "C" int ipdm_conv3d_f32(const float* x, const float* wt, const float* bia
   if (B == 0) return IPDM_OK;
   IPDM_REQUIRE(x && wt && (out || out_act) && x != out && x != out_act);
   if (k == 3 && dilation > 4) return IPDM_EUNSUPPORTED;
-  ConvArgs a;
-  a.x = x; a.wt = wt; a.bias = bias; a.coef = coef; a.residual = residual; a.out = out; a.out_act = out_act; a.act_out = act_out;
-  a.B = B; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W; a.dil = k == 3 ? dilation : 1; a.act = act;
-  a.D = D; a.kd = k;
-  a.tiles_x = a.tiles_y = a.co_tiles = 0; a.dbg = nullptr;
+  ConvArgs a = conv_launch_args(x, wt, bias, residual, out, out_act, act_out, B, Cin, Cout, D, H, W, k, dilation, 0, nullptr, nullptr);
+  a.coef = coef; a.act = act;
+  a.kd = k;
   return dispatch_conv(a, k, ipdm_stream(stream));
 }
 
@@ -127,10 +118,8 @@ extern "C" int ipdm_conv_wino_weight_f32(const float* w, float* U, int Cout, int
 }
 
 extern "C" int ipdm_conv2d_wino_supported(int Cin, int Cout, int H, int W, int dilation) {
-  ConvArgs a;
-  a.coef = nullptr; a.act = IPDM_ACT_NONE; a.dil = dilation; a.D = 1; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W;
-  a.B = 1;                       // the per-launch size limit (buffer descriptors) is checked again with the real batch
-  return wino_ok(a, 3) ? 1 : 0;
+  // (one image: the per-launch size limit of the buffer descriptors is checked again with the real batch)
+  return wino_ok(conv_query_args(Cin, Cout, 1, H, W, dilation), 3) ? 1 : 0;
 }
 
 extern "C" int ipdm_conv2d_wino_f32(const float* x, const float* U, const float* bias, const float* residual, float* out,
@@ -139,10 +128,7 @@ extern "C" int ipdm_conv2d_wino_f32(const float* x, const float* U, const float*
   IPDM_REQUIRE(B >= 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0 && dilation >= 1);
   if (B == 0) return IPDM_OK;
   IPDM_REQUIRE(x && U && (out || out_act) && x != out && x != out_act);
-  ConvArgs a;
-  a.x = x; a.wt = U; a.bias = bias; a.coef = nullptr; a.residual = residual; a.out = out; a.out_act = out_act;
-  a.act_out = act_out; a.B = B; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W; a.dil = dilation; a.act = IPDM_ACT_NONE;
-  a.D = 1; a.kd = 1; a.tiles_x = a.tiles_y = a.co_tiles = 0; a.dbg = g_wino_dbg; a.dbg = g_wino_dbg;
+  const ConvArgs a = conv_launch_args(x, U, bias, residual, out, out_act, act_out, B, Cin, Cout, 1, H, W, 3, dilation, 0, nullptr, g_wino_dbg);
   if (!wino_ok(a, 3) || !wino_pairs_aligned(a)) return IPDM_EUNSUPPORTED;
   return conv_wino_launch(a, ipdm_stream(stream));
 }

@@ -523,22 +523,14 @@ int launch_bx3_cfg(const ConvArgs& a, int ks, hipStream_t s) {
 }
 
 static int bx3_forced_cfg() {
-  static int v = -2;
-  if (v == -2) {
-    const char* e = getenv("IPDM_BX3_CFG");
-    v = e ? atoi(e) : -1;
-  }
+  static const int v = ipdm_env_int("IPDM_BX3_CFG", -1);
   return v;
 }
 
 // two depth slices per workgroup (BxCfg): undilated 3x3x3 layers on slices at most 16 pixels wide with >= 128 output channels --
 // a rule of the LAYER SHAPE only (the form accumulates straight through, so it must never alternate with the grouped one)
 bool bx3_two_slices(int D, int Cin, int Cout, int W, int k, int dil, int kd) {
-  static int on = -1;
-  if (on < 0) {
-    const char* e = getenv("IPDM_BX3_ZT2");
-    on = e ? atoi(e) : 1;
-  }
+  static const int on = ipdm_env_int("IPDM_BX3_ZT2", 1);
   return on && kd == 3 && k == 3 && dil == 1 && D >= 2 && W <= 16 && Cout >= 128 && Cin % 16 == 0;
 }
 
@@ -610,11 +602,7 @@ __global__ __launch_bounds__(256) void bx3_splitk_reduce_kernel(const float* __r
 // for the 16-pixel tile configurations, whose accumulation is grouped (BX3_KG chunks): the answer is either 1 or the
 // number of groups, and both give bit-identical results.
 int bx3_choose_ksplit(int B, int D, int Cin, int Cout, int H, int W, int k, int dil) {
-  static int forced = -2;                        // IPDM_BX3_KSPLIT=0: never split, =1: split whenever allowed
-  if (forced == -2) {
-    const char* e = getenv("IPDM_BX3_KSPLIT");
-    forced = e ? atoi(e) : -1;
-  }
+  static const int forced = ipdm_env_int("IPDM_BX3_KSPLIT", -1);     // =0: never split, =1: split whenever allowed
   if (W > 16 || forced == 0) return 1;
   if (bx3_two_slices(D, Cin, Cout, W, k, dil, D > 1 && k == 3 ? 3 : 1)) return 1;      // (that form is never split)
   const int64_t tiles = (int64_t)B * D * ((H + 7) / 8) * ((Cout + 63) / 64);
@@ -736,13 +724,9 @@ static int conv3d_bx3_entry(const float* x, const void* wq, const float* bias, c
   if (B == 0) return IPDM_OK;
   IPDM_REQUIRE(x && wq && (out || out_act) && x != out && x != out_act);
   if (k == 3 && dilation > 4) return IPDM_EUNSUPPORTED;
-  ConvArgs a;
-  a.x = x; a.wt = (const float*)wq; a.bias = bias; a.coef = coef; a.residual = residual; a.out = out; a.out_act = out_act;
-  a.act_out = act_out; a.B = B; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W; a.dil = k == 3 ? dilation : 1; a.act = act;
-  a.D = D; a.kd = k;
-  a.tiles_x = a.tiles_y = a.co_tiles = 0; a.dbg = conv_debug_stamps();
-  a.hx = hx;
-  conv_apply_ext(a, ext, hx);
+  ConvArgs a = conv_launch_args(x, wq, bias, residual, out, out_act, act_out, B, Cin, Cout, D, H, W, k, dilation, hx, ext, conv_debug_stamps());
+  a.coef = coef; a.act = act;
+  a.kd = k;
   return conv_bx3_dispatch(a, k, ipdm_stream(stream));
 }
 
@@ -775,14 +759,11 @@ static int conv_bx3_splitk_entry(const float* x, const void* wq, const float* bi
   IPDM_REQUIRE(x && wq && work && ksplit > 1 && (out || out_act) && x != out && x != out_act);
   IPDM_REQUIRE(B <= 65535 || !ext || (!ext->out_amax && !ext->act_amax));
   if (k == 3 && dilation > 4) return IPDM_EUNSUPPORTED;
-  ConvArgs a;
-  a.x = x; a.wt = (const float*)wq; a.bias = nullptr; a.coef = coef; a.residual = nullptr; a.out = nullptr; a.out_act = nullptr;
-  a.act_out = IPDM_ACT_NONE; a.B = B; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W; a.dil = k == 3 ? dilation : 1; a.act = act;
-  a.D = D; a.kd = volume ? k : 1;             // volume: the weights carry depth taps (ipdm_conv3d_bx3_f32 semantics)
-  a.tiles_x = a.tiles_y = a.co_tiles = 0; a.dbg = nullptr;
+  // the parts are raw partial sums: bias / residual / both outputs / activation / stamps belong to the reduce pass or to nobody
+  ConvArgs a = conv_launch_args(x, wq, nullptr, nullptr, nullptr, nullptr, IPDM_ACT_NONE, B, Cin, Cout, D, H, W, k, dilation, hx, ext, nullptr);
+  a.coef = coef; a.act = act;
+  a.kd = volume ? k : 1;                        // volume: the weights carry depth taps (ipdm_conv3d_bx3_f32 semantics)
   a.ksplit = ksplit; a.partial = work;
-  a.hx = hx;
-  conv_apply_ext(a, ext, hx);
   const float out_scale = a.out_scale;
   a.out_scale = 1.f;                            // the parts are raw partial sums; the reduce pass applies bias / residual / scale
   float* const amax_out = a.amax_out;
@@ -821,13 +802,8 @@ static int conv2d_bx3_entry(const float* x, const void* wq, const float* bias, c
   if (B == 0) return IPDM_OK;
   IPDM_REQUIRE(x && wq && (out || out_act) && x != out && x != out_act);
   if (k == 3 && dilation > 4) return IPDM_EUNSUPPORTED;
-  ConvArgs a;
-  a.x = x; a.wt = (const float*)wq; a.bias = bias; a.coef = coef; a.residual = residual; a.out = out; a.out_act = out_act;
-  a.act_out = act_out; a.B = B; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W; a.dil = k == 3 ? dilation : 1; a.act = act;
-  a.D = 1; a.kd = 1;
-  a.tiles_x = a.tiles_y = a.co_tiles = 0; a.dbg = conv_debug_stamps();
-  a.hx = hx;
-  conv_apply_ext(a, ext, hx);
+  ConvArgs a = conv_launch_args(x, wq, bias, residual, out, out_act, act_out, B, Cin, Cout, 1, H, W, k, dilation, hx, ext, conv_debug_stamps());
+  a.coef = coef; a.act = act;
   return conv_bx3_dispatch(a, k, ipdm_stream(stream));
 }
 

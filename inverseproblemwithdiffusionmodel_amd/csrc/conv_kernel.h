@@ -1,6 +1,7 @@
 // Templates of the fp32 MFMA implicit-GEMM convolution; design notes in conv.hip.
 #pragma once
 #include "launch.h"
+#include <cstddef>
 #include <cstdlib>
 #include <type_traits>
 #include <utility>
@@ -116,18 +117,18 @@ __device__ __forceinline__ float half_wave_sum(float v) {
 
 
 struct ConvArgs {
-  const float* x;
-  const float* wt;
-  const float* bias;
-  const float* coef;
-  const float* residual;
-  float* out;      // raw result (may be NULL when only out_act is wanted)
-  float* out_act;  // act_out(result) (may be NULL)
-  int act_out;
-  int B, Cin, Cout, H, W, dil, act;
-  int D, kd;       // depth slices per volume (1 = plain 2-D) and depth taps (1 or 3): 3-D convolution as extra K chunks
-  int tiles_x, tiles_y, co_tiles;
-  unsigned long long* dbg;   // optional in-kernel stamps (diagnostic builds / IPDM tuning only; NULL in production)
+  const float* x = nullptr;
+  const float* wt = nullptr;
+  const float* bias = nullptr;
+  const float* coef = nullptr;
+  const float* residual = nullptr;
+  float* out = nullptr;      // raw result (may be NULL when only out_act is wanted)
+  float* out_act = nullptr;  // act_out(result) (may be NULL)
+  int act_out = IPDM_ACT_NONE;
+  int B = 0, Cin = 0, Cout = 0, H = 0, W = 0, dil = 1, act = IPDM_ACT_NONE;
+  int D = 1, kd = 1;         // depth slices per volume (1 = plain 2-D) and depth taps (1 or 3): 3-D convolution as extra K chunks
+  int tiles_x = 0, tiles_y = 0, co_tiles = 0;   // filled by the launcher
+  unsigned long long* dbg = nullptr;   // optional in-kernel stamps (diagnostic builds / IPDM tuning only; NULL in production)
   int pool2 = 0;             // conv_wino_bx3 wide kernels only: write the 2x2 MEAN of every output tile (ConvMeanPool,
                              //   layers.py:291-313) to out / out_act [B][Cout][H/2][W/2]; residual is at that size too
   int ksplit = 1;            // conv_bx3 only: the K (input channel x depth tap) chunks are dealt to ksplit workgroups
@@ -165,6 +166,9 @@ inline dim3 splitk_reduce_grid(int B, int64_t per_image, bool by_image) {
   return dim3((unsigned)bx, (unsigned)B);
 }
 
+static_assert(sizeof(ConvArgs) == 200 && offsetof(ConvArgs, dbg) == 112 && offsetof(ConvArgs, stats) == 192,
+              "ConvArgs is the kernels' argument: its layout is part of the device code");
+
 // optional extras of the split-operand entry points (include/ipdm.h: ipdm_conv_ext_t) -> ConvArgs
 inline void conv_apply_ext(ConvArgs& a, const ipdm_conv_ext_t* ext, int hx) {
   a.in_amax = hx && ext ? ext->in_amax : nullptr;
@@ -173,6 +177,27 @@ inline void conv_apply_ext(ConvArgs& a, const ipdm_conv_ext_t* ext, int hx) {
   a.res_second = ext ? (ext->res_second != 0) : 0;
   a.amax_out = ext ? ext->out_amax : nullptr;
   a.amax_act = ext ? ext->act_amax : nullptr;
+}
+
+// The ConvArgs of a launch, from an entry point's arguments (the fp32 direct entries have no ext: NULL).  A 1 x 1 convolution has
+// no dilation.  What an entry point does differently (fused input normalisation, depth taps, an epilogue, the split-K parts'
+// nulled outputs) is a one-line override after this call.
+inline ConvArgs conv_launch_args(const float* x, const void* wt, const float* bias, const float* residual, float* out, float* out_act,
+                                 int act_out, int B, int Cin, int Cout, int D, int H, int W, int k, int dilation, int hx,
+                                 const ipdm_conv_ext_t* ext, unsigned long long* dbg) {
+  ConvArgs a;
+  a.x = x; a.wt = static_cast<const float*>(wt); a.bias = bias; a.residual = residual; a.out = out; a.out_act = out_act;
+  a.act_out = act_out; a.B = B; a.Cin = Cin; a.Cout = Cout; a.D = D; a.H = H; a.W = W; a.dil = k == 3 ? dilation : 1;
+  a.hx = hx; a.dbg = dbg;
+  conv_apply_ext(a, ext, hx);
+  return a;
+}
+
+// ... and of a shape-only query (the _supported / _splitk / _form / _partials calls): one image, no tensors
+inline ConvArgs conv_query_args(int Cin, int Cout, int D, int H, int W, int dilation) {
+  ConvArgs a;
+  a.B = 1; a.Cin = Cin; a.Cout = Cout; a.D = D; a.H = H; a.W = W; a.dil = dilation;
+  return a;
 }
 
 // NCT x NPT MFMA tiles per wave, WCO x WPX waves (WCO*WPX == 4), PW = pixel-tile width (16 or 32),

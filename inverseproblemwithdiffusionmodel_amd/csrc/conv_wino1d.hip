@@ -703,27 +703,31 @@ bool wino1d_ok(const ConvArgs& a) {
   return a.H % 2 == 0 && a.W % 4 == 0 && a.H >= 8 && a.W >= 32 && (reinterpret_cast<uintptr_t>(a.x) & 15) == 0;
 }
 
-int conv_wino1d_launch(ConvArgs a, hipStream_t s) {
-  // IPDM_W1D_STAGGER=<cycles>[:<groups 2|4|8>[:<min passes per workgroup>]]: start delay per phase group
-  static int stagger = -1, st_groups = 4, st_minpass = 0;
-  if (stagger < 0) {
-    const char* e = getenv("IPDM_W1D_STAGGER");
-    stagger = 0;
-    if (e) {
-      int c = 0, g = 4, m = 0;
-      const int n = sscanf(e, "%d:%d:%d", &c, &g, &m);
-      if (n >= 1) stagger = c / 512;
-      if (n >= 2 && (g == 2 || g == 4 || g == 8)) st_groups = g;
-      if (n >= 3) st_minpass = m;
-    }
+// IPDM_W1D_STAGGER=<cycles>[:<groups 2|4|8>[:<min passes per workgroup>]]: start delay per phase group (tuning)
+struct W1dStagger {
+  int step = 0, groups = 4, minpass = 0;         // step: units of 512 cycles
+};
+static W1dStagger w1d_stagger_parse(const char* e) {
+  W1dStagger st;
+  if (e) {
+    int c = 0, g = 4, m = 0;
+    const int n = sscanf(e, "%d:%d:%d", &c, &g, &m);
+    if (n >= 1) st.step = c / 512;
+    if (n >= 2 && (g == 2 || g == 4 || g == 8)) st.groups = g;
+    if (n >= 3) st.minpass = m;
   }
+  return st;
+}
+
+int conv_wino1d_launch(ConvArgs a, hipStream_t s) {
+  static const W1dStagger st = w1d_stagger_parse(getenv("IPDM_W1D_STAGGER"));
   a.tiles_x = (a.W + 2 * Y_TX - 1) / (2 * Y_TX);
   a.tiles_y = (a.H + Y_ROWS - 1) / Y_ROWS;
   a.co_tiles = a.Cout / Y_CO;
   const int64_t nblk = (int64_t)a.B * a.tiles_x * a.tiles_y * a.co_tiles;
   if (nblk > 0x7fffffff) return IPDM_EUNSUPPORTED;
-  a.phase_step = stagger > 0 && nblk >= (int64_t)st_minpass * 256 ? stagger : 0;
-  a.phase_mask = st_groups - 1;
+  a.phase_step = st.step > 0 && nblk >= (int64_t)st.minpass * 256 ? st.step : 0;
+  a.phase_mask = st.groups - 1;
   const dim3 grid(ipdm_persistent_grid(nblk));
   const int outs = (a.out ? 1 : 0) | (a.out_act ? 2 : 0);
 #define W1D_LAUNCH(O, S_, P_)                                                                                            \
@@ -767,9 +771,7 @@ extern "C" int ipdm_conv_wino1d_pack_weight(const float* w, void* U, int Cout, i
 }
 
 extern "C" int ipdm_conv2d_wino1d_supported(int Cin, int Cout, int H, int W) {
-  ConvArgs a;
-  a.x = nullptr; a.out = a.out_act = nullptr; a.act_out = IPDM_ACT_NONE; a.coef = nullptr; a.act = IPDM_ACT_NONE; a.dil = 1; a.D = 1; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W; a.B = 1;
-  return wino1d_ok(a) ? 1 : 0;
+  return wino1d_ok(conv_query_args(Cin, Cout, 1, H, W, 1)) ? 1 : 0;
 }
 
 static int wino1d_entry(const float* x, const void* U, const float* bias, const float* coef, int act, const float* residual,
@@ -778,14 +780,10 @@ static int wino1d_entry(const float* x, const void* U, const float* bias, const 
   IPDM_REQUIRE(B >= 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0);
   if (B == 0) return IPDM_OK;
   IPDM_REQUIRE(x && U && (out || out_act) && x != out && x != out_act);
-  ConvArgs a;
-  a.x = x; a.wt = (const float*)U; a.bias = bias; a.coef = coef; a.residual = residual; a.out = out; a.out_act = out_act;
-  a.act_out = act_out; a.B = B; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W; a.dil = 1; a.act = coef ? act : IPDM_ACT_NONE;
-  a.D = 1; a.kd = 1; a.tiles_x = a.tiles_y = a.co_tiles = 0; a.dbg = conv_debug_stamps();
-  a.hx = 1;
+  ConvArgs a = conv_launch_args(x, U, bias, residual, out, out_act, act_out, B, Cin, Cout, 1, H, W, 3, 1, 1, ext, conv_debug_stamps());
+  a.coef = coef; a.act = coef ? act : IPDM_ACT_NONE;
   a.stats = stats;
   a.pool2 = pool2 ? 1 : 0;
-  conv_apply_ext(a, ext, 1);
   if (!wino1d_ok(a) || !wino_pairs_aligned(a)) return IPDM_EUNSUPPORTED;
   return conv_wino1d_launch(a, ipdm_stream(stream));
 }
@@ -830,11 +828,7 @@ int conv_wino1d_vol_launch(ConvArgs a, hipStream_t s) {
   a.co_tiles = a.Cout / Y_CO;
   const int64_t nblk = (int64_t)a.B * (pack ? (a.D + 1) / 2 : a.D) * a.tiles_x * a.tiles_y * a.co_tiles;
   if (nblk > 0x7fffffff) return IPDM_EUNSUPPORTED;
-  static int compact = -1;                       // IPDM_W1D_COMPACT=0: four column blocks everywhere (tuning / fallback)
-  if (compact < 0) {
-    const char* e = getenv("IPDM_W1D_COMPACT");
-    compact = e ? atoi(e) : 1;
-  }
+  static const int compact = ipdm_env_int("IPDM_W1D_COMPACT", 1);    // =0: four column blocks everywhere (tuning / fallback)
   const bool nbu3 = compact && a.H % Y_ROWS == 0 && (pack ? a.W == 12 : a.W == 24);     // exactly 12 used pairs in each of 8 rows
   const dim3 grid(ipdm_persistent_grid(nblk));
   const int outs = (a.out ? 1 : 0) | (a.out_act ? 2 : 0);
@@ -860,10 +854,7 @@ extern "C" int ipdm_conv_wino1d_pack_weight3d(const float* w, void* U, int Cout,
 }
 
 extern "C" int ipdm_conv3d_wino1d_supported(int Cin, int Cout, int D, int H, int W) {
-  ConvArgs a;
-  a.x = nullptr; a.out = a.out_act = nullptr; a.act_out = IPDM_ACT_NONE; a.coef = nullptr; a.act = IPDM_ACT_NONE; a.dil = 1;
-  a.D = D; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W; a.B = 1;
-  return wino1d_vol_ok(a) ? 1 : 0;
+  return wino1d_vol_ok(conv_query_args(Cin, Cout, D, H, W, 1)) ? 1 : 0;
 }
 
 extern "C" int ipdm_conv3d_wino1d_f32(const float* x, const void* U, const float* bias, const float* residual, float* out,
@@ -872,12 +863,8 @@ extern "C" int ipdm_conv3d_wino1d_f32(const float* x, const void* U, const float
   IPDM_REQUIRE(B >= 0 && Cin > 0 && Cout > 0 && D > 0 && H > 0 && W > 0);
   if (B == 0) return IPDM_OK;
   IPDM_REQUIRE(x && U && (out || out_act) && x != out && x != out_act);
-  ConvArgs a;
-  a.x = x; a.wt = (const float*)U; a.bias = bias; a.coef = nullptr; a.residual = residual; a.out = out; a.out_act = out_act;
-  a.act_out = act_out; a.B = B; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W; a.dil = 1; a.act = IPDM_ACT_NONE;
-  a.D = D; a.kd = 3; a.tiles_x = a.tiles_y = a.co_tiles = 0; a.dbg = conv_debug_stamps();
-  a.hx = 1;
-  conv_apply_ext(a, ext, 1);
+  ConvArgs a = conv_launch_args(x, U, bias, residual, out, out_act, act_out, B, Cin, Cout, D, H, W, 3, 1, 1, ext, conv_debug_stamps());
+  a.kd = 3;
   if (!wino1d_vol_ok(a) || !wino_pairs_aligned(a)) return IPDM_EUNSUPPORTED;
   return conv_wino1d_vol_launch(a, ipdm_stream(stream));
 }

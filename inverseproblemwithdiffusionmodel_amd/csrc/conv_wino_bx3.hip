@@ -22,15 +22,13 @@
 // Eligible: 3x3, Cin % 16 == 0, Cout % 64 == 0, no fused input normalisation / activation; wide images (W >= 32,
 // dilation 1) or the linear-tile-space variant for small / dilated images (polyphase, as conv_wino.hip).
 #include "conv_kernel.h"
+#include "wino_plan.h"
 
 namespace ipdm_conv {
 
 namespace {
 
-constexpr int X_KC = 16;                 // input channels per chunk (one bf16 MFMA k-step)
-constexpr int X_CO = 64;
-constexpr int X_TX = 16, X_TY = 4;
-constexpr int X_TILES = X_TX * X_TY;     // 64
+// (X_KC = 16 input channels per chunk, X_CO = 64 output channels and X_TX x X_TY = 16 x 4 tiles per workgroup: wino_plan.h)
 constexpr int X_V_ELEMS = 16 * X_KC * X_TILES;                   // 16384 floats per stage
 // wide images: the raw input region of a chunk ((2*TY+2) x (2*TX+2) pixels x 16 channels) is brought into LDS by
 // LDS-DMA (buffer_load ... lds: no VGPRs, hardware zero padding) and the 4x4 patches are read from there
@@ -1577,179 +1575,71 @@ __global__ __launch_bounds__(512) void conv_wino_bx3_wide_kernel(ConvArgs a, int
 #undef IPDM_TR
 
 
-bool x_small(const ConvArgs& a) { return a.W < 32 || a.dil > 1; }
-// undilated images of up to 16 x 16 pixels with enough (image, channel tile) pairs to fill the chip: the persistent
-// LDS-DMA kernel with an 8 x 8 tile block per image
-bool x_small_dma(const ConvArgs& a) {
-  static int min_pairs = -1;                     // IPDM_WBX3_SMALL_MIN: tuning aid
-  if (min_pairs < 0) {
-    const char* e = getenv("IPDM_WBX3_SMALL_MIN");
-    min_pairs = e ? atoi(e) : 160;
-  }
-  return a.dil == 1 && a.W <= 16 && a.H <= 16 && a.W % 2 == 0 && a.H % 2 == 0 && a.Cin >= 2 * X_KC &&
-         (int64_t)a.B * (a.Cout / X_CO) >= min_pairs;
-}
+// the instantiations by name.  wide_kernel<HX, TX, TY, CO_MAJOR, DMA4, POOL, STATS, KSP, POLY, CO32, HALF>
+template <bool HX> constexpr auto k_poly = conv_wino_bx3_wide_kernel<HX, 8, 8, true, true, false, false, false, true>;
+constexpr auto k_half = conv_wino_bx3_wide_kernel<true, 8, 4, true, true, false, false, false, false, false, true>;
+constexpr auto k_co32 = conv_wino_bx3_wide_kernel<true, 8, 8, true, true, false, false, false, false, true>;
+template <bool HX, bool DMA4> constexpr auto k_small_dma = conv_wino_bx3_wide_kernel<HX, 8, 8, true, DMA4>;
+template <bool HX, bool DMA4, bool POOL = false, bool STATS = false>
+constexpr auto k_wide = conv_wino_bx3_wide_kernel<HX, 16, 4, false, DMA4, POOL, STATS>;
+template <bool HX> constexpr auto k_ksplit = conv_wino_bx3_wide_kernel<HX, 8, 8, true, true, false, false, true>;
 
-// 16-pixel layers with fewer than 512 output channels as 32-channel workgroups (CO32): what the f16x2 family's PLAIN call runs for
-// the shapes whose split-K rule says 2 (the host mirror then does not split: one launch instead of two K halves + a reduction;
-// IPDM_WBX3_CO32=0: off; a function of the layer shape only)
-bool x_co32(const ConvArgs& a) {
-  static int enabled = -1;
-  if (enabled < 0) {
-    const char* e = getenv("IPDM_WBX3_CO32");
-    enabled = e ? atoi(e) : 1;
-  }
-  return enabled && a.hx && a.dil == 1 && a.W <= 16 && a.H <= 16 && a.W % 4 == 0 && a.H % 2 == 0 && a.Cin >= 2 * X_KC &&
-         a.Cout < 512 && !a.pool2 && !a.stats;
-}
-
-// ... and of those the 16 x 16 images as (image, upper / lower eight rows, 64 channels) workgroups (HALF): the same count of
-// workgroups, one patch per thread and chunk instead of two (IPDM_WBX3_HALF=0: off, i.e. CO32; a function of the layer shape only)
-bool x_half(const ConvArgs& a) {
-  static int enabled = -1;
-  if (enabled < 0) {
-    const char* e = getenv("IPDM_WBX3_HALF");
-    enabled = e ? atoi(e) : 1;
-  }
-  return enabled && x_co32(a) && a.W == 16 && a.H == 16;
-}
-
-int wino_persist() {                             // IPDM_WBX3_PERSIST=0: one workgroup per tile (tuning / fallback)
-  static int persist = -1;
-  if (persist < 0) {
-    const char* e = getenv("IPDM_WBX3_PERSIST");
-    persist = e ? atoi(e) : 1;
-  }
-  return persist;
+WinoShape wino_shape_of(const ConvArgs& a) {
+  return WinoShape{a.B, a.Cin, a.Cout, a.H, a.W, a.dil, a.hx != 0, a.pool2 != 0, a.stats != nullptr,
+                   (reinterpret_cast<uintptr_t>(a.x) & 15) == 0};
 }
 
 }  // namespace
 
 bool wino_bx3_ok(const ConvArgs& a, int ks) {
-  if (!(ks == 3 && a.D == 1 && a.Cin % X_KC == 0 && a.Cout % X_CO == 0 && !a.coef && a.act == IPDM_ACT_NONE)) return false;
-  if (a.dil < 1 || a.dil > 4) return false;
-  // buffer descriptors: the tensor must end below the padding marker (2^29 + 2^29 register path, 2^30 DMA path)
-  if ((size_t)a.B * a.Cin * a.H * a.W * 4 >= (x_small(a) ? 0x1fffffffull : 0x3fffffffull)) return false;
-  if (x_small(a)) return a.H % (2 * a.dil) == 0 && a.W % (2 * a.dil) == 0 && (a.H * a.W) / 4 >= 32;
-  return a.H % 2 == 0 && a.W % 2 == 0 && a.H >= 8;
+  return ks == 3 && a.D == 1 && !a.coef && a.act == IPDM_ACT_NONE && wino_bx3_shape_ok(wino_shape_of(a));
 }
 
-// dilated 16 x 16 images (the deepest stages of the score networks): the persistent kernel on the polyphase tile space with the
-// whole padded image in the raw stage (a function of the layer shape; IPDM_WBX3_POLY=0: the register-staged kernel)
-bool x_poly(const ConvArgs& a) {
-  static int enabled = -1;
-  if (enabled < 0) {
-    const char* e = getenv("IPDM_WBX3_POLY");
-    enabled = e ? atoi(e) : 1;
-  }
-  return enabled && wino_persist() && a.dil > 1 && a.H == 16 && a.W == 16 && 16 % (2 * a.dil) == 0 && a.Cin >= 2 * X_KC &&
-         !a.pool2 && !a.stats && (reinterpret_cast<uintptr_t>(a.x) & 15) == 0;
-}
-
+// plan (wino_plan.h: the whole choice of the form), the plan's tiles into `a`, the form's instantiation
 template <bool HXV>
 static int conv_wino_bx3_launch_t(ConvArgs a, hipStream_t s) {
-  if (x_poly(a)) {
-    a.tiles_x = a.tiles_y = 1;
-    a.co_tiles = a.Cout / X_CO;
-    const int64_t nblk = (int64_t)a.B * a.co_tiles;
-    return ipdm_launch_lds(conv_wino_bx3_wide_kernel<HXV, 8, 8, true, true, false, false, false, true>, dim3(ipdm_persistent_grid(nblk)),
-                           dim3(512), X_LDS_BYTES, s, a, (int)nblk);
+  const WinoPlan p = wino_bx3_plan(wino_shape_of(a), wino_switches());
+  if (p.rc != IPDM_OK) return p.rc;
+  a.tiles_x = p.tiles_x;
+  a.tiles_y = p.tiles_y;
+  a.co_tiles = p.co_tiles;
+  const auto persistent = [&](void (*kernel)(ConvArgs, int)) {            // one 128+32 KiB workgroup per CU walks the tiles
+    return ipdm_launch_lds(kernel, dim3(ipdm_persistent_grid(p.nblk)), dim3(512), X_LDS_BYTES, s, a, (int)p.nblk);
+  };
+  const auto per_tile = [&](void (*kernel)(ConvArgs)) {
+    return ipdm_launch_lds(kernel, dim3((unsigned)p.nblk), dim3(512), X_LDS_BYTES, s, a);
+  };
+  switch (p.form) {
+    case WINO_POLY: return persistent(k_poly<HXV>);
+    case WINO_HALF: return persistent(k_half);                            // (the plan gives these two to f16x2 only)
+    case WINO_CO32: return persistent(k_co32);
+    case WINO_SMALL_DMA: return persistent(p.dma4 ? k_small_dma<HXV, true> : k_small_dma<HXV, false>);
+    case WINO_SMALL_REG: return per_tile(conv_wino_bx3_kernel<HXV, true>);
+    case WINO_TILE: return per_tile(conv_wino_bx3_kernel<HXV, false>);
+    case WINO_WIDE:
+      if (p.stats) return persistent(p.pool ? k_wide<HXV, true, true, true> : k_wide<HXV, true, false, true>);   // (DMA4 only)
+      if (p.pool) return persistent(p.dma4 ? k_wide<HXV, true, true> : k_wide<HXV, false, true>);
+      return persistent(p.dma4 ? k_wide<HXV, true> : k_wide<HXV, false>);
+    case WINO_KSPLIT: break;                                              // conv_wino_bx3_launch_ksplit's
   }
-  const bool small = x_small(a);
-  if (HXV && small && wino_persist() && x_co32(a) && (reinterpret_cast<uintptr_t>(a.x) & 15) == 0) {
-    if (x_half(a)) {
-      a.tiles_x = 1;
-      a.tiles_y = 2;
-      a.co_tiles = a.Cout / X_CO;
-      const int64_t nblk = (int64_t)a.B * 2 * a.co_tiles;
-      if (nblk > 0x7fffffff) return IPDM_EUNSUPPORTED;
-      return ipdm_launch_lds(conv_wino_bx3_wide_kernel<true, 8, 4, true, true, false, false, false, false, false, true>,
-                             dim3(ipdm_persistent_grid(nblk)), dim3(512), X_LDS_BYTES, s, a, (int)nblk);
-    }
-    a.tiles_x = (a.W + 15) / 16;
-    a.tiles_y = (a.H + 15) / 16;
-    a.co_tiles = a.Cout / 32;
-    const int64_t nblk = (int64_t)a.B * a.tiles_x * a.tiles_y * a.co_tiles;
-    if (nblk > 0x7fffffff) return IPDM_EUNSUPPORTED;
-    return ipdm_launch_lds(conv_wino_bx3_wide_kernel<true, 8, 8, true, true, false, false, false, false, true>,
-                           dim3(ipdm_persistent_grid(nblk)), dim3(512), X_LDS_BYTES, s, a, (int)nblk);
-  }
-  const bool small_dma = small && wino_persist() && x_small_dma(a);
-  // the pooled epilogue lives in the persistent wide kernels only (the ConvMeanPool layers of the score nets are 32..128
-  // pixels wide); everything else reports "unsupported" and the caller runs convolution + mean-pool separately
-  if (a.pool2 && (small || !wino_persist() || a.Cin < 2 * X_KC || a.H % 2 || a.W % 2)) return IPDM_EUNSUPPORTED;
-  if (small_dma) {
-    a.tiles_x = (a.W + 15) / 16;
-    a.tiles_y = (a.H + 15) / 16;
-  } else if (small) {
-    a.tiles_x = ((a.H * a.W) / 4 + X_TILES - 1) / X_TILES;
-    a.tiles_y = 1;
-  } else {
-    a.tiles_x = (a.W + 2 * X_TX - 1) / (2 * X_TX);
-    a.tiles_y = (a.H + 2 * X_TY - 1) / (2 * X_TY);
-  }
-  a.co_tiles = a.Cout / X_CO;
-  const int64_t nblk = (int64_t)a.B * a.tiles_x * a.tiles_y * a.co_tiles;
-  if (nblk > 0x7fffffff) return IPDM_EUNSUPPORTED;
-  const dim3 grid(ipdm_persistent_grid(nblk));                         // one 128+24 KiB workgroup per CU
-  static int dma4_ok = -1;                       // IPDM_WBX3_DMA4=0: dword LDS-DMA everywhere (tuning / fallback)
-  if (dma4_ok < 0) {
-    const char* e = getenv("IPDM_WBX3_DMA4");
-    dma4_ok = e ? atoi(e) : 1;
-  }
-  const bool dma4 = dma4_ok && a.W % 4 == 0 && (reinterpret_cast<uintptr_t>(a.x) & 15) == 0;
-  if (a.stats && (small || !wino_persist() || a.Cin < 2 * X_KC)) return IPDM_EUNSUPPORTED;
-  if (small_dma) {
-    if (dma4) return ipdm_launch_lds(conv_wino_bx3_wide_kernel<HXV, 8, 8, true, true>, grid, dim3(512), X_LDS_BYTES, s, a, (int)nblk);
-    return ipdm_launch_lds(conv_wino_bx3_wide_kernel<HXV, 8, 8, true, false>, grid, dim3(512), X_LDS_BYTES, s, a, (int)nblk);
-  }
-  if (small) return ipdm_launch_lds(conv_wino_bx3_kernel<HXV, true>, dim3((unsigned)nblk), dim3(512), X_LDS_BYTES, s, a);
-  if (!(wino_persist() && a.Cin >= 2 * X_KC))
-    return ipdm_launch_lds(conv_wino_bx3_kernel<HXV, false>, dim3((unsigned)nblk), dim3(512), X_LDS_BYTES, s, a);
-  if (a.stats) {
-    if (!dma4) return IPDM_EUNSUPPORTED;
-    if (a.pool2)
-      return ipdm_launch_lds(conv_wino_bx3_wide_kernel<HXV, 16, 4, false, true, true, true>, grid, dim3(512), X_LDS_BYTES, s, a, (int)nblk);
-    return ipdm_launch_lds(conv_wino_bx3_wide_kernel<HXV, 16, 4, false, true, false, true>, grid, dim3(512), X_LDS_BYTES, s, a, (int)nblk);
-  }
-  if (a.pool2 && dma4)
-    return ipdm_launch_lds(conv_wino_bx3_wide_kernel<HXV, 16, 4, false, true, true>, grid, dim3(512), X_LDS_BYTES, s, a, (int)nblk);
-  if (a.pool2)
-    return ipdm_launch_lds(conv_wino_bx3_wide_kernel<HXV, 16, 4, false, false, true>, grid, dim3(512), X_LDS_BYTES, s, a, (int)nblk);
-  if (dma4) return ipdm_launch_lds(conv_wino_bx3_wide_kernel<HXV, 16, 4, false, true>, grid, dim3(512), X_LDS_BYTES, s, a, (int)nblk);
-  return ipdm_launch_lds(conv_wino_bx3_wide_kernel<HXV, 16, 4, false, false>, grid, dim3(512), X_LDS_BYTES, s, a, (int)nblk);
+  return IPDM_EUNSUPPORTED;
 }
 
 int conv_wino_bx3_launch(ConvArgs a, hipStream_t s) {
   return a.hx ? conv_wino_bx3_launch_t<true>(a, s) : conv_wino_bx3_launch_t<false>(a, s);
 }
 
-// K parts that pay for a layer shape (a function of the SHAPE only, so that a sample's bits do not depend on its batch):
-// undilated images of at most 16 x 16 pixels with fewer than 512 output channels -- (image, channel tile) pairs alone fill
-// under half of the chip at the production batch -- run as two K halves when each half keeps at least two chunks
-int wino_bx3_ksplit_for(int Cin, int Cout, int H, int W, int dilation) {
-  static int enabled = -1;                       // IPDM_WBX3_KSPLIT=0: off (tuning / fallback)
-  if (enabled < 0) {
-    const char* e = getenv("IPDM_WBX3_KSPLIT");
-    enabled = e ? atoi(e) : 1;
-  }
-  if (!enabled || !wino_persist()) return 1;
-  if (dilation != 1 || W > 16 || H > 16 || W % 4 || H % 2 || Cout % X_CO || Cout >= 512) return 1;
-  if (Cin % (2 * X_KC) || Cin / X_KC < 4) return 1;
-  return 2;
-}
-
 template <bool HXV>
 static int conv_wino_bx3_launch_ksplit_t(ConvArgs a, int ksplit, float* work, hipStream_t s) {
-  if (ksplit != wino_bx3_ksplit_for(a.Cin, a.Cout, a.H, a.W, a.dil) || ksplit < 2 || !work) return IPDM_EUNSUPPORTED;
-  if ((reinterpret_cast<uintptr_t>(a.x) & 15) != 0) return IPDM_EUNSUPPORTED;          // 16-byte LDS-DMA form only
+  const WinoPlan p = wino_bx3_ksplit_plan(wino_shape_of(a), wino_switches(), ksplit);
+  if (p.rc != IPDM_OK || !work) return IPDM_EUNSUPPORTED;
   const float* bias = a.bias;
   const float* residual = a.residual;
   float* out = a.out;
   float* out_act = a.out_act;
-  a.tiles_x = (a.W + 15) / 16;
-  a.tiles_y = (a.H + 15) / 16;
-  a.co_tiles = a.Cout / X_CO;
+  a.tiles_x = p.tiles_x;
+  a.tiles_y = p.tiles_y;
+  a.co_tiles = p.co_tiles;
   a.ksplit = ksplit;
   a.bias = nullptr; a.residual = nullptr; a.out_act = nullptr; a.out = work; a.pool2 = 0; a.stats = nullptr;
   float* const amax_out = a.amax_out;
@@ -1759,10 +1649,7 @@ static int conv_wino_bx3_launch_ksplit_t(ConvArgs a, int ksplit, float* work, hi
   a.res_second = 0;
   const float out_scale = a.out_scale;
   a.out_scale = 1.f;                              // the parts are raw sums: bias / residual / scale belong to the reduce pass
-  const int64_t nblk = (int64_t)a.B * a.tiles_x * a.tiles_y * a.co_tiles * ksplit;
-  if (nblk > 0x7fffffff) return IPDM_EUNSUPPORTED;
-  const int rc = ipdm_launch_lds(conv_wino_bx3_wide_kernel<HXV, 8, 8, true, true, false, false, true>, dim3(ipdm_persistent_grid(nblk)),
-                                 dim3(512), X_LDS_BYTES, s, a, (int)nblk);
+  const int rc = ipdm_launch_lds(k_ksplit<HXV>, dim3(ipdm_persistent_grid(p.nblk)), dim3(512), X_LDS_BYTES, s, a, (int)p.nblk);
   if (rc != IPDM_OK) return rc;
   const int64_t plane = (int64_t)a.H * a.W, total = (int64_t)a.B * a.Cout * plane;
   hipLaunchKernelGGL(bx3_splitk_reduce_kernel, splitk_reduce_grid(a.B, (int64_t)a.Cout * plane, amax_out || amax_act), dim3(256), 0, s, work, ksplit, bias, residual,
@@ -1817,10 +1704,7 @@ extern "C" int ipdm_conv_wino_bx3_pack_weight(const float* w, void* U, int Cout,
 }
 
 extern "C" int ipdm_conv2d_wino_bx3_supported(int Cin, int Cout, int H, int W, int dilation) {
-  ConvArgs a;
-  a.coef = nullptr; a.act = IPDM_ACT_NONE; a.dil = dilation; a.D = 1; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W;
-  a.B = 1;
-  return wino_bx3_ok(a, 3) ? 1 : 0;
+  return wino_bx3_ok(conv_query_args(Cin, Cout, 1, H, W, dilation), 3) ? 1 : 0;
 }
 
 static int wino_bx3_entry(const float* x, const void* U, const float* bias, const float* residual, float* out,
@@ -1829,14 +1713,9 @@ static int wino_bx3_entry(const float* x, const void* U, const float* bias, cons
   IPDM_REQUIRE(B >= 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0 && dilation >= 1);
   if (B == 0) return IPDM_OK;
   IPDM_REQUIRE(x && U && (out || out_act) && x != out && x != out_act);
-  ConvArgs a;
-  a.x = x; a.wt = (const float*)U; a.bias = bias; a.coef = nullptr; a.residual = residual; a.out = out; a.out_act = out_act;
-  a.act_out = act_out; a.B = B; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W; a.dil = dilation; a.act = IPDM_ACT_NONE;
-  a.D = 1; a.kd = 1; a.tiles_x = a.tiles_y = a.co_tiles = 0; a.dbg = conv_debug_stamps();
+  ConvArgs a = conv_launch_args(x, U, bias, residual, out, out_act, act_out, B, Cin, Cout, 1, H, W, 3, dilation, hx, ext, conv_debug_stamps());
   a.pool2 = pool2 ? 1 : 0;
   a.stats = stats;
-  a.hx = hx;
-  conv_apply_ext(a, ext, hx);
   if (!wino_bx3_ok(a, 3) || !wino_pairs_aligned(a)) return IPDM_EUNSUPPORTED;
   return conv_wino_bx3_launch(a, ipdm_stream(stream));
 }
@@ -1851,22 +1730,14 @@ extern "C" int ipdm_conv2d_wino_bx3_f32(const float* x, const void* U, const flo
  * parts (1: use the plain call; a function of the layer shape only), the _f32 call runs the parts into `work`
  * (ksplit * B * Cout * H * W floats) and adds them in fixed order with bias / residual / activation. */
 extern "C" int ipdm_conv2d_wino_bx3_splitk(int Cin, int Cout, int H, int W, int dilation) {
-  ConvArgs a;
-  a.coef = nullptr; a.act = IPDM_ACT_NONE; a.dil = dilation; a.D = 1; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W; a.B = 1;
-  if (!wino_bx3_ok(a, 3)) return 1;
-  return wino_bx3_ksplit_for(Cin, Cout, H, W, dilation);
+  if (!wino_bx3_ok(conv_query_args(Cin, Cout, 1, H, W, dilation), 3)) return 1;
+  return wino_bx3_ksplit_for(Cin, Cout, H, W, dilation, wino_switches());
 }
 
 /* the instantiation the f16x2 plain call runs for a layer shape (IPDM_WINO_FORM_*, include/ipdm.h; 16-byte aligned input, plain
  * epilogue; a function of the layer shape and the IPDM_WBX3_* switches only) */
 extern "C" int ipdm_conv2d_wino_hx2_form(int Cin, int Cout, int H, int W, int dilation) {
-  ConvArgs a;
-  a.x = nullptr; a.coef = nullptr; a.act = IPDM_ACT_NONE; a.dil = dilation; a.D = 1; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W;
-  a.B = 1; a.hx = 1; a.pool2 = 0; a.stats = nullptr;
-  if (Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || dilation < 1 || !wino_bx3_ok(a, 3)) return IPDM_EUNSUPPORTED;
-  if (x_poly(a)) return IPDM_WINO_FORM_POLY;
-  if (x_small(a) && wino_persist() && x_co32(a)) return x_half(a) ? IPDM_WINO_FORM_HALF : IPDM_WINO_FORM_CO32;
-  return IPDM_WINO_FORM_OTHER;
+  return wino_hx2_form(Cin, Cout, H, W, dilation, wino_switches());
 }
 
 static int wino_bx3_splitk_entry(const float* x, const void* U, const float* bias, const float* residual, float* out,
@@ -1876,12 +1747,8 @@ static int wino_bx3_splitk_entry(const float* x, const void* U, const float* bia
   if (B == 0) return IPDM_OK;
   IPDM_REQUIRE(x && U && work && (out || out_act) && x != out && x != out_act);
   IPDM_REQUIRE(B <= 65535 || !ext || (!ext->out_amax && !ext->act_amax));
-  ConvArgs a;
-  a.x = x; a.wt = (const float*)U; a.bias = bias; a.coef = nullptr; a.residual = residual; a.out = out; a.out_act = out_act;
-  a.act_out = act_out; a.B = B; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W; a.dil = dilation; a.act = IPDM_ACT_NONE;
-  a.D = 1; a.kd = 1; a.tiles_x = a.tiles_y = a.co_tiles = 0; a.dbg = nullptr;
-  a.hx = hx;
-  conv_apply_ext(a, ext, hx);
+  const ConvArgs a = conv_launch_args(x, U, bias, residual, out, out_act, act_out, B, Cin, Cout, 1, H, W, 3, dilation, hx, ext,
+                                      nullptr);               // (no stamps: dbg = NULL)
   if (!wino_bx3_ok(a, 3)) return IPDM_EUNSUPPORTED;
   return conv_wino_bx3_launch_ksplit(a, ksplit, work, ipdm_stream(stream));
 }
@@ -1911,12 +1778,7 @@ extern "C" int ipdm_conv2d_wino_hx2_splitk_f32(const float* x, const void* U, co
 
 // partials per plane the statistics epilogue writes for this layer shape (0: that epilogue does not serve it)
 extern "C" int ipdm_conv2d_wino_bx3_stats_partials(int Cin, int Cout, int H, int W, int dilation, int pool2) {
-  ConvArgs a;
-  a.coef = nullptr; a.act = IPDM_ACT_NONE; a.dil = dilation; a.D = 1; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W; a.B = 1;
-  a.pool2 = pool2 ? 1 : 0;
-  if (!wino_bx3_ok(a, 3) || x_small(a) || !wino_persist() || Cin < 2 * X_KC || W % 4 != 0) return 0;
-  if (pool2 && (H % 2 || W % 2)) return 0;
-  return 2 * ((W + 2 * X_TX - 1) / (2 * X_TX)) * ((H + 2 * X_TY - 1) / (2 * X_TY));
+  return wino_stats_partials(Cin, Cout, H, W, dilation, pool2, wino_switches());
 }
 
 extern "C" int ipdm_conv2d_wino_bx3_stats_f32(const float* x, const void* U, const float* bias, const float* residual,

@@ -435,11 +435,7 @@ extern "C" int64_t ipdm_fft2c_workspace_bytes(int batch, int H, int W) {
 
 // IPDM_SENSE_COILS=0: the one-workgroup-per-sample kernel (tuning / comparison; same bits)
 static int sense_coil_parallel() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("IPDM_SENSE_COILS");
-    v = e ? atoi(e) : 1;
-  }
+  static const int v = ipdm_env_int("IPDM_SENSE_COILS", 1);
   return v;
 }
 

@@ -1,6 +1,8 @@
-// Host-side launch helpers shared by every kernel family: the dynamic-LDS opt-in and the persistent-grid rule.  Their state
-// (one grant table, one CU count per device, one call counter) lives in launch.hip.
+// Host-side launch helpers shared by every kernel family: the dynamic-LDS opt-in, the persistent-grid rule and the reader of
+// the environment switches (env_int.h).  The state of the first two (one grant table, one CU count per device, one call
+// counter) lives in launch.hip.
 #pragma once
+#include "env_int.h"
 #include "ipdm_common.h"
 
 // Raises hipFuncAttributeMaxDynamicSharedMemorySize of `kernel` on the CURRENT device to `bytes` unless that much was granted

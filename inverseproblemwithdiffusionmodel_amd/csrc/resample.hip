@@ -11,6 +11,7 @@
 //
 // Semantics follow op/upfirdn2d.py:168-209 (upfirdn2d_native) / op/upfirdn2d_kernel.cu:49-105 and
 // op/fused_bias_act_kernel.cu:19-49 of the reference.
+#include "env_int.h"
 #include "ipdm_common.h"
 #include <stdlib.h>
 #include <type_traits>
@@ -303,7 +304,7 @@ int launch_stream(const float* in, const float* kernel, float* out, const Upfird
   // in flight chip-wide -- long strips (few threads, each streaming many rows: the (NR - ADV)-row halo is amortised and the
   // window loads of a group are all independent) until the thread count drops below that; 128 K threads for the
   // down-sampler (8 loads per group), 350 K for the up-sampler (3).  IPDM_FIR_GPS overrides (tuning).
-  static const int tune_gps = getenv("IPDM_FIR_GPS") ? atoi(getenv("IPDM_FIR_GPS")) : 0;
+  static const int tune_gps = ipdm_env_int("IPDM_FIR_GPS", 0);
   long long gps = (long long)p.major * groups * nq * (G::ADV * G::NW) >> 20;
   gps = gps < 1 ? 1 : (gps > 32 ? 32 : gps);
   if (tune_gps > 0) gps = tune_gps;

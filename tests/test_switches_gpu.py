@@ -12,7 +12,8 @@ another, and asserts per arm:
   * inside the arm, a sample's bits do not depend on its batch and the per-image maxima are exact (flags the child computes);
   * THE SWITCH TOOK EFFECT: an observable named in ARMS differs from the baseline child's.  `IPDM_W1D_COMPACT`, `IPDM_FIR_GPS`
     have no host-visible observable (the former picks a column mapping inside the launcher, the latter a strip length): for
-    them the parent asserts that the name occurs as a getenv("...") literal in csrc/, so a renamed switch cannot turn the arm
+    them the parent asserts that the name occurs as an ipdm_env_int("...") literal in csrc/ (the one reader of the native
+    switches, env_int.h), so a renamed switch cannot turn the arm
     into a second baseline;
   * bit-identity with the baseline where the source claims it (`IPDM_BX3_KSPLIT`: conv_bx3.hip, "the answer is either 1 or the
     number of groups, and both give bit-identical results"); everywhere else the parent only prints whether the bits were equal.
@@ -478,7 +479,7 @@ def test_switch(arm, baseline, refs, tmp_path_factory):
         src = "".join(open(f).read() for f in glob.glob(os.path.join(REPO, "inverseproblemwithdiffusionmodel_amd", "csrc", "*.hip")) +
                       glob.glob(os.path.join(REPO, "inverseproblemwithdiffusionmodel_amd", "csrc", "*.h")))
         for name in literals:
-            assert f'getenv("{name}")' in src, f"{name} is no longer read by the native code: the arm would be a second baseline"
+            assert f'ipdm_env_int("{name}"' in src, f"{name} is no longer read by the native code: the arm would be a second baseline"
     same = [k for k in results if np.array_equal(results[k], base_results[k])]
     print(f"[{arm}] {len(same)} of {len(results)} results bit-identical to the baseline; differing: "
           + ", ".join(sorted(set(results) - set(same))[:12]))
