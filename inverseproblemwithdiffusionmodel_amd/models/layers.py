@@ -85,14 +85,12 @@ class Conv(ops.PackedWeightMixin, nn.Module):
         bias = None if self.bias is None else self.bias.data
         if bias_rows is not None:
             bias = bias_rows
-        if (self.kernel_size == 3 and self.dilation == 1 and residual is None and min(self.in_planes, self.out_planes) <= 3
-                and ops.conv3x3_thin_ok(self.in_planes, self.out_planes, x.shape[2], x.shape[3], x)):
+        route = ops.conv_route("sde", 2, self.kernel_size, self.dilation, self.in_planes, self.out_planes, tuple(x.shape[2:]),
+                               x.data_ptr() % 16 == 0, impl, residual=residual is not None, want_stats=want_stats)
+        if route == ops.ROUTE_THIN:
             return ops.conv3x3_thin(x, self.weight.data, bias)         # first / last layer: streaming kernels
-        if (ops.impl_unbounded() in ops.SPLIT_IMPLS and self.kernel_size == 3
-                and ops.wino_bx3_pays(self.in_planes, self.out_planes, x.shape[2], x.shape[3], self.dilation)):
-            one_d = (impl == "hx2" and x.data_ptr() % 16 == 0
-                     and ops.wino1d_pays(self.in_planes, self.out_planes, x.shape[2], x.shape[3], self.dilation))
-            return ops.conv2d_wino_bx3(x, self.packed_wino1d() if one_d else self.packed_wino(), bias, residual,
+        if route in (ops.ROUTE_WINO1D, ops.ROUTE_WINO_SPLIT):
+            return ops.conv2d_wino_bx3(x, self.packed_wino1d() if route == ops.ROUTE_WINO1D else self.packed_wino(), bias, residual,
                                        dilation=self.dilation, in_amax=amax, out_scale=out_scale, want_amax=produce,
                                        want_stats=want_stats and GN_FROM_PARTIALS)
         return ops.conv2d(x, self.packed(), bias, residual=residual, dilation=self.dilation, in_amax=amax, out_scale=out_scale,

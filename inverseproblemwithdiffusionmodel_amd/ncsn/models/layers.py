@@ -86,12 +86,17 @@ class Conv2d(ops.PackedWeightMixin, nn.Module):
     def packed_wino1d(self):
         return self._cached("wino1d", ops.conv_wino1d_weight)
 
+    def route(self, x, site="ncsn", coef=None, **call):
+        """ops.conv_route's answer for this layer reading x (`call`: the options of the call that the route looks at)"""
+        return ops.conv_route(site, self.ndim, self.kernel_size, self.dilation, self.in_planes, self.out_planes, tuple(x.shape[2:]),
+                              x.data_ptr() % 16 == 0, ops.CONV_IMPL, winograd=USE_WINOGRAD, fuse_pool=FUSE_POOL,
+                              full_range=self.full_range, coef=coef is not None,
+                              coef_bound=getattr(coef, "_ipdm_amax_bound", None) is not None, **call)
+
     def fuses_input(self, x, coef):
         """True when this layer takes act(InstanceNorm++(x)) as (raw x, coefficients): the 1-D Winograd kernel applies the affine +
         ELU to the raw rows in its producer, so the normalised tensor is never written (IPDM_WINO1D_FIN=0: the separate pass)"""
-        return (ops.WINO1D_FIN and USE_WINOGRAD and ops.split_impl() and self.ndim == 2 and self.kernel_size == 3 and x.dim() == 4
-                and x.data_ptr() % 16 == 0 and (not ops.dynamic_range() or getattr(coef, "_ipdm_amax_bound", None) is not None)
-                and ops.wino1d_pays(self.in_planes, self.out_planes, x.shape[2], x.shape[3], self.dilation))
+        return self.route(x, coef=coef, act=ops.ACT_ELU) == ops.ROUTE_WINO1D
 
     def packed_conv1d(self):
         return self._cached("conv1d", ops.conv1d_weight)
@@ -104,8 +109,7 @@ class Conv2d(ops.PackedWeightMixin, nn.Module):
 
     def conv1d_ok(self, x):
         """True when the 1-D kernel takes this layer (its shape alone decides: ops.conv1d_pays)"""
-        return (self.ndim == 1 and not self.full_range
-                and ops.conv1d_pays(self.in_planes, self.out_planes, x.shape[2], self.kernel_size, self.dilation))
+        return self.ndim == 1 and self.route(x) == ops.ROUTE_SEQ
 
     def packed(self):
         if self.full_range and ops.CONV_IMPL == "hx2":
@@ -126,49 +130,35 @@ class Conv2d(ops.PackedWeightMixin, nn.Module):
         produce = dyn and feeds_conv
         if in_amax is None and dyn and coef is None and act == ops.ACT_NONE:
             in_amax = ops.in_amax_for(x)
-        if self.ndim == 1:
-            # (N, C, L) sequences (layers1d.py): the 1-D kernel where the layer shape is its, else the one-row image on the direct
-            # 2-D kernel -- a fused input (coef / act) is that kernel's too
-            if out is not None:
-                raise NotImplementedError("Conv2d(ndim=1): no `out=` form")
-            if coef is None and act == ops.ACT_NONE and self.conv1d_ok(x):
-                return ops.conv1d(x, self.packed_conv1d(), bias, residual, self.dilation, act_out=act_out, raw=raw,
-                                  in_amax=in_amax, want_amax=produce, res_second=res_second)
-            return ops.conv1d_rows(x, self.packed_rows(), bias, coef, act, residual, self.dilation, act_out=act_out, raw=raw,
-                                   in_amax=in_amax, want_amax=produce, res_second=res_second)
-        if coef is not None and act == ops.ACT_ELU and out is None and self.fuses_input(x, coef):
+        if self.ndim == 1 and out is not None:
+            raise NotImplementedError("Conv2d(ndim=1): no `out=` form")
+        route = self.route(x, coef=coef, act=act, residual=residual is not None, out=out is not None, act_out=act_out, raw=raw,
+                           want_stats=want_stats)
+        tail = dict(act_out=act_out, raw=raw, in_amax=in_amax, want_amax=produce, res_second=res_second)
+        # (N, C, L) sequences (layers1d.py): the 1-D kernel where the layer shape is its, else the one-row image on the direct
+        # 2-D kernel -- a fused input (coef / act) is that kernel's too
+        if route == ops.ROUTE_SEQ:
+            return ops.conv1d(x, self.packed_conv1d(), bias, residual, self.dilation, **tail)
+        if route == ops.ROUTE_ROWS:
+            return ops.conv1d_rows(x, self.packed_rows(), bias, coef, act, residual, self.dilation, **tail)
+        if route == ops.ROUTE_WINO1D and coef is not None:               # the fused input (fuses_input)
             return ops.conv2d_wino_bx3(x, self.packed_wino1d(), bias, residual, act_out=act_out, raw=raw, want_stats=want_stats,
                                        in_amax=getattr(coef, "_ipdm_amax_bound", None) if dyn else None, want_amax=produce,
                                        res_second=res_second, coef=coef, act=act)
-        if (self.ndim == 2 and self.kernel_size == 3 and self.dilation == 1 and act == ops.ACT_NONE
-                and residual is None and out is None and act_out == ops.ACT_NONE and raw and x.dim() == 4
-                and (self.in_planes <= 3 or (self.out_planes <= 3 and coef is None))
-                and ops.conv3x3_thin_ok(self.in_planes, self.out_planes, x.shape[2], x.shape[3], x)):
+        if route == ops.ROUTE_THIN:
             return ops.conv3x3_thin(x, self.weight.data, bias, coef)   # first / last layer: streaming kernels
-        if (USE_WINOGRAD and ops.CONV_IMPL == "f32" and self.ndim == 2 and self.kernel_size == 3 and coef is None and act == ops.ACT_NONE
-                and out is None
-                and ops.conv_wino_supported(self.in_planes, self.out_planes, x.shape[2], x.shape[3], self.dilation)):
+        if route == ops.ROUTE_WINO_F32:
             return ops.conv2d_wino(x, self.packed_wino(), bias, residual, act_out=act_out, raw=raw,
                                    dilation=self.dilation)
-        if (USE_WINOGRAD and ops.split_impl() and self.ndim == 2 and self.kernel_size == 3 and coef is None
-                and act == ops.ACT_NONE and out is None and ops.wino_bx3_pays(self.in_planes, self.out_planes, x.shape[2],
-                                                                              x.shape[3], self.dilation)):
-            one_d = (x.data_ptr() % 16 == 0 and act_out in (ops.ACT_NONE, ops.ACT_ELU, ops.ACT_COPY)
-                     and (ops.WINO1D_STATS or not (want_stats and raw and ops.USE_STATS_EPILOGUE))
-                     and ops.wino1d_pays(self.in_planes, self.out_planes, x.shape[2], x.shape[3], self.dilation))
-            return ops.conv2d_wino_bx3(x, self.packed_wino1d() if one_d else self.packed_wino_bx3(), bias, residual,
+        if route in (ops.ROUTE_WINO1D, ops.ROUTE_WINO_SPLIT):
+            return ops.conv2d_wino_bx3(x, self.packed_wino1d() if route == ops.ROUTE_WINO1D else self.packed_wino_bx3(), bias, residual,
                                        act_out=act_out, raw=raw, dilation=self.dilation, want_stats=want_stats, in_amax=in_amax,
                                        want_amax=produce, res_second=res_second)
-        if (self.ndim == 3 and self.kernel_size == 3 and self.dilation == 1 and coef is None and act == ops.ACT_NONE and out is None
-                and x.dim() == 5 and x.data_ptr() % 16 == 0 and act_out in (ops.ACT_NONE, ops.ACT_ELU, ops.ACT_COPY)
-                and ops.wino1d_vol_pays(self.in_planes, self.out_planes, x.shape[2], x.shape[3], x.shape[4])):
-            return ops.conv3d(x, self._cached("wino1d_vol", ops.conv_wino1d_weight3d), bias, residual=residual, act_out=act_out,
-                              raw=raw, in_amax=in_amax, want_amax=produce, res_second=res_second)
-        if self.ndim == 3:
-            return ops.conv3d(x, self.packed(), bias, coef, act, residual, self.dilation, act_out=act_out, raw=raw,
-                              in_amax=in_amax, want_amax=produce, res_second=res_second)
-        return ops.conv2d(x, self.packed(), bias, coef, act, residual, self.dilation, out=out, act_out=act_out, raw=raw,
-                          in_amax=in_amax, want_amax=produce, res_second=res_second)
+        if route == ops.ROUTE_WINO1D_VOL:
+            return ops.conv3d(x, self._cached("wino1d_vol", ops.conv_wino1d_weight3d), bias, residual=residual, **tail)
+        if route == ops.ROUTE_DIRECT3D:
+            return ops.conv3d(x, self.packed(), bias, coef, act, residual, self.dilation, **tail)
+        return ops.conv2d(x, self.packed(), bias, coef, act, residual, self.dilation, out=out, **tail)
 
 
 def conv1x1(in_planes, out_planes, stride=1, bias=True, spec_norm=False, ndim=2):
@@ -216,32 +206,23 @@ class ConvMeanPool(nn.Module):
         """3x3 ConvMeanPool (+ pooled-size residual, + activated copy) in ONE launch: the Winograd kernel's 2x2 output tile
         is the pooling window.  -> out or (out, out_act); None where the pooled epilogue is not built for this layer."""
         c = self.conv
-        if c.ndim == 1:                                  # the 1-D kernel's pair-mean epilogue
-            if not (FUSE_POOL and coef is None and act == ops.ACT_NONE and c.kernel_size == 3 and inputs.shape[2] % 2 == 0
-                    and c.conv1d_ok(inputs)):
-                return None
-            dyn = ops.dynamic_range()
-            return ops.conv1d(inputs, c.packed_conv1d(), None if c.bias is None else c.bias.data, residual, c.dilation,
+        route = c.route(inputs, site="pool", coef=coef, act=act, act_out=act_out)
+        bias, dyn = None if c.bias is None else c.bias.data, ops.dynamic_range()
+        if route is None:
+            return None
+        if route == ops.ROUTE_SEQ:                       # the 1-D kernel's pair-mean epilogue
+            return ops.conv1d(inputs, c.packed_conv1d(), bias, residual, c.dilation,
                               act_out=act_out, in_amax=ops.in_amax_for(inputs) if dyn else None, want_amax=dyn and feeds_conv,
                               pool2=True)
-        if not (FUSE_POOL and USE_WINOGRAD and ops.split_impl() and c.ndim == 2 and c.kernel_size == 3 and c.dilation == 1
-                and inputs.shape[2] % 2 == 0 and inputs.shape[3] % 2 == 0
-                and ops.wino_bx3_pays(c.in_planes, c.out_planes, inputs.shape[2], inputs.shape[3], 1)):
-            return None
-        one_d = (inputs.data_ptr() % 16 == 0 and act_out in (ops.ACT_NONE, ops.ACT_ELU, ops.ACT_COPY) and ops.WINO1D_STATS
-                 and ops.wino1d_pays(c.in_planes, c.out_planes, inputs.shape[2], inputs.shape[3], 1))
         try:
             if coef is not None:                         # fused input: the 1-D kernel's only (the caller asked c.fuses_input)
-                if not one_d:
-                    return None
-                return ops.conv2d_wino_bx3(inputs, c.packed_wino1d(), None if c.bias is None else c.bias.data, residual,
+                return ops.conv2d_wino_bx3(inputs, c.packed_wino1d(), bias, residual,
                                            act_out=act_out, pool2=True, want_stats=True,
-                                           in_amax=getattr(coef, "_ipdm_amax_bound", None) if ops.dynamic_range() else None,
-                                           want_amax=ops.dynamic_range() and feeds_conv, coef=coef, act=act)
-            return ops.conv2d_wino_bx3(inputs, c.packed_wino1d() if one_d else c.packed_wino_bx3(),
-                                       None if c.bias is None else c.bias.data, residual,
+                                           in_amax=getattr(coef, "_ipdm_amax_bound", None) if dyn else None,
+                                           want_amax=dyn and feeds_conv, coef=coef, act=act)
+            return ops.conv2d_wino_bx3(inputs, c.packed_wino1d() if route == ops.ROUTE_WINO1D else c.packed_wino_bx3(), bias, residual,
                                        act_out=act_out, pool2=True, want_stats=True,     # a block's result: normalised next
-                                       in_amax=ops.in_amax_for(inputs), want_amax=ops.dynamic_range() and feeds_conv)
+                                       in_amax=ops.in_amax_for(inputs), want_amax=dyn and feeds_conv)
         except _lib.IpdmUnsupported:
             return None
 

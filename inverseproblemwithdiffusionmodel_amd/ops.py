@@ -1367,6 +1367,62 @@ def _wino_residual(residual):
     return residual.clone() if residual.data_ptr() % 8 else residual
 
 
+# The frame the convolution wrappers share: _conv_outputs (the output pair and its maxima slots), _need_both (res_second),
+# _trace_open / _conv_done (the CONV_TRACE bracket, the maxima tags and the return convention), _chunks (the batch loop).
+def _conv_outputs(x, shape, raw, act_out, who=None, out=None, want_amax=False, amax_cap=65535):
+    """-> (out, out_act, slot_o, slot_a): the raw result (raw; the caller's `out=` where given) and the activated copy (act_out),
+    fresh float32 tensors of `shape`, and -- want_amax -- a zeroed maxima vector for each of the two that exists (out's first: the
+    arena hands slots out in sequence).  who: the wrapper's name where it refuses raw=False without act_out itself.
+    amax_cap: batches above it get no maxima (the kernels' grid limit); conv1d passes None -- it has no cap"""
+    want_act = act_out != ACT_NONE
+    if who and not raw and not want_act:
+        raise ValueError(f"{who}: raw=False needs act_out")
+    B = x.shape[0]
+    want_amax = (bool(want_amax) and (amax_cap is None or B <= amax_cap) and os.environ.get("IPDM_AMAX_PRODUCE", "1") != "0")
+    slot_o = amax_slot(B, x.device) if want_amax and raw else None
+    slot_a = amax_slot(B, x.device) if want_amax and want_act else None
+    if not raw:
+        out = None
+    elif out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    out_act = torch.empty(shape, dtype=torch.float32, device=x.device) if want_act else None
+    return out, out_act, slot_o, slot_a
+
+
+def _need_both(who, res_second, residual, act_out, raw, how=" (act_out, e.g. ACT_COPY; raw=True)"):
+    if res_second and (residual is None or act_out == ACT_NONE or not raw):
+        raise ValueError(f"{who}: res_second needs a residual and both outputs{how}")
+
+
+def _trace_open():
+    """-> the recorded start event of this call's CONV_TRACE record (None: no census is running)"""
+    if CONV_TRACE is None:
+        return None
+    e0 = torch.cuda.Event(enable_timing=True)
+    e0.record()
+    return e0
+
+
+def _conv_done(e0, out, out_act, slot_o=None, slot_a=None, **record):
+    """the tail of a wrapper: closes the CONV_TRACE bracket (`record`: the shape keys of the census), hangs the maxima on the
+    results and returns them as every wrapper does -- out, or (out, out_act) where an activated copy was asked for"""
+    if e0 is not None:
+        e1 = torch.cuda.Event(enable_timing=True)
+        e1.record()
+        CONV_TRACE.append(dict(record, n_out=int(out is not None) + int(out_act is not None), e0=e0, e1=e1))
+    tag_amax(out, slot_o)
+    tag_amax(out_act, slot_a)
+    return out if out_act is None else (out, out_act)
+
+
+def _chunks(B, nb):
+    """the batch loop of the kernels with 32-bit buffer offsets: B images as launches of nb at most -> per launch (its images,
+    cut), where cut(t) is that launch's slice t[b0:b1] of a per-image operand (None stays None)"""
+    for b0 in range(0, B, nb):
+        b1 = min(B, b0 + nb)
+        yield b1 - b0, lambda t: None if t is None else t[b0:b1]
+
+
 def conv2d_wino(x, U, bias=None, residual=None, act_out=ACT_NONE, raw=True, dilation=1):
     """3x3 / dilation-1 convolution through the Winograd F(2x2,3x3) kernel (same output options as conv2d).
     A residual that does not start on an 8-byte boundary is copied first (_wino_residual: the epilogue fetches pairs)."""
@@ -1374,19 +1430,11 @@ def conv2d_wino(x, U, bias=None, residual=None, act_out=ACT_NONE, raw=True, dila
     residual = _wino_residual(residual)
     B, Cin, H, W = x.shape
     Cout = U.shape[2]
-    want_act = act_out != ACT_NONE
-    out = torch.empty((B, Cout, H, W), dtype=torch.float32, device=x.device) if raw else None
-    out_act = torch.empty((B, Cout, H, W), dtype=torch.float32, device=x.device) if want_act else None
-    if CONV_TRACE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    out, out_act, _, _ = _conv_outputs(x, (B, Cout, H, W), raw, act_out)
+    e0 = _trace_open()
     call("ipdm_conv2d_wino_f32", _ptr(x), _ptr(U), _ptr(bias), _ptr(residual), _ptr(out), _ptr(out_act), act_out,
          B, Cin, Cout, H, W, dilation, _stream())
-    if CONV_TRACE is not None:
-        e1.record()
-        CONV_TRACE.append(dict(B=B, Cin=Cin, Cout=Cout, H=H, W=W, k=3, dil=dilation, wino=True, res=residual is not None,
-                               n_out=int(raw) + int(want_act), e0=e0, e1=e1))
-    return (out, out_act) if want_act else out
+    return _conv_done(e0, out, out_act, B=B, Cin=Cin, Cout=Cout, H=H, W=W, k=3, dil=dilation, wino=True, res=residual is not None)
 
 
 def conv3d(x, wt, bias=None, coef=None, act=ACT_NONE, residual=None, dilation=1, act_out=ACT_NONE, raw=True, in_amax=None,
@@ -1408,19 +1456,11 @@ def conv3d(x, wt, bias=None, coef=None, act=ACT_NONE, residual=None, dilation=1,
     if Cin_w != Cin:
         raise ValueError(f"conv3d: weight Cin {Cin_w} != input Cin {Cin}")
     k = {1: 1, 27: 3}[kk]
-    want_act = act_out != ACT_NONE
-    out = torch.empty((B, Cout, D, H, W), dtype=torch.float32, device=x.device) if raw else None
-    out_act = torch.empty((B, Cout, D, H, W), dtype=torch.float32, device=x.device) if want_act else None
-    if CONV_TRACE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    out, out_act, _, _ = _conv_outputs(x, (B, Cout, D, H, W), raw, act_out)
+    e0 = _trace_open()
     call("ipdm_conv3d_f32", _ptr(x), _ptr(wt), _ptr(bias), _ptr(coef), act, _ptr(residual), _ptr(out), _ptr(out_act),
          act_out, B, Cin, Cout, D, H, W, k, dilation, _stream())
-    if CONV_TRACE is not None:
-        e1.record()
-        CONV_TRACE.append(dict(B=B * D, Cin=Cin, Cout=Cout, H=H, W=W, k=k, dil=dilation, taps3d=kk, res=residual is not None,
-                               n_out=int(raw) + int(want_act), e0=e0, e1=e1))
-    return (out, out_act) if want_act else out
+    return _conv_done(e0, out, out_act, B=B * D, Cin=Cin, Cout=Cout, H=H, W=W, k=k, dil=dilation, taps3d=kk, res=residual is not None)
 
 
 def maxpool3d5(x):
@@ -1461,25 +1501,12 @@ def conv2d(x, wt, bias=None, coef=None, act=ACT_NONE, residual=None, dilation=1,
         raise ValueError(f"conv2d: weight Cin {Cin_w} != input Cin {Cin}")
     k = {1: 1, 9: 3}[kk]
     oh, ow = (H // 2, W // 2) if pool2 else (H, W)
-    want_act = act_out != ACT_NONE
-    if not raw and not want_act:
-        raise ValueError("conv2d: raw=False needs act_out")
-    if raw:
-        out = torch.empty((B, Cout, oh, ow), dtype=torch.float32, device=x.device) if out is None else out
-    else:
-        out = None
-    out_act = torch.empty((B, Cout, oh, ow), dtype=torch.float32, device=x.device) if want_act else None
-    if CONV_TRACE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    out, out_act, _, _ = _conv_outputs(x, (B, Cout, oh, ow), raw, act_out, "conv2d", out)
+    e0 = _trace_open()
     call("ipdm_conv2d_f32", _ptr(x), _ptr(wt), _ptr(bias), _ptr(coef), act, _ptr(residual), _ptr(out), _ptr(out_act),
          act_out, B, Cin, Cout, H, W, k, dilation, int(bool(pool2)), _stream())
     _written(out)
-    if CONV_TRACE is not None:
-        e1.record()
-        CONV_TRACE.append(dict(B=B, Cin=Cin, Cout=Cout, H=H, W=W, k=k, dil=dilation, res=residual is not None,
-                               n_out=int(raw) + int(want_act), e0=e0, e1=e1))
-    return (out, out_act) if want_act else out
+    return _conv_done(e0, out, out_act, B=B, Cin=Cin, Cout=Cout, H=H, W=W, k=k, dil=dilation, res=residual is not None)
 
 
 USE_THIN_CONV = os.environ.get("IPDM_THIN_CONV", "1") != "0"
@@ -1505,18 +1532,13 @@ def conv3x3_thin(x, weight, bias=None, coef=None):
     if tuple(weight.shape) != (Cout, Cin, 3, 3):
         raise ValueError(f"conv3x3_thin: weight {tuple(weight.shape)} does not match input channels {Cin}")
     out = torch.empty((B, Cout, H, W), dtype=torch.float32, device=x.device)
-    if CONV_TRACE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    e0 = _trace_open()
     if coef is not None:
         coef = _gpu(coef, torch.float32, "coef")
         if tuple(coef.shape) != (B, Cin, 3):
             raise ValueError(f"conv3x3_thin: coef {tuple(coef.shape)} != {(B, Cin, 3)}")
     call("ipdm_conv3x3_thin_f32", _ptr(x), _ptr(weight), _ptr(bias), _ptr(coef), _ptr(out), B, Cin, Cout, H, W, _stream())
-    if CONV_TRACE is not None:
-        e1.record()
-        CONV_TRACE.append(dict(B=B, Cin=Cin, Cout=Cout, H=H, W=W, k=3, dil=1, res=False, n_out=1, e0=e0, e1=e1, thin=True))
-    return out
+    return _conv_done(e0, out, None, B=B, Cin=Cin, Cout=Cout, H=H, W=W, k=3, dil=1, res=False, thin=True)
 
 
 # ---- fp32 convolution on the 16-bit matrix cores (exactly split operands) ---------------------------------------
@@ -1677,32 +1699,18 @@ def conv_bx3(x, wq, bias=None, coef=None, act=ACT_NONE, residual=None, dilation=
     bias_per_image = bias is not None and bias.dim() == 2
     if bias_per_image and (tuple(bias.shape) != (x.shape[0], wq.Cout) or bias.stride(1) != 1):
         raise ValueError(f"conv_bx3: per-image bias {tuple(bias.shape)} != {(x.shape[0], wq.Cout)} (rows may be strided, not columns)")
-    want_act = act_out != ACT_NONE
-    want_amax = bool(want_amax) and x.shape[0] <= 65535 and os.environ.get("IPDM_AMAX_PRODUCE", "1") != "0"
-    slot_o = amax_slot(x.shape[0], x.device) if want_amax and raw else None
-    slot_a = amax_slot(x.shape[0], x.device) if want_amax and want_act else None
-    if res_second and (residual is None or not want_act or not raw):
-        raise ValueError("conv_bx3: res_second needs a residual and both outputs (act_out, e.g. ACT_COPY; raw=True)")
-    ext = _conv_ext(wq.fmt, in_amax, x, coef is not None or act != ACT_NONE, bias_per_image, out_scale,
-                    bias.stride(0) if bias_per_image else 0, slot_o, slot_a, res_second)
+    _need_both("conv_bx3", res_second, residual, act_out, raw)
     if wq.Cin != x.shape[1]:
         raise ValueError(f"conv_bx3: weight Cin {wq.Cin} != input Cin {x.shape[1]}")
     vol = x.dim() == 5
     k = {1: 1, 9: 3, 27: 3}[wq.kk]
     if (wq.kk == 27) != (vol and k == 3):
         raise ValueError("conv_bx3: kernel / input rank mismatch")
-    want_act = act_out != ACT_NONE
-    if not raw and not want_act:
-        raise ValueError("conv_bx3: raw=False needs act_out")
     shape = (x.shape[0], wq.Cout) + tuple(x.shape[2:])
-    if raw:
-        out = torch.empty(shape, dtype=torch.float32, device=x.device) if out is None else out
-    else:
-        out = None
-    out_act = torch.empty(shape, dtype=torch.float32, device=x.device) if want_act else None
-    if CONV_TRACE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    out, out_act, slot_o, slot_a = _conv_outputs(x, shape, raw, act_out, "conv_bx3", out, want_amax)
+    ext = _conv_ext(wq.fmt, in_amax, x, coef is not None or act != ACT_NONE, bias_per_image, out_scale,
+                    bias.stride(0) if bias_per_image else 0, slot_o, slot_a, res_second)
+    e0 = _trace_open()
     if vol:
         B, Cin, D, H, W = x.shape
     else:
@@ -1719,15 +1727,9 @@ def conv_bx3(x, wq, bias=None, coef=None, act=ACT_NONE, residual=None, dilation=
     else:
         call(f"ipdm_conv2d_{wq.fmt}_f32", _ptr(x), _ptr(wq.blob), _ptr(bias), _ptr(coef), act, _ptr(residual), _ptr(out),
              _ptr(out_act), act_out, B, Cin, wq.Cout, H, W, k, dilation, ext, _stream())
-    if CONV_TRACE is not None:
-        e1.record()
-        CONV_TRACE.append(dict(B=B * D, Cin=Cin, Cout=wq.Cout, H=H, W=W, k=k, dil=dilation, bx3=True, fmt=wq.fmt, res=residual is not None,
-                               n_out=int(raw) + int(want_act),
-                               taps3d=wq.kk if vol else None, e0=e0, e1=e1))
     _written(out)                                   # (a caller's `out=` tensor: whatever was cached on it is stale)
-    tag_amax(out, slot_o)
-    tag_amax(out_act, slot_a)
-    return (out, out_act) if want_act else out
+    return _conv_done(e0, out, out_act, slot_o, slot_a, B=B * D, Cin=Cin, Cout=wq.Cout, H=H, W=W, k=k, dil=dilation, bx3=True,
+                      fmt=wq.fmt, res=residual is not None, taps3d=wq.kk if vol else None)
 
 
 def conv_wino_bx3_weight(w, fmt="bx3"):
@@ -1773,8 +1775,7 @@ def conv3d_wino1d(x, U, bias=None, residual=None, act_out=ACT_NONE, raw=True, in
     B, Cin, D, H, W = x.shape
     if U.kk != 36 or U.Cin != Cin:
         raise ValueError("conv3d_wino1d: weight blob does not match the input")
-    if res_second and (residual is None or act_out == ACT_NONE or not raw):
-        raise ValueError("conv3d_wino1d: res_second needs a residual and both outputs")
+    _need_both("conv3d_wino1d", res_second, residual, act_out, raw, how="")
     Cout = U.Cout
     if residual is not None and tuple(residual.shape) != (B, Cout, D, H, W):
         raise ValueError(f"conv3d_wino1d: residual {tuple(residual.shape)} != output {(B, Cout, D, H, W)}")
@@ -1782,30 +1783,15 @@ def conv3d_wino1d(x, U, bias=None, residual=None, act_out=ACT_NONE, raw=True, in
     amax_t = None
     if in_amax is not None:
         amax_t = absmax_per_image(x) if in_amax is True else in_amax
-    want_amax = bool(want_amax) and B <= 65535 and os.environ.get("IPDM_AMAX_PRODUCE", "1") != "0"
-    want_act = act_out != ACT_NONE
-    slot_o = amax_slot(B, x.device) if want_amax and raw else None
-    slot_a = amax_slot(B, x.device) if want_amax and want_act else None
-    out = torch.empty((B, Cout, D, H, W), dtype=torch.float32, device=x.device) if raw else None
-    out_act = torch.empty((B, Cout, D, H, W), dtype=torch.float32, device=x.device) if want_act else None
-    if CONV_TRACE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    out, out_act, slot_o, slot_a = _conv_outputs(x, (B, Cout, D, H, W), raw, act_out, want_amax=want_amax)
+    e0 = _trace_open()
     nb = max(1, (0x3fffffff - 1) // (Cin * D * H * W * 4))       # images per launch inside the buffer descriptor's reach
-    for b0 in range(0, B, nb):
-        b1 = min(B, b0 + nb)
-        ext = _conv_ext("hx2", None if amax_t is None else amax_t[b0:b1], x[b0:b1], False, False, 1.0, 0,
-                        None if slot_o is None else slot_o[b0:b1], None if slot_a is None else slot_a[b0:b1], res_second)
-        call("ipdm_conv3d_wino1d_f32", _ptr(x[b0:b1]), _ptr(U.blob), _ptr(bias), _ptr(None if residual is None else residual[b0:b1]),
-             _ptr(None if out is None else out[b0:b1]), _ptr(None if out_act is None else out_act[b0:b1]), act_out, b1 - b0, Cin,
-             Cout, D, H, W, ext, _stream())
-    if CONV_TRACE is not None:
-        e1.record()
-        CONV_TRACE.append(dict(B=B * D, Cin=Cin, Cout=Cout, H=H, W=W, k=3, dil=1, wino=True, bx3=True, fmt="hx2", wino1d=True,
-                               res=residual is not None, n_out=int(raw) + int(want_act), taps3d=27, e0=e0, e1=e1))
-    tag_amax(out, slot_o)
-    tag_amax(out_act, slot_a)
-    return (out, out_act) if want_act else out
+    for n, cut in _chunks(B, nb):
+        ext = _conv_ext("hx2", cut(amax_t), cut(x), False, False, 1.0, 0, cut(slot_o), cut(slot_a), res_second)
+        call("ipdm_conv3d_wino1d_f32", _ptr(cut(x)), _ptr(U.blob), _ptr(bias), _ptr(cut(residual)), _ptr(cut(out)), _ptr(cut(out_act)),
+             act_out, n, Cin, Cout, D, H, W, ext, _stream())
+    return _conv_done(e0, out, out_act, slot_o, slot_a, B=B * D, Cin=Cin, Cout=Cout, H=H, W=W, k=3, dil=1, wino=True, bx3=True,
+                      fmt="hx2", wino1d=True, res=residual is not None, taps3d=27)
 
 
 def wino1d_vol_pays(Cin, Cout, D, H, W, dilation=1):
@@ -1860,18 +1846,6 @@ def conv2d_wino_bx3(x, U, bias=None, residual=None, act_out=ACT_NONE, raw=True, 
     bias_per_image = bias is not None and bias.dim() == 2
     if bias_per_image and (tuple(bias.shape) != (B, U.Cout) or bias.stride(1) != 1):
         raise ValueError(f"conv2d_wino_bx3: per-image bias {tuple(bias.shape)} != {(B, U.Cout)} (rows may be strided, not columns)")
-
-    want_amax = bool(want_amax) and B <= 65535 and os.environ.get("IPDM_AMAX_PRODUCE", "1") != "0"
-    slot_o = amax_slot(B, x.device) if want_amax and raw else None
-    slot_a = amax_slot(B, x.device) if want_amax and act_out != ACT_NONE else None
-
-    def ext_of(b0, b1):
-        return _conv_ext(U.fmt, None if amax_t is None else amax_t[b0:b1], x[b0:b1], False, bias_per_image, out_scale,
-                         bias.stride(0) if bias_per_image else 0,
-                         None if slot_o is None else slot_o[b0:b1], None if slot_a is None else slot_a[b0:b1], res_second)
-
-    def bias_of(b0, b1):
-        return bias[b0:b1] if bias_per_image else bias
     one_d = U.kk == 12                   # conv_wino1d_weight: 1-D Winograd along x (conv_wino1d.hip), plain epilogues only
     if U.kk not in (12, 16) or U.Cin != Cin:
         raise ValueError("conv2d_wino_bx3: weight blob does not match the input")
@@ -1884,72 +1858,49 @@ def conv2d_wino_bx3(x, U, bias=None, residual=None, act_out=ACT_NONE, raw=True, 
         coef = _gpu(coef, torch.float32, "coef")
         if tuple(coef.shape) != (B, Cin, 3):
             raise ValueError(f"conv2d_wino_bx3: coef {tuple(coef.shape)} != {(B, Cin, 3)}")
-    if res_second and (residual is None or act_out == ACT_NONE or not raw):
-        raise ValueError("conv2d_wino_bx3: res_second needs a residual and both outputs (act_out, e.g. ACT_COPY; raw=True)")
+    _need_both("conv2d_wino_bx3", res_second, residual, act_out, raw)
     Cout = U.Cout
-    want_act = act_out != ACT_NONE
     oh, ow = (H // 2, W // 2) if pool2 else (H, W)
     if residual is not None and tuple(residual.shape) != (B, Cout, oh, ow):
         raise ValueError(f"conv2d_wino_bx3: residual {tuple(residual.shape)} != output {(B, Cout, oh, ow)}")
     residual = _wino_residual(residual)
-    out = torch.empty((B, Cout, oh, ow), dtype=torch.float32, device=x.device) if raw else None
-    out_act = torch.empty((B, Cout, oh, ow), dtype=torch.float32, device=x.device) if want_act else None
-    if CONV_TRACE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    out, out_act, slot_o, slot_a = _conv_outputs(x, (B, Cout, oh, ow), raw, act_out, want_amax=want_amax)
+    e0 = _trace_open()
     nb = wino_bx3_max_batch(Cin, H, W, dilation)
+    # 16-pixel layers with few channel tiles: two K halves + a fixed-order reduction
     ksplit = 1 if one_d or pool2 or x.data_ptr() % 16 or (WBX3_CO32 and U.fmt == "hx2") else wino_bx3_splitk(Cin, Cout, H, W, dilation)
-    if ksplit > 1:                       # 16-pixel layers with few channel tiles: two K halves + a fixed-order reduction
-        for b0 in range(0, B, nb):
-            b1 = min(B, b0 + nb)
-            work = torch.empty((ksplit, b1 - b0, Cout, H, W), dtype=torch.float32, device=x.device)
-            call(f"ipdm_conv2d_wino_{U.fmt}_splitk_f32", _ptr(x[b0:b1]), _ptr(U.blob), _ptr(bias_of(b0, b1)),
-                 _ptr(None if residual is None else residual[b0:b1]), _ptr(None if out is None else out[b0:b1]),
-                 _ptr(None if out_act is None else out_act[b0:b1]), act_out, b1 - b0, Cin, Cout, H, W, dilation, ksplit,
-                 _ptr(work), ext_of(b0, b1), _stream())
-        if CONV_TRACE is not None:
-            e1.record()
-            CONV_TRACE.append(dict(B=B, Cin=Cin, Cout=Cout, H=H, W=W, k=3, dil=dilation, wino=True, bx3=True, fmt=U.fmt, res=residual is not None,
-                                   n_out=int(raw) + int(want_act), pool2=False, ksplit=ksplit, e0=e0, e1=e1))
-        tag_amax(out, slot_o)
-        tag_amax(out_act, slot_a)
-        return (out, out_act) if want_act else out
     part = None
-    if want_stats and raw and USE_STATS_EPILOGUE and x.data_ptr() % 16 == 0:
+    if ksplit == 1 and want_stats and raw and USE_STATS_EPILOGUE and x.data_ptr() % 16 == 0:
         P = (int(_lib.lib.ipdm_conv2d_wino1d_stats_partials(Cin, Cout, H, W)) if one_d else
              int(_lib.lib.ipdm_conv2d_wino_bx3_stats_partials(Cin, Cout, H, W, dilation, int(bool(pool2)))))
         if P > 0:
             part = torch.empty((B, Cout, P, 3), dtype=torch.float32, device=x.device)
-    for b0 in range(0, B, nb):           # one launch unless the batch outgrows the kernel's 32-bit buffer offsets
-        b1 = min(B, b0 + nb)
-        args = (_ptr(x[b0:b1]), _ptr(U.blob), _ptr(bias_of(b0, b1)),
-                _ptr(None if residual is None else residual[b0:b1]), _ptr(None if out is None else out[b0:b1]),
-                _ptr(None if out_act is None else out_act[b0:b1]), act_out, b1 - b0, Cin, Cout, H, W, dilation,
-                int(bool(pool2)))
-        am = (ext_of(b0, b1),)
-        if one_d:
-            a1 = args[:3] + (_ptr(None if coef is None else coef[b0:b1]), act) + args[3:-2] + args[-1:]   # (+ fused input, no dilation)
+    for n, cut in _chunks(B, nb):        # one launch unless the batch outgrows the kernel's 32-bit buffer offsets
+        head = (_ptr(cut(x)), _ptr(U.blob), _ptr(cut(bias) if bias_per_image else bias))
+        outs = (_ptr(cut(residual)), _ptr(cut(out)), _ptr(cut(out_act)), act_out, n, Cin, Cout, H, W)
+        ext = _conv_ext(U.fmt, cut(amax_t), cut(x), False, bias_per_image, out_scale, bias.stride(0) if bias_per_image else 0,
+                        cut(slot_o), cut(slot_a), res_second)
+        if ksplit > 1:
+            work = torch.empty((ksplit, n, Cout, H, W), dtype=torch.float32, device=x.device)
+            call(f"ipdm_conv2d_wino_{U.fmt}_splitk_f32", *head, *outs, dilation, ksplit, _ptr(work), ext, _stream())
+        elif one_d:                      # (+ fused input, no dilation)
+            stats = () if part is None else (_ptr(cut(part)),)
+            call("ipdm_conv2d_wino1d_f32" if part is None else "ipdm_conv2d_wino1d_stats_f32", *head, _ptr(cut(coef)), act, *outs,
+                 int(bool(pool2)), *stats, ext, _stream())
+        else:
+            args = head + outs + (dilation, int(bool(pool2)))
             if part is not None:
-                call("ipdm_conv2d_wino1d_stats_f32", *a1, _ptr(part[b0:b1]), *am, _stream())
-            else:
-                call("ipdm_conv2d_wino1d_f32", *a1, *am, _stream())
-            continue
-        if part is not None:
-            try:
-                call(f"ipdm_conv2d_wino_{U.fmt}_stats_f32", *args, _ptr(part[b0:b1]), *am, _stream())
-                continue
-            except _lib.IpdmUnsupported:         # e.g. IPDM_WBX3_DMA4=0: no statistics epilogue on that kernel form
-                part = None
-        call(f"ipdm_conv2d_wino_{U.fmt}_f32", *args, *am, _stream())
+                try:
+                    call(f"ipdm_conv2d_wino_{U.fmt}_stats_f32", *args, _ptr(cut(part)), ext, _stream())
+                    continue
+                except _lib.IpdmUnsupported:         # e.g. IPDM_WBX3_DMA4=0: no statistics epilogue on that kernel form
+                    part = None
+            call(f"ipdm_conv2d_wino_{U.fmt}_f32", *args, ext, _stream())
     if part is not None:
         out._ipdm_partials = (part, (out._version, out.data_ptr()))
-    if CONV_TRACE is not None:
-        e1.record()
-        CONV_TRACE.append(dict(B=B, Cin=Cin, Cout=Cout, H=H, W=W, k=3, dil=dilation, wino=True, bx3=True, fmt=U.fmt, res=residual is not None,
-                               n_out=int(raw) + int(want_act), pool2=bool(pool2), wino1d=one_d, stats=part is not None, e0=e0, e1=e1))
-    tag_amax(out, slot_o)
-    tag_amax(out_act, slot_a)
-    return (out, out_act) if want_act else out
+    form = dict(pool2=False, ksplit=ksplit) if ksplit > 1 else dict(pool2=bool(pool2), wino1d=one_d, stats=part is not None)
+    return _conv_done(e0, out, out_act, slot_o, slot_a, B=B, Cin=Cin, Cout=Cout, H=H, W=W, k=3, dil=dilation, wino=True, bx3=True,
+                      fmt=U.fmt, res=residual is not None, **form)
 
 
 # f16x2 family: the 16-pixel layers whose split-K rule says "two K halves" run as ONE launch of 32-channel workgroups instead
@@ -2025,6 +1976,58 @@ def conv1d_pays(Cin, Cout, L, k, dilation=1):
             and bool(_lib.lib.ipdm_conv1d_hx2_supported(int(Cin), int(Cout), int(L), int(k), int(dilation))))
 
 
+# ---- which kernel runs a layer ------------------------------------------------------------------------------------------------
+ROUTE_THIN, ROUTE_WINO_F32, ROUTE_WINO1D, ROUTE_WINO_SPLIT = "thin", "wino_f32", "wino1d", "wino_split"
+ROUTE_WINO1D_VOL, ROUTE_SEQ, ROUTE_ROWS, ROUTE_DIRECT2D, ROUTE_DIRECT3D = "wino1d_vol", "conv1d", "rows", "direct2d", "direct3d"
+
+
+def conv_route(site, ndim, k, dilation, Cin, Cout, size, aligned, impl, winograd=True, fuse_pool=True, full_range=False,
+               coef=False, coef_bound=False, act=ACT_NONE, residual=False, out=False, act_out=ACT_NONE, raw=True, want_stats=False):
+    """-> the ROUTE_* of one layer call; None: "no fused pooled launch" (site "pool" only).  The ONE place that decides: the
+    modules ask, switch on the answer and forward their arguments.  Pure host code, no tensor: size = x.shape[2:], aligned = x
+    starts on a 16-byte boundary, coef / residual / out = "one is given", coef_bound = the coefficients carry their bound
+    (`_ipdm_amax_bound`).  The switches of this module are read at call time.  The sites differ, on purpose or not:
+    site: "ncsn" = Conv2d.forward, "pool" = ConvMeanPool.fused (a pooled launch or None), "sde" = Conv.forward (score_sde networks)
+    impl: the kernel family -- "ncsn" / "pool" pass CONV_IMPL, "sde" passes impl_unbounded(); wino1d_pays tests CONV_IMPL all the same
+    winograd: "ncsn" / "pool" pass their USE_WINOGRAD; "sde" passes nothing (it does not consult the switch)
+    fuse_pool: "pool" passes its FUSE_POOL; read by no other site
+    coef / act / out / act_out / raw / full_range: "sde" has none of them and passes nothing; "pool" passes coef, act, act_out
+    want_stats: gates the 1-D kernel at "ncsn" only; "pool" demands WINO1D_STATS outright, "sde" has no statistics gate"""
+    plain_in = not coef and act == ACT_NONE
+    if ndim == 1:
+        seq = plain_in and not full_range and conv1d_pays(Cin, Cout, size[0], k, dilation)
+        if site == "pool":
+            return ROUTE_SEQ if fuse_pool and k == 3 and size[0] % 2 == 0 and seq else None
+        return ROUTE_SEQ if seq else ROUTE_ROWS
+    H, W = size[0], size[1]
+    wino = winograd and impl in SPLIT_IMPLS and ndim == 2 and k == 3
+
+    def one_d():                                         # the 1-D Winograd kernel instead of the 2-D one, statistics gate apart
+        return (impl == "hx2" and aligned and act_out in (ACT_NONE, ACT_ELU, ACT_COPY) and wino1d_pays(Cin, Cout, H, W, dilation))
+    if site == "pool":
+        if not (fuse_pool and wino and dilation == 1 and H % 2 == 0 and W % 2 == 0 and wino_bx3_pays(Cin, Cout, H, W, 1)):
+            return None
+        if one_d() and WINO1D_STATS:
+            return ROUTE_WINO1D                          # (with coef: the fused input -- whatever `act` says)
+        return None if coef else ROUTE_WINO_SPLIT        # a fused input is the 1-D kernel's only; `act` alone is not looked at
+    if (site == "ncsn" and coef and act == ACT_ELU and not out and WINO1D_FIN and wino and len(size) == 2 and aligned
+            and (not dynamic_range(impl) or coef_bound) and wino1d_pays(Cin, Cout, H, W, dilation)):
+        return ROUTE_WINO1D                              # act(InstanceNorm++(x)) as (raw x, coefficients): Conv2d.fuses_input
+    if (ndim == 2 and k == 3 and dilation == 1 and act == ACT_NONE and not residual and not out and act_out == ACT_NONE and raw
+            and len(size) == 2 and (Cin <= 3 or (Cout <= 3 and not coef)) and aligned and conv3x3_thin_ok(Cin, Cout, H, W)):
+        return ROUTE_THIN                                # ("sde" writes min(Cin, Cout) <= 3: the same without a coef)
+    if (site == "ncsn" and winograd and impl == "f32" and ndim == 2 and k == 3 and plain_in and not out
+            and conv_wino_supported(Cin, Cout, H, W, dilation)):
+        return ROUTE_WINO_F32
+    if wino and plain_in and not out and wino_bx3_pays(Cin, Cout, H, W, dilation):
+        stats_ok = site == "sde" or WINO1D_STATS or not (want_stats and raw and USE_STATS_EPILOGUE)
+        return ROUTE_WINO1D if one_d() and stats_ok else ROUTE_WINO_SPLIT
+    if (ndim == 3 and k == 3 and dilation == 1 and plain_in and not out and len(size) == 3 and aligned
+            and act_out in (ACT_NONE, ACT_ELU, ACT_COPY) and wino1d_vol_pays(Cin, Cout, *size)):
+        return ROUTE_WINO1D_VOL
+    return ROUTE_DIRECT3D if ndim == 3 else ROUTE_DIRECT2D
+
+
 class PackedConv1d:
     """[Cout, Cin, k] weights as f16x2 MFMA A-fragments + per-output-channel inverse scales (ipdm_conv1d_hx2_pack_weight)"""
     __slots__ = ("blob", "Cout", "Cin", "k")
@@ -2096,35 +2099,20 @@ def conv1d(x, wq, bias=None, residual=None, dilation=1, act_out=ACT_NONE, raw=Tr
     N, Cin, L = (int(v) for v in x.shape)
     if pool2 and L % 2:
         raise ValueError("conv1d: the pair mean needs an even length")
-    want_act = act_out != ACT_NONE
-    if not raw and not want_act:
-        raise ValueError("conv1d: raw=False needs act_out")
-    if res_second and (residual is None or not want_act or not raw):
-        raise ValueError("conv1d: res_second needs a residual and both outputs (act_out, e.g. ACT_COPY; raw=True)")
     shape = (N, wq.Cout, L // 2 if pool2 else L)
+    out, out_act, slot_o, slot_a = _conv_outputs(x, shape, raw, act_out, "conv1d", None, want_amax, amax_cap=None)
+    _need_both("conv1d", res_second, residual, act_out, raw)
     if residual is not None:
         residual = _gpu(residual, torch.float32, "residual")
         if tuple(residual.shape) != shape:
             raise ValueError(f"conv1d: residual {tuple(residual.shape)} != {shape}")
-    want_amax = bool(want_amax) and os.environ.get("IPDM_AMAX_PRODUCE", "1") != "0"
-    slot_o = amax_slot(N, x.device) if want_amax and raw else None
-    slot_a = amax_slot(N, x.device) if want_amax and want_act else None
     ext = _conv_ext("hx2", in_amax, x, False, False, 1.0, 0, slot_o, slot_a, res_second)
-    out = torch.empty(shape, dtype=torch.float32, device=x.device) if raw else None
-    out_act = torch.empty(shape, dtype=torch.float32, device=x.device) if want_act else None
-    if CONV_TRACE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    e0 = _trace_open()
     call("ipdm_conv1d_hx2_f32", _ptr(x), _ptr(wq.blob), _ptr(bias), _ptr(residual), _ptr(out), _ptr(out_act), act_out, N, Cin,
          wq.Cout, L, wq.k, int(dilation), int(bool(pool2)), ext, _stream())
     CONV1D_LAUNCHES += 1
-    if CONV_TRACE is not None:
-        e1.record()
-        CONV_TRACE.append(dict(B=N, Cin=Cin, Cout=wq.Cout, H=1, W=L, k=wq.k, dil=dilation, conv1d=True, res=residual is not None,
-                               n_out=int(raw) + int(want_act), e0=e0, e1=e1))
-    tag_amax(out, slot_o)
-    tag_amax(out_act, slot_a)
-    return (out, out_act) if want_act else out
+    return _conv_done(e0, out, out_act, slot_o, slot_a, B=N, Cin=Cin, Cout=wq.Cout, H=1, W=L, k=wq.k, dil=dilation, conv1d=True,
+                      res=residual is not None)
 
 
 def meanpool1d2(x):
