@@ -341,6 +341,40 @@ int ipdm_coil_apply_c64(const float* y, const float* A, int per_image, float* ou
 int ipdm_coil_compress_c64(const float* y, int ah, int aw, int n_virtual, const float* noise_cov, float* A, float* eig,
                            int32_t* status, float* out, float* work, int B, int n_coils, int H, int W, void* stream);
 
+/* ESPIRiT coil sensitivity maps from the calibration region (Uecker et al. 2014; one map set).  y [n_coils][B][H][W] c64 and
+ * the calibration box (ah, aw) as above; ksize the side k of the k-space kernels, M = n_coils k^2.
+ *   gram     Gm_b[i][j] = sum over the (2ah+2-k)(2aw+2-k) patch positions p of conj(a_p[i]) a_p[j], a_p[(c, ty, tx)] =
+ *            y_c(H/2-ah+py+ty, W/2-aw+px+tx), columns in the order (coil, ty, tx): [B][M][M] complex double (re, im),
+ *            products and sums in double, exactly Hermitian with a real diagonal
+ *   kernels  gram, then Gm = V diag(lam) V^H by cyclic two-sided Hermitian Jacobi in double (round-robin ordering; stops
+ *            when a sweep met off(G) <= 1e-12 ||G||_F, at most 60 sweeps), lam [B][M] descending, rank[b] =
+ *            #{sqrt(max(lam_i, 0)) > sv_thresh sqrt(max(lam_0, 0))}, decided on the device, and the kernel correlation
+ *            K [B][n][n][2k-1][2k-1] c64, K[c][c'][dy][dx] = sum over t - t' = (dy-(k-1), dx-(k-1)) of P[(c,t)][(c',t')],
+ *            P the projector onto the first rank[b] eigenvectors (summed in double, rounded once).  status [B] int32: 0, or 1
+ *            where the sweeps did not converge or a value is not finite; that image's lam, rank, K and maps are zeros.
+ *            sweeps [B] int32 (or NULL): the sweeps made.  work: ipdm_espirit_workspace_bytes(B, n_coils, ksize) bytes.
+ *   pixel    G(x)[c][c'] = (1/k^2) sum_d K[c][c'][d] exp(-2 pi i (dy (xr - H/2) / H + dx (xc - W/2) / W)), a direct DFT of
+ *            the taps (every H, W up to 1024, also sizes without an FFT kernel); u = normalise(G(x) 1), power_iters further
+ *            applications u <- normalise(G(x) u) (normalise divides by the 2-norm, by 1 where it is 0); eigval [B][H][W]
+ *            (or NULL) = Re(u^H G(x) u); maps [n_coils][B][H][W] c64 = conj(u) turned so that coil 0 is real and
+ *            non-negative where eigval > crop, exactly 0 elsewhere.  fp32.  status [B] (or NULL: every image is computed).
+ *   espirit  kernels, then pixel.
+ * n_coils 1..16, ksize 3..8, M <= 432, H, W <= 1024, B <= 65535, otherwise IPDM_EUNSUPPORTED (ipdm_espirit_supported tells,
+ * without a GPU).  IPDM_EINVAL: a box outside the image or with a side below ksize, sv_thresh outside [0, 1) or NaN, crop
+ * NaN, power_iters < 0, a NULL tensor.  Asynchronous, allocation-free, hipGraph-capturable, no atomics and no host
+ * synchronisation: an image's results do not depend on its batch.  y, K, maps on any 8-byte boundary, the others on their
+ * element's. */
+int ipdm_espirit_supported(int n_coils, int ksize, int H, int W);    /* 1 / 0, no GPU needed */
+size_t ipdm_espirit_workspace_bytes(int B, int n_coils, int ksize);  /* Gm and V; 0 when unserved */
+int ipdm_espirit_gram_c64(const float* y, int ah, int aw, int ksize, double* gram, int B, int n_coils, int H, int W, void* stream);
+int ipdm_espirit_kernels_c64(const float* y, int ah, int aw, int ksize, double sv_thresh, float* K, double* lam, int32_t* rank,
+                             int32_t* status, int32_t* sweeps, double* work, int B, int n_coils, int H, int W, void* stream);
+int ipdm_espirit_pixel_c64(const float* K, const int32_t* status, int ksize, float crop, int power_iters, float* maps,
+                           float* eigval, int B, int n_coils, int H, int W, void* stream);
+int ipdm_espirit_c64(const float* y, int ah, int aw, int ksize, double sv_thresh, float crop, int power_iters, float* maps,
+                     float* eigval, float* K, double* lam, int32_t* rank, int32_t* status, double* work, int B, int n_coils,
+                     int H, int W, void* stream);
+
 /* Mask-weighted time average of 2D+time multi-coil k-space: the composite a cine acquisition is calibrated from (its
  * interleaved per-frame patterns together sample the centre fully; maps and compression matrix come from the composite
  * and are shared by the frames).  y [n_coils][B][T][H][W] c64 (the cine measurement (n, B, T, 1, H, W)); mask / mask_t as

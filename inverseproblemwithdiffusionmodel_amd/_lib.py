@@ -11,7 +11,7 @@ import torch  # noqa: F401  -- MUST precede the dlopen below: libipdm.so then bi
 #                              PyTorch-ROCm already loaded (its bundled libamdhip64), so both share one
 #                              runtime, device context and stream table.  Loading /opt/rocm's copy first
 #                              leaves torch and the kernels on two different runtimes ("no device", error 100).
-from ctypes import c_char_p, c_float, c_int, c_int64, c_uint64, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_uint64, c_void_p
 
 
 class ConvExt(ctypes.Structure):
@@ -79,6 +79,12 @@ SIGNATURES = {
     "ipdm_coilcomp_matrix_c64": [P, P, c_int, P, P, P, c_int, c_int, P],
     "ipdm_coil_apply_c64": [P, P, c_int, P, c_int, c_int, c_int, c_int64, P],
     "ipdm_coil_compress_c64": [P, c_int, c_int, c_int, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P],
+    "ipdm_espirit_supported": [c_int, c_int, c_int, c_int],
+    "ipdm_espirit_workspace_bytes": [c_int, c_int, c_int],
+    "ipdm_espirit_gram_c64": [P, c_int, c_int, c_int, P, c_int, c_int, c_int, c_int, P],
+    "ipdm_espirit_kernels_c64": [P, c_int, c_int, c_int, c_double, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P],
+    "ipdm_espirit_pixel_c64": [P, P, c_int, c_float, c_int, P, P, c_int, c_int, c_int, c_int, P],
+    "ipdm_espirit_c64": [P, c_int, c_int, c_int, c_double, c_float, c_int, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P],
     "ipdm_kspace_tavg_c64": [P, P, c_int, P, P, c_int, c_int, c_int, c_int, c_int, P],
     "ipdm_singlecoil_prox_f32": [P, P, P, P, c_int, c_float, c_int, P, P, P, c_int, c_int, c_int, P],
     "ipdm_ald_singlecoil_step_f32": [P, P, P, P, P, P, c_float, c_float, c_uint64, c_int64, c_int64, P,
@@ -183,7 +189,7 @@ _RESTYPES = {"ipdm_build_arch": c_char_p, "ipdm_debug_lds_optin_count": c_int64,
              "ipdm_conv_wino_bx3_weight_bytes": c_int64, "ipdm_conv_hx2_weight_bytes": c_int64,
              "ipdm_conv_wino_hx2_weight_bytes": c_int64, "ipdm_conv_wino1d_weight_bytes": c_int64, "ipdm_conv_wino1d_weight_bytes3d": c_int64,
              "ipdm_conv1d_hx2_weight_bytes": c_int64, "ipdm_csm_workspace_bytes": ctypes.c_size_t,
-             "ipdm_coilcomp_workspace_bytes": ctypes.c_size_t}
+             "ipdm_coilcomp_workspace_bytes": ctypes.c_size_t, "ipdm_espirit_workspace_bytes": ctypes.c_size_t}
 
 IPDM_EINVAL = -1
 IPDM_EUNSUPPORTED = -2

@@ -57,13 +57,17 @@ def build_scorenet(cfg, seed=0):
 
 def build_problem(device, n_samples, R=40, H=128, W=128, num_sens=4, seed=0, scorenet=None, cfg=None, lr_scaled=1.0,
                   sens_maps=None, proximal="L2Penalty", proximal_kwargs=None, mask=None, estimate_maps=False, measurement=None,
-                  calib_max=12, kspace_scale=None, coil_compress=None, noise_cov=None, n_slices=None):
+                  calib_max=12, kspace_scale=None, coil_compress=None, noise_cov=None, n_slices=None, maps_method="walsh",
+                  maps_kwargs=None):
     """-> Namespace(sampler, scorenet, sigmas, op, image, measurement, call_kwargs); sens_maps: measured coil maps
     (num_sens, H, W), real or complex, instead of the synthetic "exp" maps (RSS-normalised where non-zero); proximal: a
     get_proximal name ("L2PenaltyCG": the exact proximal, proximal_kwargs = dict(max_iter=, tol=)); mask: the sampling mask
     of an acquisition, a line or 2-D mask (SENSE mask_mode="custom"), instead of the generated line mask at R.
     estimate_maps: the sampler runs on coil maps estimated from the measurement's calibration region
     (SENSE.estimate_sens_maps, calib_max); without `measurement` the measurement is still simulated with the true maps.
+    maps_method: "walsh" (default) or "espirit", maps_kwargs the estimator's keywords (espirit: ksize, sv_thresh, crop,
+    power_iters); ESPIRiT serves up to 16 coils with n ksize^2 <= 432 (more coils: coil_compress=), and the Namespace then
+    carries the eigenvalue map as espirit_eigval ((H, W), or (S, H, W) for a stack, float32 on the host; None for Walsh).
     measurement: measured k-space (n, H, W) instead of the simulated one: no phantom (image is None), maps from
     sens_maps or estimated, the data multiplied by kspace_scale -- None: 1 / rss_max of its calibration image, since the
     score prior expects magnitudes in [0, 1].  The Namespace then carries kspace_scale; estimated_maps is True when the
@@ -85,6 +89,9 @@ def build_problem(device, n_samples, R=40, H=128, W=128, num_sens=4, seed=0, sco
     prox_cls = get_proximal(proximal)                        # an unknown name fails here, before any GPU work
     kspace_scale = None if kspace_scale is None else float(kspace_scale)
     region = None
+    maps_kwargs = dict(maps_kwargs or {})
+    if maps_method != "walsh" and not estimate_maps:
+        raise ValueError(f"build_problem: maps_method={maps_method!r} goes with estimate_maps=True")
     if noise_cov is not None and coil_compress is None:
         raise ValueError("build_problem: noise_cov= goes with coil_compress= (whitening is part of the compression)")
     if n_slices is not None:
@@ -95,7 +102,7 @@ def build_problem(device, n_samples, R=40, H=128, W=128, num_sens=4, seed=0, sco
     if n_slices is not None or (measurement is not None and torch.as_tensor(measurement).dim() == 4):
         return _build_stack(device, n_samples, R, H, W, num_sens, seed, scorenet, cfg, lr_scaled, sens_maps, prox_cls,
                             proximal_kwargs, mask, estimate_maps, measurement, calib_max, kspace_scale, coil_compress, noise_cov,
-                            None if n_slices is None else int(n_slices))
+                            None if n_slices is None else int(n_slices), maps_method, maps_kwargs)
     if measurement is not None:                              # host-side checks: all fail before any GPU work
         if mask is None:
             raise ValueError("build_problem(measurement=...): pass mask=, the sampling mask of the acquisition")
@@ -112,7 +119,9 @@ def build_problem(device, n_samples, R=40, H=128, W=128, num_sens=4, seed=0, sco
         coil_compress = ops_mod._coilcomp_counts(num_sens, coil_compress, "build_problem(coil_compress=...)")
         if noise_cov is not None:
             noise_cov = ops_mod.check_noise_cov(noise_cov, num_sens, "build_problem: noise_cov")
-    coil_matrix = None
+    n_est = num_sens if coil_compress is None else coil_compress
+    _check_maps(maps_method, maps_kwargs, n_est, H, W, region)
+    coil_matrix = eigval = None
     cfg = acdc_config(device, H) if cfg is None else cfg
     scorenet = build_scorenet(cfg, seed) if scorenet is None else scorenet
     sigmas = get_sigmas(cfg, "recons")
@@ -135,6 +144,9 @@ def build_problem(device, n_samples, R=40, H=128, W=128, num_sens=4, seed=0, sco
                 if not peak > 0.0:
                     raise ValueError("build_problem: the measurement's calibration region holds no signal")
                 kspace_scale = 1.0 / peak
+        if estimate_maps and maps_method == "espirit":
+            maps, eigval = SENSE._espirit_maps(y, *region, "build_problem", **maps_kwargs)
+            eigval = eigval[0]
         if estimate_maps:
             op = SENSE("custom", num_sens, R, 0.04, (1, H, W), seed=seed, mask_T=1, sens_maps=maps.cpu(), normalize=False, **mk)
         else:
@@ -148,6 +160,7 @@ def build_problem(device, n_samples, R=40, H=128, W=128, num_sens=4, seed=0, sco
             op = SENSE("custom", num_sens, R, 0.04, (1, H, W), seed=seed, mask_T=1, sens_maps=sens_maps, **mk)
         if estimate_maps or coil_compress is not None:       # host only: an unusable centre fails before the forward model runs
             region = calibration_region(op.random_under_fourier.mask, H, W, calib_max)
+            _check_maps(maps_method, maps_kwargs, n_est, H, W, region)
         img = phantom_image(H, W, seed=seed).to(device)
         meas1 = op(img)
         if coil_compress is not None:                        # simulated with the physical coils, compressed like a measured scan
@@ -158,13 +171,31 @@ def build_problem(device, n_samples, R=40, H=128, W=128, num_sens=4, seed=0, sco
                            mask=op.random_under_fourier.mask,
                            sens_maps=_compress_maps(op.sens_maps, coil_matrix, num_sens, H, W, device))
         if estimate_maps:                                    # simulated with the true maps, reconstructed with the estimated ones
-            op = SENSE.from_measurement(meas1, op.random_under_fourier.mask, R=R, seed=seed, calib_max=calib_max)
+            op, eigval = _maps_from_simulated(meas1, op.random_under_fourier.mask, R, seed, calib_max, maps_method, maps_kwargs)
     return _assemble(device, n_samples, 1, H, W, scorenet, cfg, sigmas, op, img, meas1, prox_cls, proximal_kwargs, lr_scaled,
-                     estimate_maps, kspace_scale, coil_matrix)
+                     estimate_maps, kspace_scale, coil_matrix, eigval)
+
+
+def _check_maps(maps_method, maps_kwargs, n_coils, H, W, region):
+    """host-side check of the estimator choice; while the region is unknown (a mask still to be simulated) the box test
+    waits for it: 9 x 9 passes every ksize"""
+    if maps_method != "walsh":
+        ah, aw = region if region is not None else (4, 4)
+        SENSE._check_maps_method(maps_method, n_coils, H, W, ah, aw, dict(maps_kwargs), "build_problem")
+
+
+def _maps_from_simulated(meas, mask, R, seed, calib_max, maps_method, maps_kwargs):
+    """the operator with maps estimated from a simulated measurement ((n, 1, 1, H, W), or a stack (S, n, H, W)) -> (op,
+    ESPIRiT eigenvalue map on the host or None)"""
+    if maps_method == "walsh":
+        return SENSE.from_measurement(meas, mask, R=R, seed=seed, calib_max=calib_max), None
+    maps, eigval = SENSE.estimate_sens_maps(meas, mask, calib_max=calib_max, method=maps_method, return_eig=True, **maps_kwargs)
+    n, H, W = maps.shape[-3:]
+    return SENSE("custom", n, R, 0.04, (1, H, W), seed, mask_mode="custom", mask=mask, sens_maps=maps, normalize=False), eigval
 
 
 def _assemble(device, n_samples, S, H, W, scorenet, cfg, sigmas, op, img, meas1, prox_cls, proximal_kwargs, lr_scaled,
-              estimate_maps, kspace_scale, coil_matrix):
+              estimate_maps, kspace_scale, coil_matrix, eigval=None):
     """the sampler on n_samples copies of meas1 (n, S, 1, H, W): repeat along the batch axis gives row sample * S + slice"""
     meas = meas1.repeat(1, n_samples, 1, 1, 1).contiguous()
     params = dict(n_steps_each=cfg.sampling.n_steps_each, step_lr=cfg.sampling.step_lr, denoise=True,
@@ -175,11 +206,13 @@ def _assemble(device, n_samples, S, H, W, scorenet, cfg, sigmas, op, img, meas1,
                      params=params, call_kwargs=dict(label=None, lamda=0.1, save_dir=None, lr_scaled=lr_scaled,
                                                      seg_mode="full"),
                      estimated_maps=bool(estimate_maps), kspace_scale=kspace_scale,
-                     coil_matrix=None if coil_matrix is None else coil_matrix.cpu(), n_slices=S)
+                     coil_matrix=None if coil_matrix is None else coil_matrix.cpu(), n_slices=S,
+                     espirit_eigval=None if eigval is None else eigval.cpu())
 
 
 def _build_stack(device, n_samples, R, H, W, num_sens, seed, scorenet, cfg, lr_scaled, sens_maps, prox_cls, proximal_kwargs,
-                 mask, estimate_maps, measurement, calib_max, kspace_scale, coil_compress, noise_cov, n_slices):
+                 mask, estimate_maps, measurement, calib_max, kspace_scale, coil_compress, noise_cov, n_slices,
+                 maps_method="walsh", maps_kwargs=None):
     """build_problem for a stack of slices (its docstring): measurement (S, n, H, W), or n_slices simulated ones.  Every
     shape, mask and calibration-region check runs on the host before the score network is built or the GPU is touched."""
     region = None
@@ -221,7 +254,9 @@ def _build_stack(device, n_samples, R, H, W, num_sens, seed, scorenet, cfg, lr_s
             op = SENSE("custom", num_sens, R, 0.04, (1, H, W), seed=seed, mask_T=1, sens_maps=sens_maps, **mk)
         if estimate_maps or coil_compress is not None:
             region = calibration_region(op.random_under_fourier.mask, H, W, calib_max)
-    coil_matrix = None
+    maps_kwargs = dict(maps_kwargs or {})
+    _check_maps(maps_method, maps_kwargs, num_sens if coil_compress is None else coil_compress, H, W, region)
+    coil_matrix = eigval = None
     cfg = acdc_config(device, H) if cfg is None else cfg
     scorenet = build_scorenet(cfg, seed) if scorenet is None else scorenet
     sigmas = get_sigmas(cfg, "recons")
@@ -240,6 +275,8 @@ def _build_stack(device, n_samples, R, H, W, num_sens, seed, scorenet, cfg, lr_s
                 if not peak > 0.0:
                     raise ValueError("build_problem: the measurement's calibration region holds no signal")
                 kspace_scale = 1.0 / peak
+        if estimate_maps and maps_method == "espirit":
+            maps, eigval = SENSE._espirit_maps(y, *region, "build_problem", **maps_kwargs)
         if estimate_maps:
             op = SENSE("custom", n_out, R, 0.04, (1, H, W), seed=seed, mask_T=1, sens_maps=maps.transpose(0, 1).cpu(),
                        normalize=False, **mk)
@@ -257,9 +294,10 @@ def _build_stack(device, n_samples, R, H, W, num_sens, seed, scorenet, cfg, lr_s
                 op = SENSE("custom", n_out, R, 0.04, (1, H, W), seed=seed, mask_T=1, normalize=False, mask_mode="custom",
                            mask=sim_mask, sens_maps=_compress_map_sets(op.sens_maps, coil_matrix, device))
         if estimate_maps:
-            op = SENSE.from_measurement(meas1[:, :, 0].transpose(0, 1), sim_mask, R=R, seed=seed, calib_max=calib_max)
+            op, eigval = _maps_from_simulated(meas1[:, :, 0].transpose(0, 1), sim_mask, R, seed, calib_max, maps_method,
+                                              maps_kwargs)
     return _assemble(device, n_samples, S, H, W, scorenet, cfg, sigmas, op, img, meas1, prox_cls, proximal_kwargs, lr_scaled,
-                     estimate_maps, kspace_scale, coil_matrix)
+                     estimate_maps, kspace_scale, coil_matrix, eigval)
 
 
 def _compress_map_sets(maps, A, device):

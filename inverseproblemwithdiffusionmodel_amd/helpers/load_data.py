@@ -332,6 +332,44 @@ def driver_sens_maps(path, sens_phase, num_sens, H, W, seed):
     return None, num_sens
 
 
+def add_maps_method_args(parser):
+    """the drivers' choice of the coil-map estimator behind --estimate_maps"""
+    parser.add_argument("--maps_method", choices=["walsh", "espirit"], default="walsh",
+                        help="--estimate_maps: Walsh's adaptive estimator (default) or ESPIRiT (up to 16 coils and "
+                             "n_coils * K^2 <= 432; more coils go through --coil_compress first)")
+    parser.add_argument("--espirit_kernel", type=int, default=6, metavar="K", help="--maps_method espirit: kernel side, 3..8")
+    parser.add_argument("--espirit_thresh", type=float, default=0.02, metavar="T",
+                        help="--maps_method espirit: singular values of the calibration matrix above T * the largest span "
+                             "the row space (noisy data may want another value)")
+    parser.add_argument("--espirit_crop", type=float, default=0.8, metavar="C",
+                        help="--maps_method espirit: the maps are zero where the eigenvalue of G(x) is at most C")
+
+
+def driver_maps_method(a, estimate_maps, n_coils, H, W, region):
+    """host-side check of add_maps_method_args' flags, before a score network is built or a GPU touched; every failure is a
+    ``sys.exit``.  a: the parsed flags (Namespace or dict); n_coils: the coils the estimator sees (the virtual ones with
+    --coil_compress); region: the calibration half-widths.  -> (method, kwargs for the estimator)"""
+    import math
+    import sys
+    from .. import ops
+    get = a.get if isinstance(a, dict) else lambda k: getattr(a, k)
+    method = get("maps_method")
+    if method == "walsh":
+        return "walsh", {}
+    if not estimate_maps:
+        sys.exit("--maps_method espirit goes with --estimate_maps")
+    k, t, c = get("espirit_kernel"), get("espirit_thresh"), get("espirit_crop")
+    if not (math.isfinite(t) and 0.0 <= t < 1.0):
+        sys.exit(f"--espirit_thresh {t}: a fraction of the largest singular value, 0 <= T < 1")
+    if not (math.isfinite(c) and 0.0 <= c < 1.0):
+        sys.exit(f"--espirit_crop {c}: an eigenvalue threshold, 0 <= C < 1")
+    try:
+        ops.espirit_check(n_coils, k, region[0], region[1], H, W, "--maps_method espirit")
+    except (ValueError, NotImplementedError) as e:
+        sys.exit(str(e))
+    return "espirit", dict(ksize=k, sv_thresh=t, crop=c)
+
+
 def add_cine_measurement_args(parser):
     """the cine drivers' measured-data flags, with the meanings scripts/acdc_SENSE_real_img.py gives them"""
     parser.add_argument("--kspace", default=None,
@@ -347,11 +385,12 @@ def add_cine_measurement_args(parser):
                         help="--coil_compress: .npy / .pt file with the (n_coils, n_coils) coil noise covariance of the prescan")
     parser.add_argument("--kspace_scale", default="auto",
                         help="--kspace: factor on the measurement; auto: 1 / the peak of its composite calibration image")
+    add_maps_method_args(parser)
 
 
 def cine_measurement_requested(a):
     """whether any of add_cine_measurement_args' flags asks for the calibrated path (a: the parsed Namespace)"""
-    return bool(a.kspace or a.estimate_maps or a.coil_compress is not None or a.noise_cov)
+    return bool(a.kspace or a.estimate_maps or a.coil_compress is not None or a.noise_cov or a.maps_method != "walsh")
 
 
 def driver_cine_checks(a, H, W, T, num_sens, mask):
@@ -394,11 +433,14 @@ def driver_cine_checks(a, H, W, T, num_sens, mask):
     try:
         if kspace is not None:
             uf.SENSE._cine_operands(kspace, mask, "--kspace / --mask")
-        uf.calibration_region(mask, H, W, a.calib_max, composite=True)
+        region = uf.calibration_region(mask, H, W, a.calib_max, composite=True)
     except (ValueError, TypeError) as e:
         sys.exit(f"--estimate_maps / --coil_compress / --kspace: {e}")
+    maps_method, maps_kwargs = driver_maps_method(a, a.estimate_maps, num_sens if a.coil_compress is None else a.coil_compress,
+                                                  H, W, region)
     return Namespace(kspace=kspace, H=H, W=W, T=T, num_sens=num_sens, noise_cov=noise_cov,
-                     kspace_scale=None if a.kspace_scale == "auto" else float(a.kspace_scale))
+                     kspace_scale=None if a.kspace_scale == "auto" else float(a.kspace_scale), maps_method=maps_method,
+                     maps_kwargs=maps_kwargs)
 
 
 def driver_cine_measurement(a, checked, op, frames, device):
@@ -414,7 +456,7 @@ def driver_cine_measurement(a, checked, op, frames, device):
         y = op(frames).reshape(op.num_sens, checked.T, checked.H, checked.W)
         mask = op.random_under_fourier.mask
     cal = SENSE.from_cine_measurement(y, mask, R=a.R, seed=a.seed, calib_max=a.calib_max, n_virtual=a.coil_compress,
-                                      noise_cov=checked.noise_cov)
+                                      noise_cov=checked.noise_cov, method=checked.maps_method, **checked.maps_kwargs)
     cal.kspace_scale = None
     if checked.kspace is not None:
         cal.kspace_scale = checked.kspace_scale

@@ -248,22 +248,57 @@ class SENSE(LinearTransform):
         return maps / torch.where(rss > 0, rss, torch.ones_like(rss))
 
     @staticmethod
-    def estimate_sens_maps(y, mask, calib_max=12, **kw):
+    def estimate_sens_maps(y, mask, calib_max=12, method="walsh", **kw):
         """coil maps from the measurement itself: y (n, H, W) multi-coil k-space (tensor or ndarray; singleton batch /
         channel dims as in a saved (n, 1, 1, H, W) measurement are dropped), centred with orthonormal scale as this
         operator produces it, mask its sampling mask.  The calibration box is ``calibration_region(mask, H, W, calib_max)``,
-        the estimator ``ops.estimate_sens_maps`` on the current GPU (kw: radius, power_iters, thresh).
+        the estimator ``ops.estimate_sens_maps`` on the current GPU (method="walsh"; kw: radius, power_iters, thresh) or
+        ``ops.espirit_maps`` (method="espirit"; kw: ksize, sv_thresh, crop, power_iters; up to 16 coils and
+        n ksize^2 <= 432 -- compress more coils first; return_eig=True: -> (maps, eigval (H, W) float32 on the host)).
         -> host complex128 (n, H, W), unit RSS inside the support and zero outside: ready for ``sens_maps=``.
         y (S, n, H, W), a stack of slices: one batched estimator call, each slice from its own calibration data
         -> (S, n, H, W)."""
         y, stack = SENSE._measurement_operand(y, "estimate_sens_maps")
-        H, W = y.shape[-2:]
+        n, H, W = y.shape[-3:]
         ah, aw = calibration_region(mask, H, W, calib_max)                  # host only: fails before any GPU work
+        return_eig = SENSE._check_maps_method(method, n, H, W, ah, aw, kw, "estimate_sens_maps")
         yd = y.to(torch.complex64).to(y.device if y.is_cuda else "cuda")
-        if stack:
-            maps = ops.estimate_sens_maps(yd.transpose(0, 1).contiguous(), ah, aw, **kw)        # (n, S, H, W), one per image
-            return maps.transpose(0, 1).cpu().to(torch.complex128).contiguous()
-        return ops.estimate_sens_maps(yd.contiguous(), ah, aw, **kw).cpu().to(torch.complex128)
+        yd = yd.transpose(0, 1).contiguous() if stack else yd.contiguous()  # (n, S, H, W), one per image
+        if method == "espirit":
+            maps, eigval = SENSE._espirit_maps(yd, ah, aw, "estimate_sens_maps", **kw)
+        else:
+            maps = ops.estimate_sens_maps(yd, ah, aw, **kw)
+        maps = maps.transpose(0, 1).cpu().to(torch.complex128).contiguous() if stack else maps.cpu().to(torch.complex128)
+        if return_eig:
+            return maps, (eigval if stack else eigval[0]).cpu()
+        return maps
+
+    ESPIRIT_KW = ("ksize", "sv_thresh", "crop", "power_iters")
+
+    @staticmethod
+    def _check_maps_method(method, n, H, W, ah, aw, kw, what):
+        """host-side check of the estimator choice, before any GPU work; pops and returns kw's return_eig (espirit only)"""
+        if method == "walsh":
+            return False
+        if method != "espirit":
+            raise ValueError(f"{what}: method {method!r}; 'walsh' or 'espirit'")
+        return_eig = bool(kw.pop("return_eig", False))
+        unknown = sorted(set(kw) - set(SENSE.ESPIRIT_KW))
+        if unknown:
+            raise TypeError(f"{what}: method='espirit' takes {', '.join(SENSE.ESPIRIT_KW)}; got {', '.join(unknown)}")
+        ops.espirit_check(n, kw.get("ksize", 6), ah, aw, H, W, what)
+        return return_eig
+
+    @staticmethod
+    def _espirit_maps(yd, ah, aw, what, **kw):
+        """ops.espirit_maps of yd (n, H, W) / (n, B, H, W) on the GPU -> (maps, eigval (B, H, W)); RuntimeError naming the
+        images whose decomposition failed"""
+        maps, eigval, _, status = ops.espirit_maps(yd, ah, aw, return_eig=True, **kw)
+        bad = torch.nonzero(status.cpu()).flatten().tolist()
+        if bad:
+            raise RuntimeError(f"{what}: the ESPIRiT eigendecomposition did not converge, or met a non-finite value, for "
+                               f"image(s) {bad} of the batch")
+        return maps, eigval
 
     @staticmethod
     def _measurement_operand(y, what):
@@ -302,17 +337,23 @@ class SENSE(LinearTransform):
         return out, A[0].cpu()
 
     @classmethod
-    def from_measurement(cls, y, mask, R=1, seed=None, calib_max=12, n_virtual=None, noise_cov=None, **kw):
+    def from_measurement(cls, y, mask, R=1, seed=None, calib_max=12, n_virtual=None, noise_cov=None, method="walsh", **kw):
         """the ``"custom"`` operator of an acquisition: maps estimated from its own measurement y (n, H, W) and sampling
-        mask (estimate_sens_maps; kw goes to the estimator).  R is informational, as for every custom mask.  n_virtual:
+        mask (estimate_sens_maps; method and kw go to the estimator).  R is informational, as for every custom mask.  n_virtual:
         the measurement is whitened (noise_cov) and compressed first (compress_measurement) and the maps are those of the
         virtual coils -- the operator then has n_virtual coils and serves the compressed measurement.  y (S, n, H, W), a
         stack of slices: the multi-set operator, maps (and compression) per slice (n_map_sets == S)."""
+        if method != "walsh":                                               # host only: fails before the compression runs
+            y0, _ = cls._measurement_operand(y, "from_measurement")
+            n0, H0, W0 = y0.shape[-3:]
+            cls._check_maps_method(method, n0 if n_virtual is None else int(n_virtual), H0, W0,
+                                   *calibration_region(mask, H0, W0, calib_max), dict(kw), "from_measurement")
         if n_virtual is not None:
             y, _ = cls.compress_measurement(y, mask, n_virtual, noise_cov=noise_cov, calib_max=calib_max)
         elif noise_cov is not None:
             raise ValueError("from_measurement: noise_cov= goes with n_virtual= (whitening is part of the compression)")
-        maps = cls.estimate_sens_maps(y, mask, calib_max=calib_max, **kw)
+        kw.pop("return_eig", None)
+        maps = cls.estimate_sens_maps(y, mask, calib_max=calib_max, method=method, **kw)
         n, H, W = maps.shape[-3:]
         return cls("custom", n, R, 0.04, (1, H, W), seed, mask_mode="custom", mask=mask, sens_maps=maps, normalize=False)
 
@@ -354,13 +395,15 @@ class SENSE(LinearTransform):
         return ops.kspace_time_average(yd, ops._mask_u8(mask, y.shape[-2], y.shape[-1], yd.device))
 
     @classmethod
-    def from_cine_measurement(cls, y, mask, R=1, seed=None, calib_max=12, n_virtual=None, noise_cov=None, **kw):
+    def from_cine_measurement(cls, y, mask, R=1, seed=None, calib_max=12, n_virtual=None, noise_cov=None, method="walsh",
+                              **kw):
         """the ``"custom"`` operator of a 2D+time acquisition, calibrated from its time-averaged composite: y (n, T, H, W)
         multi-coil k-space and its per-frame sampling mask, as for ``time_average``.  The calibration box is
         ``calibration_region(mask, H, W, calib_max, composite=True)``; with n_virtual ONE compression matrix
         (``ops.coilcomp_matrix`` of the composite's Gram matrix, whitened with noise_cov) is applied to every frame and to
-        the composite; the maps are those of the (virtual) coils of the composite (``ops.estimate_sens_maps``; kw goes to
-        the estimator) and serve every frame.  -> Namespace(op, measurement (n', T, H, W) complex64 on the GPU, sens_maps
+        the composite; the maps are those of the (virtual) coils of the composite (``ops.estimate_sens_maps``, or
+        ``ops.espirit_maps`` with method="espirit"; kw goes to the estimator; eigval: the ESPIRiT eigenvalue map (H, W) on
+        the host, None for Walsh) and serve every frame.  -> Namespace(op, measurement (n', T, H, W) complex64 on the GPU, sens_maps
         (n', H, W) complex128 on the host, coil_matrix (n', n) complex64 on the host or None, region (ah, aw), rss_max (the
         peak of the composite's calibration image), composite (n', H, W) complex64 on the GPU).  Every argument is
         checked on the host before any GPU work."""
@@ -374,18 +417,25 @@ class SENSE(LinearTransform):
         elif noise_cov is not None:
             raise ValueError("from_cine_measurement: noise_cov= goes with n_virtual= (whitening is part of the compression)")
         ah, aw = calibration_region(mask, H, W, calib_max, composite=True)
+        cls._check_maps_method(method, n if n_virtual is None else n_virtual, H, W, ah, aw, kw, "from_cine_measurement")
         yd = y.to(torch.complex64).to(y.device if y.is_cuda else "cuda").contiguous()
         ybar = ops.kspace_time_average(yd, ops._mask_u8(mask, H, W, yd.device))
         A = None
         if n_virtual is not None:
             A = ops.coilcomp_matrix(ops.coil_gram(ybar, ah, aw), n_virtual, noise_cov)[0]
             yd, ybar = ops.coil_apply(yd, A), ops.coil_apply(ybar, A)
-        maps, _, rss_max = ops.estimate_sens_maps(ybar, ah, aw, return_rss=True, **kw)
+        eigval = None
+        if method == "espirit":                                             # rss_max: the peak of the Walsh calibration image
+            _, _, rss_max = ops.estimate_sens_maps(ybar, ah, aw, return_rss=True)
+            maps, eigval = cls._espirit_maps(ybar, ah, aw, "from_cine_measurement", **kw)
+            eigval = eigval[0].cpu()
+        else:
+            maps, _, rss_max = ops.estimate_sens_maps(ybar, ah, aw, return_rss=True, **kw)
         maps = maps.cpu().to(torch.complex128)
         op = cls("custom", maps.shape[0], R, 0.04, (1, H, W), seed, mask_T=planes, mask_mode="custom", mask=mask, sens_maps=maps,
                  normalize=False)
         return Namespace(op=op, measurement=yd, sens_maps=op.sens_maps, coil_matrix=None if A is None else A.cpu(),
-                         region=(ah, aw), rss_max=float(rss_max[0]), composite=ybar)
+                         region=(ah, aw), rss_max=float(rss_max[0]), composite=ybar, eigval=eigval)
 
     @staticmethod
     def _as_host_maps(maps):

@@ -663,6 +663,122 @@ def coil_compress(y, ah, aw, n_virtual, noise_cov=None, return_matrix=False, *, 
     return (out, A, eig, status) if return_matrix else out
 
 
+# ---- ESPIRiT coil sensitivity maps from the calibration region (csrc/espirit.hip) ------------------------------------------
+ESPIRIT_MAX_COILS, ESPIRIT_MAX_COLUMNS = 16, 432
+
+
+def espirit_supported(n_coils, ksize, H, W):
+    """whether espirit_maps has kernels for this coil count (1..16), kernel side (3..8, n_coils ksize^2 <= 432) and image
+    size (every H, W up to 1024).  Needs no GPU."""
+    return bool(_lib.lib.ipdm_espirit_supported(int(n_coils), int(ksize), int(H), int(W)))
+
+
+def espirit_workspace(B, n_coils, ksize, device):
+    """scratch tensor of espirit_kernels / espirit_maps (Gram matrix and eigenvectors, double); None without a kernel"""
+    nbytes = _lib.lib.ipdm_espirit_workspace_bytes(int(B), int(n_coils), int(ksize))
+    return torch.empty(nbytes // 8, dtype=torch.float64, device=device) if nbytes else None
+
+
+def espirit_check(n_coils, ksize, ah, aw, H, W, what="espirit"):
+    """host-side check of an ESPIRiT request, before any launch: ValueError for a calibration box with a side below ksize,
+    IpdmUnsupported (naming n_virtual as the way out) for more coils or kernel columns than the kernels serve"""
+    if isinstance(ksize, bool) or int(ksize) != ksize:
+        raise ValueError(f"ipdm {what}: ksize must be an integer, got {ksize!r}")
+    ksize = int(ksize)
+    if ksize < 3 or ksize > 8:
+        raise _lib.IpdmUnsupported(f"ipdm {what}: ksize = {ksize}; the kernels serve 3..8")
+    if n_coils > ESPIRIT_MAX_COILS or n_coils * ksize * ksize > ESPIRIT_MAX_COLUMNS:
+        raise _lib.IpdmUnsupported(f"ipdm {what}: {n_coils} coils with ksize = {ksize} make {n_coils * ksize * ksize} kernel "
+                                   f"columns; the kernels serve up to {ESPIRIT_MAX_COILS} coils and n_coils ksize^2 <= "
+                                   f"{ESPIRIT_MAX_COLUMNS}: compress the measurement first (n_virtual= / coil_compress=)")
+    if 2 * ah + 1 < ksize or 2 * aw + 1 < ksize:
+        raise ValueError(f"ipdm {what}: the calibration box {2 * ah + 1} x {2 * aw + 1} is smaller than ksize = {ksize}")
+    if not espirit_supported(n_coils, ksize, H, W):
+        raise _lib.IpdmUnsupported(f"ipdm {what}: no kernel for {n_coils} coils, ksize {ksize}, {H} x {W}")
+    return ksize
+
+
+def espirit_gram(y, ah, aw, ksize=6):
+    """Gram matrix of the ESPIRiT calibration matrix of multi-coil k-space y ((n, H, W), (n, B, H, W) or (n, B, 1, H, W)
+    complex64): every ksize x ksize patch of the box, columns in the order (coil, ty, tx) -> (B, M, M) complex128,
+    M = n ksize^2, summed in double, exactly Hermitian"""
+    n, B, H, W = _csm_measurement(y, "espirit_gram")
+    ah, aw = _csm_box(ah, aw)
+    M = n * int(ksize) ** 2
+    out = torch.empty((B, M, M), dtype=torch.complex128, device=y.device)
+    call("ipdm_espirit_gram_c64", _ptr(y), ah, aw, int(ksize), _ptr(out), B, n, H, W, _stream())
+    return out
+
+
+def _espirit_work(work, B, n, ksize, device, what):
+    need = _lib.lib.ipdm_espirit_workspace_bytes(B, n, int(ksize))
+    if work is None:
+        return espirit_workspace(B, n, ksize, device)         # None for a shape without a kernel: the call reports it
+    if (not isinstance(work, torch.Tensor) or not work.is_cuda or work.dtype != torch.float64 or not work.is_contiguous()
+            or work.numel() * 8 < need):
+        raise ValueError(f"{what}: `work` must be a contiguous float64 GPU tensor of >= {need} bytes "
+                         f"(ops.espirit_workspace({B}, {n}, {ksize}, device))")
+    return work
+
+
+def espirit_kernels(y, ah, aw, ksize=6, sv_thresh=0.02, return_sweeps=False, *, work=None):
+    """row space of the calibration matrix and its kernel correlation (ipdm.h, ipdm_espirit_kernels_c64) -> (K (B, n, n,
+    2 ksize - 1, 2 ksize - 1) complex64, lam (B, M) float64 descending, rank (B,) int32, status (B,) int32: 0 = fine);
+    return_sweeps: -> (..., sweeps (B,) int32, the Jacobi sweeps made).  Asynchronous; the rank is decided on the device."""
+    n, B, H, W = _csm_measurement(y, "espirit_kernels")
+    ah, aw = _csm_box(ah, aw)
+    ksize = int(ksize)
+    work = _espirit_work(work, B, n, ksize, y.device, "espirit_kernels")
+    side = 2 * ksize - 1
+    K = torch.empty((B, n, n, side, side), dtype=torch.complex64, device=y.device)
+    lam = torch.empty((B, n * ksize * ksize), dtype=torch.float64, device=y.device)
+    rank = torch.empty(B, dtype=torch.int32, device=y.device)
+    status = torch.empty(B, dtype=torch.int32, device=y.device)
+    sweeps = torch.empty(B, dtype=torch.int32, device=y.device)
+    call("ipdm_espirit_kernels_c64", _ptr(y), ah, aw, ksize, float(sv_thresh), _ptr(K), _ptr(lam), _ptr(rank), _ptr(status),
+         _ptr(sweeps), _ptr(work), B, n, H, W, _stream())
+    return (K, lam, rank, status, sweeps) if return_sweeps else (K, lam, rank, status)
+
+
+def espirit_pixel(K, H, W, crop=0.8, power_iters=30, status=None, shape=None):
+    """the per-pixel stage alone: K (B, n, n, 2k-1, 2k-1) complex64 -> (maps (n, B, H, W) complex64 (or `shape`), eigval
+    (B, H, W) float32)"""
+    _c64_operand(K, "K", "espirit_pixel")
+    if K.dim() != 5 or K.shape[1] != K.shape[2] or K.shape[3] != K.shape[4] or K.shape[3] % 2 == 0:
+        raise ValueError(f"ipdm espirit_pixel: K {tuple(K.shape)}; (B, n, n, 2k-1, 2k-1) expected")
+    B, n, ksize = K.shape[0], K.shape[1], (K.shape[3] + 1) // 2
+    if status is not None:
+        _inplace_operand(status, torch.int32, "status")
+    maps = torch.empty(shape if shape is not None else (n, B, H, W), dtype=torch.complex64, device=K.device)
+    eigval = torch.empty((B, H, W), dtype=torch.float32, device=K.device)
+    call("ipdm_espirit_pixel_c64", _ptr(K), _ptr(status), ksize, float(crop), int(power_iters), _ptr(maps), _ptr(eigval), B, n,
+         int(H), int(W), _stream())
+    return maps, eigval
+
+
+def espirit_maps(y, ah, aw, ksize=6, sv_thresh=0.02, crop=0.8, power_iters=30, return_eig=False, *, work=None):
+    """ESPIRiT coil sensitivity maps from the fully sampled calibration box of multi-coil k-space y ((n, H, W), (n, B, H, W)
+    or (n, B, 1, H, W) complex64; (ah, aw): SENSE's calibration_region), one map set (ipdm.h, ipdm_espirit_c64) -> maps of
+    y's shape: unit norm over the coils and coil 0 real and non-negative where the eigenvalue of G(x) exceeds crop, exactly
+    zero elsewhere.  return_eig: -> (maps, eigval (B, H, W) float32, rank (B,) int32, status (B,) int32; a non-zero status
+    marks an image whose decomposition failed: its maps are zeros).  Every H, W up to 1024 (the pixel stage is a direct DFT
+    of the kernel taps).  Asynchronous; no host synchronisation."""
+    n, B, H, W = _csm_measurement(y, "espirit_maps")
+    ah, aw = _csm_box(ah, aw)
+    ksize = int(ksize)
+    work = _espirit_work(work, B, n, ksize, y.device, "espirit_maps")
+    side = 2 * ksize - 1
+    maps = torch.empty_like(y)
+    eigval = torch.empty((B, H, W), dtype=torch.float32, device=y.device)
+    K = torch.empty((B, n, n, side, side), dtype=torch.complex64, device=y.device)
+    lam = torch.empty((B, n * ksize * ksize), dtype=torch.float64, device=y.device)
+    rank = torch.empty(B, dtype=torch.int32, device=y.device)
+    status = torch.empty(B, dtype=torch.int32, device=y.device)
+    call("ipdm_espirit_c64", _ptr(y), ah, aw, ksize, float(sv_thresh), float(crop), int(power_iters), _ptr(maps), _ptr(eigval),
+         _ptr(K), _ptr(lam), _ptr(rank), _ptr(status), _ptr(work), B, n, H, W, _stream())
+    return (maps, eigval, rank, status) if return_eig else maps
+
+
 # ---- mask-weighted time average of 2D+time k-space (csrc/kspace_tavg.hip) ------------------------------------------------
 TAVG_MAX_FRAMES = 4096
 

@@ -80,6 +80,8 @@ if __name__ == '__main__':
                         help="--coil_compress: .npy / .pt file with the (n_coils, n_coils) coil noise covariance of the prescan")
     parser.add_argument("--kspace_scale", default="auto",
                         help="--kspace: factor on the measurement; auto: 1 / the peak of its calibration image")
+    from inverseproblemwithdiffusionmodel_amd.helpers.load_data import add_maps_method_args, driver_maps_method
+    add_maps_method_args(parser)
     parser.add_argument("--seg_synthetic", action="store_true",
                         help="run the guidance with seeded random UNet weights (exercises the path; not meaningful imaging)")
     args_dict = vars(parser.parse_args())
@@ -131,7 +133,7 @@ if __name__ == '__main__':
     # the mask, and the calibration region the run depends on, before the score network is built or a GPU is touched
     from inverseproblemwithdiffusionmodel_amd.helpers.load_data import driver_mask
     mask = driver_mask(args_dict["mask"], args_dict["mask_2d"], H, W, args_dict["R"], args_dict["seed"])
-    noise_cov = None
+    noise_cov = region = None
     if args_dict["noise_cov"] and args_dict["coil_compress"] is None:
         sys.exit("--noise_cov PATH goes with --coil_compress N (whitening is part of the compression)")
     if args_dict["coil_compress"] is not None:                            # a bad N or a bad covariance fails here
@@ -145,11 +147,14 @@ if __name__ == '__main__':
     if args_dict["estimate_maps"] or args_dict["coil_compress"] is not None or (kspace is not None and kspace_scale is None):
         from inverseproblemwithdiffusionmodel_amd.ncsn.linear_transforms import undersampling_fourier as uf
         try:
-            uf.calibration_region(mask if mask is not None else
+            region = uf.calibration_region(mask if mask is not None else
                                   uf.RandomUndersamplingFourier(args_dict["R"], 0.04, (1, H, W), args_dict["seed"]).mask,
                                   H, W, args_dict["calib_max"])
         except ValueError as e:
             sys.exit(f"--estimate_maps / --coil_compress / --kspace: {e}")
+    maps_method, maps_kwargs = driver_maps_method(
+        args_dict, args_dict["estimate_maps"],
+        args_dict["num_sens"] if args_dict["coil_compress"] is None else args_dict["coil_compress"], H, W, region)
     from inverseproblemwithdiffusionmodel_amd import engine, sharding
     world, rank, device = sharding.init_distributed()
     from inverseproblemwithdiffusionmodel_amd.helpers.load_model import load_scorenet_weights
@@ -176,6 +181,7 @@ if __name__ == '__main__':
                                 calib_max=args_dict["calib_max"], kspace_scale=kspace_scale,
                                 coil_compress=args_dict["coil_compress"], noise_cov=noise_cov,
                                 n_slices=None if kspace is not None else args_dict["n_slices"],
+                                maps_method=maps_method, maps_kwargs=maps_kwargs,
                                 proximal=args_dict["proximal_type"],
                                 proximal_kwargs=(dict(max_iter=args_dict["cg_iters"], tol=args_dict["cg_tol"])
                                                  if args_dict["proximal_type"] == "L2PenaltyCG" else None))
@@ -235,6 +241,8 @@ if __name__ == '__main__':
             torch.save(prob.op.sens_maps, os.path.join(save_dir, "sens_maps.pt"))
         if prob.coil_matrix is not None:
             torch.save(prob.coil_matrix, os.path.join(save_dir, "coil_matrix.pt"))
+        if prob.espirit_eigval is not None:
+            torch.save(prob.espirit_eigval, os.path.join(save_dir, "espirit_eigval.pt"))
         if post is not None:
             torch.save({k: v.cpu() for k, v in post.items()}, os.path.join(save_dir, "posterior.pt"))
         if post_slices is not None:

@@ -139,6 +139,8 @@ if __name__ == '__main__':
             torch.save(cal.measurement.cpu(), os.path.join(a.save_dir, "measurement.pt"))
             if cal.coil_matrix is not None:
                 torch.save(cal.coil_matrix, os.path.join(a.save_dir, "coil_matrix.pt"))
+            if cal.eigval is not None:
+                torch.save(cal.eigval, os.path.join(a.save_dir, "espirit_eigval.pt"))
         if post is not None:
             torch.save({k: v.cpu() for k, v in post.items()}, os.path.join(a.save_dir, "posterior.pt"))
         with open(os.path.join(a.save_dir, "args_dict.pkl"), "wb") as wf:

@@ -129,5 +129,7 @@ if __name__ == '__main__':
         torch.save(op.sens_maps, os.path.join(save_dir, "sens_maps.pt"))
     if cal is not None and cal.coil_matrix is not None:
         torch.save(cal.coil_matrix, os.path.join(save_dir, "coil_matrix.pt"))
+    if cal is not None and cal.eigval is not None:
+        torch.save(cal.eigval, os.path.join(save_dir, "espirit_eigval.pt"))
     with open(os.path.join(save_dir, "args_dict.pkl"), "wb") as wf:
         pickle.dump(args_dict, wf)
