@@ -341,6 +341,38 @@ int ipdm_coil_apply_c64(const float* y, const float* A, int per_image, float* ou
 int ipdm_coil_compress_c64(const float* y, int ah, int aw, int n_virtual, const float* noise_cov, float* A, float* eig,
                            int32_t* status, float* out, float* work, int B, int n_coils, int H, int W, void* stream);
 
+/* Geometric coil compression along the fully sampled readout axis H (Zhang et al. 2013): one matrix per readout position.
+ *   readout_fft  centred orthonormal DFT (inverse != 0: inverse DFT) along H of every column of `planes` [H][W] c64 planes,
+ *                fft2c's centring, so that row x of the inverse transform of k-space is image row x.  H a power of two from
+ *                4 or a multiple of 16 of the form 2^a 3^b 5^c, at most 2048 (else IPDM_EUNSUPPORTED); any W.  out == in is
+ *                allowed, a partial overlap is IPDM_EINVAL.
+ *   gram         h [n_coils][B][H][W] c64 (hybrid space): G_{b,x}[i][j] = sum over the rows [x-win, x+win] clipped to the
+ *                image, ascending, and the columns [W/2-aw, W/2+aw], ascending, of h_i conj(h_j), summed in double and
+ *                rounded once: [B][H][n_coils][n_coils] c64, exactly Hermitian.  win 0..8.
+ *   align        Ahat [B][H][n_virtual][n_coils] c64 (the matrix stage on every G_{b,x}) -> A of the same shape: row H/2
+ *                is copied; outward in both directions A_x = P_x Ahat_x with P_x the unitary polar factor that makes
+ *                P_x (Ahat_x psi A_p^H) Hermitian positive semidefinite (30 Newton-Schulz iterations), p the nearest
+ *                position on the centre side that was not degenerate.  A position whose iterate X has an entry of
+ *                X^H X - I above 1e-3 (real or imaginary part) is degenerate: it keeps Ahat_x.  status [B] int32: the count
+ *                of degenerate positions.  noise_cov psi [n_coils][n_coils] c64 or NULL (identity).  work: 2 * B int32.
+ *                A may not overlap Ahat.
+ *   apply_rows   out_v(b,x,c) = sum_k A[b][x][v][k] y_k(b,x,c): y [n_coils][B][H][W], out [n_virtual][B][H][W] c64; A per
+ *                image [B][H][n_virtual][n_coils] (per_image != 0) or one [H][n_virtual][n_coils] for the batch.
+ *   compress     the whole chain y -> y' [n_virtual][B][H][W] with A [B][H][n_virtual][n_coils], eig [B][H][n_coils] (or
+ *                NULL) and status [B]: the degenerate count, or -1 (and zero matrices) where a Cholesky pivot of psi was not
+ *                positive.  work: ipdm_gcc_workspace_bytes(B, n_coils, n_virtual, H, W) bytes, overlapping neither y nor out.
+ * Coil counts and B as above; ipdm_gcc_supported tells without a GPU.  Asynchronous, no atomics, capturable in a hipGraph. */
+int ipdm_gcc_supported(int n_coils, int n_virtual, int H, int W, int win);              /* 1 / 0, no GPU needed */
+size_t ipdm_gcc_workspace_bytes(int B, int n_coils, int n_virtual, int H, int W);        /* 0 when unserved */
+int ipdm_readout_fft_c64(const float* in, float* out, int inverse, int64_t planes, int H, int W, void* stream);
+int ipdm_gcc_gram_c64(const float* h, int aw, int win, float* gram, int B, int n_coils, int H, int W, void* stream);
+int ipdm_gcc_align_c64(const float* Ahat, const float* noise_cov, float* A, int32_t* status, int32_t* work, int B, int H,
+                       int n_coils, int n_virtual, void* stream);
+int ipdm_coil_apply_rows_c64(const float* y, const float* A, int per_image, float* out, int B, int n_coils, int n_virtual, int H,
+                             int W, void* stream);
+int ipdm_gcc_compress_c64(const float* y, int aw, int win, int n_virtual, const float* noise_cov, float* A, float* eig,
+                          int32_t* status, float* out, float* work, int B, int n_coils, int H, int W, void* stream);
+
 /* ESPIRiT coil sensitivity maps from the calibration region (Uecker et al. 2014; one map set).  y [n_coils][B][H][W] c64 and
  * the calibration box (ah, aw) as above; ksize the side k of the k-space kernels, M = n_coils k^2.
  *   gram     Gm_b[i][j] = sum over the (2ah+2-k)(2aw+2-k) patch positions p of conj(a_p[i]) a_p[j], a_p[(c, ty, tx)] =

@@ -79,6 +79,13 @@ SIGNATURES = {
     "ipdm_coilcomp_matrix_c64": [P, P, c_int, P, P, P, c_int, c_int, P],
     "ipdm_coil_apply_c64": [P, P, c_int, P, c_int, c_int, c_int, c_int64, P],
     "ipdm_coil_compress_c64": [P, c_int, c_int, c_int, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P],
+    "ipdm_gcc_supported": [c_int, c_int, c_int, c_int, c_int],
+    "ipdm_gcc_workspace_bytes": [c_int, c_int, c_int, c_int, c_int],
+    "ipdm_readout_fft_c64": [P, P, c_int, c_int64, c_int, c_int, P],
+    "ipdm_gcc_gram_c64": [P, c_int, c_int, P, c_int, c_int, c_int, c_int, P],
+    "ipdm_gcc_align_c64": [P, P, P, P, P, c_int, c_int, c_int, c_int, P],
+    "ipdm_coil_apply_rows_c64": [P, P, c_int, P, c_int, c_int, c_int, c_int, c_int, P],
+    "ipdm_gcc_compress_c64": [P, c_int, c_int, c_int, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P],
     "ipdm_espirit_supported": [c_int, c_int, c_int, c_int],
     "ipdm_espirit_workspace_bytes": [c_int, c_int, c_int],
     "ipdm_espirit_gram_c64": [P, c_int, c_int, c_int, P, c_int, c_int, c_int, c_int, P],
@@ -189,7 +196,8 @@ _RESTYPES = {"ipdm_build_arch": c_char_p, "ipdm_debug_lds_optin_count": c_int64,
              "ipdm_conv_wino_bx3_weight_bytes": c_int64, "ipdm_conv_hx2_weight_bytes": c_int64,
              "ipdm_conv_wino_hx2_weight_bytes": c_int64, "ipdm_conv_wino1d_weight_bytes": c_int64, "ipdm_conv_wino1d_weight_bytes3d": c_int64,
              "ipdm_conv1d_hx2_weight_bytes": c_int64, "ipdm_csm_workspace_bytes": ctypes.c_size_t,
-             "ipdm_coilcomp_workspace_bytes": ctypes.c_size_t, "ipdm_espirit_workspace_bytes": ctypes.c_size_t}
+             "ipdm_coilcomp_workspace_bytes": ctypes.c_size_t, "ipdm_gcc_workspace_bytes": ctypes.c_size_t,
+             "ipdm_espirit_workspace_bytes": ctypes.c_size_t}
 
 IPDM_EINVAL = -1
 IPDM_EUNSUPPORTED = -2

@@ -445,6 +445,16 @@ static int apply_check(int B, int n, int nv, int64_t P) {
 
 }  // namespace
 
+// the eigen-stage over any count of matrices, for gcc.hip (one matrix per readout position): the grid is one-dimensional,
+// so nothing but the public entry point's contract stops at 65535
+namespace ipdm_coilcomp {
+int matrix_many(const float2* gram, const float2* psi, int nv, float2* A, float* eig, int32_t* status, int64_t count, int n,
+                hipStream_t s) {
+  if (count > 0x7fffffffLL) return IPDM_EUNSUPPORTED;
+  return matrix_launch(gram, psi, nv, A, eig, status, (int)count, n, s);
+}
+}  // namespace ipdm_coilcomp
+
 extern "C" int ipdm_coilcomp_supported(int n_coils, int n_virtual) {
   return n_coils >= 1 && n_coils <= CC_MAX_COILS && n_virtual >= 1 && n_virtual <= n_coils && n_virtual <= CC_MAX_VIRTUAL;
 }

@@ -12,7 +12,8 @@ import torch
 from . import ops as ops_mod
 
 from .helpers.load_data import load_config
-from .ncsn.linear_transforms.undersampling_fourier import SENSE, calibration_region
+from .ncsn.linear_transforms.undersampling_fourier import (RandomUndersamplingFourier, SENSE, calibration_region,
+                                                           geometric_compression_check)
 from .ncsn.models import get_sigmas
 from .ncsn.models.ALD_optimizers import ALDInvSegProximalRealImag, SCHED_DTYPE, step_schedule
 from .ncsn.models.ncsnv2 import NCSNv2Deepest
@@ -58,7 +59,7 @@ def build_scorenet(cfg, seed=0):
 def build_problem(device, n_samples, R=40, H=128, W=128, num_sens=4, seed=0, scorenet=None, cfg=None, lr_scaled=1.0,
                   sens_maps=None, proximal="L2Penalty", proximal_kwargs=None, mask=None, estimate_maps=False, measurement=None,
                   calib_max=12, kspace_scale=None, coil_compress=None, noise_cov=None, n_slices=None, maps_method="walsh",
-                  maps_kwargs=None):
+                  maps_kwargs=None, coil_compress_mode="pca", coil_compress_window=2):
     """-> Namespace(sampler, scorenet, sigmas, op, image, measurement, call_kwargs); sens_maps: measured coil maps
     (num_sens, H, W), real or complex, instead of the synthetic "exp" maps (RSS-normalised where non-zero); proximal: a
     get_proximal name ("L2PenaltyCG": the exact proximal, proximal_kwargs = dict(max_iter=, tol=)); mask: the sampling mask
@@ -78,6 +79,10 @@ def build_problem(device, n_samples, R=40, H=128, W=128, num_sens=4, seed=0, sco
     the given / synthetic maps are compressed with the same matrix (ops.coil_apply), the automatic kspace_scale comes from
     the compressed data, and the operator, the measurement and the sampler have coil_compress coils.  The Namespace
     carries the matrix as coil_matrix ((coil_compress, n) complex64 on the host; None without compression).
+    coil_compress_mode="geometric": geometric coil compression along the readout axis H, which the mask must sample fully
+    (ops.coil_compress_geometric; coil_compress_window rows on either side of a readout position, 0..8): one matrix per
+    readout position, given / synthetic maps compressed row by row (ops.coil_apply_rows); coil_matrix is then
+    (H, coil_compress, n), or (S, H, coil_compress, n) for a stack.  "pca" (default) is the one matrix per image above.
     A stack of S slices in one batch: measurement (S, n, H, W), or n_slices=S without a measurement (not both).  Each
     slice has its own coil maps -- sens_maps (S, n, H, W), or (n, H, W) shared by the slices, or estimated / compressed per
     slice (coil_matrix (S, coil_compress, n)) -- and the operator holds them as S map sets (op.n_map_sets).  The sampler's
@@ -94,6 +99,13 @@ def build_problem(device, n_samples, R=40, H=128, W=128, num_sens=4, seed=0, sco
         raise ValueError(f"build_problem: maps_method={maps_method!r} goes with estimate_maps=True")
     if noise_cov is not None and coil_compress is None:
         raise ValueError("build_problem: noise_cov= goes with coil_compress= (whitening is part of the compression)")
+    if coil_compress_mode not in ("pca", "geometric"):
+        raise ValueError(f"build_problem: coil_compress_mode={coil_compress_mode!r}; \"pca\" or \"geometric\"")
+    geo = None                                               # the window of a geometric compression
+    if coil_compress_mode == "geometric":
+        if coil_compress is None:
+            raise ValueError("build_problem: coil_compress_mode=\"geometric\" goes with coil_compress=")
+        geo = ops_mod.gcc_window(coil_compress_window, "build_problem(coil_compress_window=...)")
     if n_slices is not None:
         if measurement is not None:
             raise ValueError("build_problem: n_slices= simulates a stack; a measured stack is measurement (S, n_coils, H, W)")
@@ -102,7 +114,7 @@ def build_problem(device, n_samples, R=40, H=128, W=128, num_sens=4, seed=0, sco
     if n_slices is not None or (measurement is not None and torch.as_tensor(measurement).dim() == 4):
         return _build_stack(device, n_samples, R, H, W, num_sens, seed, scorenet, cfg, lr_scaled, sens_maps, prox_cls,
                             proximal_kwargs, mask, estimate_maps, measurement, calib_max, kspace_scale, coil_compress, noise_cov,
-                            None if n_slices is None else int(n_slices), maps_method, maps_kwargs)
+                            None if n_slices is None else int(n_slices), maps_method, maps_kwargs, geo)
     if measurement is not None:                              # host-side checks: all fail before any GPU work
         if mask is None:
             raise ValueError("build_problem(measurement=...): pass mask=, the sampling mask of the acquisition")
@@ -119,6 +131,9 @@ def build_problem(device, n_samples, R=40, H=128, W=128, num_sens=4, seed=0, sco
         coil_compress = ops_mod._coilcomp_counts(num_sens, coil_compress, "build_problem(coil_compress=...)")
         if noise_cov is not None:
             noise_cov = ops_mod.check_noise_cov(noise_cov, num_sens, "build_problem: noise_cov")
+        if geo is not None:                                  # without mask=: the line mask the operator will generate
+            geometric_compression_check(mask if mask is not None else RandomUndersamplingFourier(R, 0.04, (1, H, W), seed).mask,
+                                        num_sens, coil_compress, H, W, calib_max, geo, "build_problem")
     n_est = num_sens if coil_compress is None else coil_compress
     _check_maps(maps_method, maps_kwargs, n_est, H, W, region)
     coil_matrix = eigval = None
@@ -130,7 +145,7 @@ def build_problem(device, n_samples, R=40, H=128, W=128, num_sens=4, seed=0, sco
         img = None
         y = measurement.to(torch.complex64).to(device).contiguous()
         if coil_compress is not None:
-            y, A, _, _ = ops_mod.coil_compress(y, *region, coil_compress, noise_cov, return_matrix=True)
+            y, A = _compress(y, region, coil_compress, noise_cov, geo)
             coil_matrix = A[0]
             if sens_maps is not None:
                 sens_maps = _compress_maps(SENSE.rss_normalize(sens_maps), coil_matrix, num_sens, H, W, device)
@@ -164,7 +179,7 @@ def build_problem(device, n_samples, R=40, H=128, W=128, num_sens=4, seed=0, sco
         img = phantom_image(H, W, seed=seed).to(device)
         meas1 = op(img)
         if coil_compress is not None:                        # simulated with the physical coils, compressed like a measured scan
-            meas1, A, _, _ = ops_mod.coil_compress(meas1, *region, coil_compress, noise_cov, return_matrix=True)
+            meas1, A = _compress(meas1, region, coil_compress, noise_cov, geo)
             coil_matrix = A[0]
             if not estimate_maps:
                 op = SENSE("custom", coil_compress, R, 0.04, (1, H, W), seed=seed, mask_T=1, normalize=False, mask_mode="custom",
@@ -212,7 +227,7 @@ def _assemble(device, n_samples, S, H, W, scorenet, cfg, sigmas, op, img, meas1,
 
 def _build_stack(device, n_samples, R, H, W, num_sens, seed, scorenet, cfg, lr_scaled, sens_maps, prox_cls, proximal_kwargs,
                  mask, estimate_maps, measurement, calib_max, kspace_scale, coil_compress, noise_cov, n_slices,
-                 maps_method="walsh", maps_kwargs=None):
+                 maps_method="walsh", maps_kwargs=None, geo=None):
     """build_problem for a stack of slices (its docstring): measurement (S, n, H, W), or n_slices simulated ones.  Every
     shape, mask and calibration-region check runs on the host before the score network is built or the GPU is touched."""
     region = None
@@ -254,6 +269,9 @@ def _build_stack(device, n_samples, R, H, W, num_sens, seed, scorenet, cfg, lr_s
             op = SENSE("custom", num_sens, R, 0.04, (1, H, W), seed=seed, mask_T=1, sens_maps=sens_maps, **mk)
         if estimate_maps or coil_compress is not None:
             region = calibration_region(op.random_under_fourier.mask, H, W, calib_max)
+    if geo is not None:
+        geometric_compression_check(mask if measurement is not None else op.random_under_fourier.mask, num_sens, coil_compress,
+                                    H, W, calib_max, geo, "build_problem")
     maps_kwargs = dict(maps_kwargs or {})
     _check_maps(maps_method, maps_kwargs, num_sens if coil_compress is None else coil_compress, H, W, region)
     coil_matrix = eigval = None
@@ -265,7 +283,7 @@ def _build_stack(device, n_samples, R, H, W, num_sens, seed, scorenet, cfg, lr_s
         img = None
         y = measurement.to(torch.complex64).to(device).transpose(0, 1).contiguous()          # (n, S, H, W): one image per slice
         if coil_compress is not None:
-            y, coil_matrix, _, _ = ops_mod.coil_compress(y, *region, coil_compress, noise_cov, return_matrix=True)
+            y, coil_matrix = _compress(y, region, coil_compress, noise_cov, geo)
             if sens_maps is not None:
                 sens_maps = _compress_map_sets(SENSE.rss_normalize(sens_maps), coil_matrix, device)
         if region is not None:
@@ -289,7 +307,7 @@ def _build_stack(device, n_samples, R, H, W, num_sens, seed, scorenet, cfg, lr_s
         meas1 = op(img)                                                                       # (n, S, 1, H, W)
         sim_mask = op.random_under_fourier.mask
         if coil_compress is not None:
-            meas1, coil_matrix, _, _ = ops_mod.coil_compress(meas1, *region, coil_compress, noise_cov, return_matrix=True)
+            meas1, coil_matrix = _compress(meas1, region, coil_compress, noise_cov, geo)
             if not estimate_maps:
                 op = SENSE("custom", n_out, R, 0.04, (1, H, W), seed=seed, mask_T=1, normalize=False, mask_mode="custom",
                            mask=sim_mask, sens_maps=_compress_map_sets(op.sens_maps, coil_matrix, device))
@@ -300,11 +318,28 @@ def _build_stack(device, n_samples, R, H, W, num_sens, seed, scorenet, cfg, lr_s
                      estimate_maps, kspace_scale, coil_matrix, eigval)
 
 
+def _compress(y, region, n_virtual, noise_cov, geo):
+    """the measurement y (n, B, ..., H, W) compressed to n_virtual coils -> (y', A): by PCA of the calibration box, A
+    (B, nv, n), or -- geo: the window -- geometrically along the readout, A (B, H, nv, n); a position that could not be
+    aligned is an error"""
+    if geo is None:
+        out, A, _, _ = ops_mod.coil_compress(y, *region, n_virtual, noise_cov, return_matrix=True)
+        return out, A
+    out, A, _, status = ops_mod.coil_compress_geometric(y, region[1], n_virtual, geo, noise_cov, return_matrix=True)
+    for b, st in enumerate(status.cpu().tolist()):
+        if st != 0:
+            raise RuntimeError(f"build_problem: geometric coil compression of image {b}: " + (
+                "the noise covariance has a non-positive Cholesky pivot in fp32" if st < 0 else
+                f"{st} readout position(s) could not be aligned with their neighbour"))
+    return out, A
+
+
 def _compress_map_sets(maps, A, device):
     """coil maps (S, n, H, W) of the physical coils -> (S, nv, H, W) of the virtual coils, host complex128: slice s by its own
-    matrix A[s] of A (S, nv, n), one call of the streaming kernel with a matrix per image"""
+    matrix A[s] of A (S, nv, n), one call of the streaming kernel with a matrix per image (A (S, H, nv, n): per row)"""
     m = torch.as_tensor(maps).to(torch.complex64).to(device).transpose(0, 1).contiguous()    # (n, S, H, W)
-    return ops_mod.coil_apply(m, A.contiguous()).transpose(0, 1).cpu().to(torch.complex128).contiguous()
+    fn = ops_mod.coil_apply_rows if A.dim() == 4 else ops_mod.coil_apply
+    return fn(m, A.contiguous()).transpose(0, 1).cpu().to(torch.complex128).contiguous()
 
 
 def _compress_maps(maps, A, n, H, W, device):
@@ -314,7 +349,8 @@ def _compress_maps(maps, A, n, H, W, device):
     if tuple(maps.shape) != (n, H, W):
         raise ValueError(f"build_problem: sens_maps {tuple(maps.shape)}, expected {(n, H, W)}")
     m = maps.to(torch.complex64).to(device).reshape(n, 1, H, W).contiguous()
-    return ops_mod.coil_apply(m, A.contiguous())[:, 0].cpu().to(torch.complex128)
+    fn = ops_mod.coil_apply_rows if A.dim() == 3 else ops_mod.coil_apply           # A (H, nv, n): one matrix per row
+    return fn(m, A.contiguous())[:, 0].cpu().to(torch.complex128)
 
 
 class IterationRunner:

@@ -98,6 +98,32 @@ def calibration_region(mask, H, W, calib_max=12, composite=False):
     return ah, aw
 
 
+def readout_fully_sampled(mask, H, W):
+    """whether every sampled column of `mask` (any shape ``ops._mask_u8`` takes) is sampled at all H rows in every frame: a
+    line mask always is, a 2-D mask only when each of its columns is full or empty.  Host only."""
+    m = ops._mask_u8(mask, H, W, "cpu").bool()
+    if m.dim() == 2:                                            # line mask [T][W]
+        return True
+    return bool((m.all(dim=-2) == m.any(dim=-2)).all())
+
+
+def geometric_compression_check(mask, n, n_virtual, H, W, calib_max=12, window=2, what="compress_measurement"):
+    """host checks of a geometric coil compression along the readout axis H -> (n_virtual, aw, window), aw the column
+    half-width of ``calibration_region(mask, H, W, calib_max)``.  ValueError: a mask whose readout is not fully sampled, a
+    window outside 0..8 or with fewer samples than virtual coils; IpdmUnsupported: an H x W without a k-space kernel, coil
+    counts outside ``ops.coilcomp_supported``.  No GPU work."""
+    n_virtual = ops._coilcomp_counts(n, n_virtual, what)
+    window = ops.gcc_window(window, what)
+    if not readout_fully_sampled(mask, H, W):
+        raise ValueError(f"{what}: geometric coil compression needs a fully sampled readout: some sampled column of the "
+                         f"{H}x{W} mask is not sampled at all {H} rows (a 2-D (ky, kz) pattern); use the PCA compression")
+    if ops.kspace_size_class(H, W) == ops.KSPACE_NONE:
+        raise ops._lib.IpdmUnsupported(f"{what}: no k-space kernel for {H}x{W}; {ops.KSPACE_SIZE_RULE}")
+    _, aw = calibration_region(mask, H, W, calib_max)
+    n_virtual, window = ops.gcc_check(n, n_virtual, H, W, aw, window, what)
+    return n_virtual, aw, window
+
+
 def composite_mask(mask, H, W):
     """-> host bool tensor, (W,) for a line mask and (H, W) for a 2-D mask: the union over the frames of `mask` (any shape
     ``ops._mask_u8`` takes), where the time-averaged composite of a cine acquisition holds data"""
@@ -316,15 +342,32 @@ class SENSE(LinearTransform):
         return y, y.dim() == 4
 
     @staticmethod
-    def compress_measurement(y, mask, n_virtual, noise_cov=None, calib_max=12):
+    def compress_measurement(y, mask, n_virtual, noise_cov=None, calib_max=12, geometric=False, window=2):
         """whitening and coil compression of a measurement: y (n, H, W) multi-coil k-space as for estimate_sens_maps (up to
         64 coils), n_virtual 1..min(n, 32) virtual coils by PCA of the calibration box ``calibration_region(mask, H, W,
         calib_max)``, noise_cov the (n, n) Hermitian positive definite coil noise covariance of the prescan (None: white
         noise assumed).  ``ops.coil_compress`` on the current GPU.  -> (y' (n_virtual, H, W) complex64 on the GPU,
         A (n_virtual, n) complex64 on the host).  y (S, n, H, W), a stack of slices: one batched call, one matrix per slice
-        -> (y' (S, n_virtual, H, W), A (S, n_virtual, n)).  Every argument is checked on the host before any GPU work."""
+        -> (y' (S, n_virtual, H, W), A (S, n_virtual, n)).  Every argument is checked on the host before any GPU work.
+        geometric=True: geometric coil compression along the readout axis H, which the mask must sample fully
+        (``ops.coil_compress_geometric``): one matrix per readout position from the calibration columns (aw of the
+        calibration box) and `window` rows on either side (0..8) -> A (H, n_virtual, n), or (S, H, n_virtual, n)."""
         y, stack = SENSE._measurement_operand(y, "compress_measurement")
         n, H, W = y.shape[-3:]
+        if geometric:
+            n_virtual, aw, window = geometric_compression_check(mask, n, n_virtual, H, W, calib_max, window)
+            if noise_cov is not None:
+                noise_cov = ops.check_noise_cov(noise_cov, n, "compress_measurement: noise_cov")
+            yd = y.to(torch.complex64).to(y.device if y.is_cuda else "cuda")
+            yd = yd.transpose(0, 1).contiguous() if stack else yd.contiguous()
+            out, A, _, status = ops.coil_compress_geometric(yd, aw, n_virtual, window, noise_cov, return_matrix=True)
+            for b, st in enumerate(status.cpu().tolist()):
+                if st != 0:
+                    raise RuntimeError(f"compress_measurement: image {b}: " + (
+                        "the noise covariance has a non-positive Cholesky pivot in fp32" if st < 0 else
+                        f"{st} readout position(s) could not be aligned with their neighbour (no signal in the calibration "
+                        "columns there?)"))
+            return (out.transpose(0, 1).contiguous(), A.cpu()) if stack else (out, A[0].cpu())
         n_virtual = ops._coilcomp_counts(n, n_virtual, "compress_measurement")
         if noise_cov is not None:
             noise_cov = ops.check_noise_cov(noise_cov, n, "compress_measurement: noise_cov")
@@ -337,19 +380,24 @@ class SENSE(LinearTransform):
         return out, A[0].cpu()
 
     @classmethod
-    def from_measurement(cls, y, mask, R=1, seed=None, calib_max=12, n_virtual=None, noise_cov=None, method="walsh", **kw):
+    def from_measurement(cls, y, mask, R=1, seed=None, calib_max=12, n_virtual=None, noise_cov=None, method="walsh",
+                         geometric=False, window=2, **kw):
         """the ``"custom"`` operator of an acquisition: maps estimated from its own measurement y (n, H, W) and sampling
         mask (estimate_sens_maps; method and kw go to the estimator).  R is informational, as for every custom mask.  n_virtual:
         the measurement is whitened (noise_cov) and compressed first (compress_measurement) and the maps are those of the
         virtual coils -- the operator then has n_virtual coils and serves the compressed measurement.  y (S, n, H, W), a
-        stack of slices: the multi-set operator, maps (and compression) per slice (n_map_sets == S)."""
+        stack of slices: the multi-set operator, maps (and compression) per slice (n_map_sets == S).  geometric, window:
+        compress_measurement's (they go with n_virtual=)."""
+        if geometric and n_virtual is None:
+            raise ValueError("from_measurement: geometric= goes with n_virtual=")
         if method != "walsh":                                               # host only: fails before the compression runs
             y0, _ = cls._measurement_operand(y, "from_measurement")
             n0, H0, W0 = y0.shape[-3:]
             cls._check_maps_method(method, n0 if n_virtual is None else int(n_virtual), H0, W0,
                                    *calibration_region(mask, H0, W0, calib_max), dict(kw), "from_measurement")
         if n_virtual is not None:
-            y, _ = cls.compress_measurement(y, mask, n_virtual, noise_cov=noise_cov, calib_max=calib_max)
+            y, _ = cls.compress_measurement(y, mask, n_virtual, noise_cov=noise_cov, calib_max=calib_max, geometric=geometric,
+                                            window=window)
         elif noise_cov is not None:
             raise ValueError("from_measurement: noise_cov= goes with n_virtual= (whitening is part of the compression)")
         kw.pop("return_eig", None)

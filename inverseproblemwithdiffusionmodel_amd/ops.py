@@ -663,6 +663,143 @@ def coil_compress(y, ah, aw, n_virtual, noise_cov=None, return_matrix=False, *, 
     return (out, A, eig, status) if return_matrix else out
 
 
+# ---- geometric coil compression along the readout (csrc/gcc.hip) -------------------------------------------------------
+GCC_MAX_WINDOW = 8
+
+
+def gcc_supported(n_coils, n_virtual, H, W, win=2):
+    """whether coil_compress_geometric has kernels for n_coils (1..64) -> n_virtual (1..min(n_coils, 32)), a readout side
+    H (a power of two from 4 or a multiple of 16 of the form 2^a 3^b 5^c, at most 2048), W >= 1 and a window half-width
+    0..8.  Needs no GPU."""
+    return bool(_lib.lib.ipdm_gcc_supported(int(n_coils), int(n_virtual), int(H), int(W), int(win)))
+
+
+def gcc_workspace(B, n_coils, n_virtual, H, W, device):
+    """scratch tensor of coil_compress_geometric (hybrid data, Gram matrices, unaligned matrices); None when unserved"""
+    nbytes = _lib.lib.ipdm_gcc_workspace_bytes(int(B), int(n_coils), int(n_virtual), int(H), int(W))
+    return torch.empty(nbytes // 4, dtype=torch.float32, device=device) if nbytes else None
+
+
+def gcc_window(win, what="gcc"):
+    """host check of the window half-width: an integer 0..8"""
+    if isinstance(win, bool) or not isinstance(win, (int, float)) or int(win) != win or not 0 <= win <= GCC_MAX_WINDOW:
+        raise ValueError(f"ipdm {what}: window = {win!r} outside 0..{GCC_MAX_WINDOW} (readout positions on either side)")
+    return int(win)
+
+
+def gcc_check(n_coils, n_virtual, H, W, aw, win, what="gcc"):
+    """host checks of a geometric compression, before any launch -> (n_virtual, win).  ValueError: a window outside 0..8, or
+    one that holds fewer samples than virtual coils; IpdmUnsupported: coil counts or a readout side without a kernel."""
+    win = gcc_window(win, what)
+    n_virtual = _coilcomp_counts(n_coils, n_virtual, what)
+    samples = (2 * win + 1) * (2 * int(aw) + 1)
+    if samples < n_virtual:
+        raise ValueError(f"ipdm {what}: the window holds {samples} samples per readout position ((2*{win}+1) rows x "
+                         f"(2*{int(aw)}+1) calibration columns), fewer than the {n_virtual} virtual coils")
+    if not gcc_supported(n_coils, n_virtual, H, W, win):
+        raise _lib.IpdmUnsupported(f"ipdm {what}: no readout transform for H = {H}; {KSPACE_SIZE_RULE}")
+    return n_virtual, win
+
+
+def readout_fft(x, inverse=False, out=None):
+    """centred orthonormal DFT (inverse=True: inverse DFT) along H of x (..., H, W) complex64, with fft2c's centring: the
+    inverse transform of k-space along its fully sampled readout axis is the hybrid space whose row x is image row x.
+    out may be x itself."""
+    _c64_operand(x, "x", "readout_fft")
+    if x.dim() < 2:
+        raise ValueError(f"ipdm readout_fft: x {tuple(x.shape)}; (..., H, W) expected")
+    H, W = x.shape[-2:]
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _c64_operand(out, "out", "readout_fft")
+        if tuple(out.shape) != tuple(x.shape):
+            raise ValueError(f"ipdm readout_fft: out {tuple(out.shape)}, expected {tuple(x.shape)}")
+    planes = x.numel() // (H * W) if H * W else 0
+    call("ipdm_readout_fft_c64", _ptr(x), _ptr(out), int(bool(inverse)), planes, H, W, _stream())
+    _written(out)
+    return out
+
+
+def gcc_gram(h, aw, win=2):
+    """windowed Gram matrices of hybrid-space data h ((n, H, W) or (n, B, H, W) complex64): G_{b,x}[i][j] = sum over the
+    rows [x-win, x+win] (clipped at the edges) and the columns [W//2-aw, W//2+aw] of h_i conj(h_j) -> (B, H, n, n)
+    complex64, exactly Hermitian"""
+    n, B, H, W = _csm_measurement(h, "gcc_gram")
+    aw = _csm_box(0, aw)[1]
+    win = gcc_window(win, "gcc_gram")
+    out = torch.empty((B, H, n, n), dtype=torch.complex64, device=h.device)
+    call("ipdm_gcc_gram_c64", _ptr(h), aw, win, _ptr(out), B, n, H, W, _stream())
+    return out
+
+
+def gcc_align(A, noise_cov=None, return_status=False):
+    """alignment of per-position compression matrices A (B, H, nv, n) or (H, nv, n) complex64 along H: the centre row
+    H // 2 is kept, every other position is turned onto its neighbour on the centre side by the unitary polar factor of
+    A_x psi A_p^H (ipdm.h, ipdm_gcc_align_c64) -> the aligned matrices of A's shape; return_status: -> (A, status (B,)
+    int32, the count of degenerate positions per image).  noise_cov is checked on the host before any launch."""
+    _c64_operand(A, "A", "gcc_align")
+    if A.dim() not in (3, 4):
+        raise ValueError(f"ipdm gcc_align: A {tuple(A.shape)}; (B, H, nv, n) or (H, nv, n) expected")
+    B = A.shape[0] if A.dim() == 4 else 1
+    H, nv, n = A.shape[-3:]
+    _coilcomp_counts(n, nv, "gcc_align")
+    psi = _noise_cov_dev(noise_cov, n, A.device, "gcc_align")
+    out = torch.empty_like(A)
+    status = torch.empty(B, dtype=torch.int32, device=A.device)
+    work = torch.empty(2 * B, dtype=torch.int32, device=A.device)
+    call("ipdm_gcc_align_c64", _ptr(A), _ptr(psi), _ptr(out), _ptr(status), _ptr(work), B, H, n, nv, _stream())
+    return (out, status) if return_status else out
+
+
+def coil_apply_rows(y, A, out=None):
+    """y'_v(x, c) = sum_k A[x][v][k] y_k(x, c), one matrix per row: y (n, H, W) or (n, B, H, W) complex64 (hybrid-space data,
+    or coil maps in image space), A (B, H, nv, n) per image or (H, nv, n) shared by the batch -> (nv,) + y.shape[1:].
+    out may not overlap y."""
+    n, B, H, W = _csm_measurement(y, "coil_apply_rows")
+    _c64_operand(A, "A", "coil_apply_rows")
+    if A.dim() not in (3, 4) or A.shape[-1] != n or A.shape[-3] != H or (A.dim() == 4 and A.shape[0] != B):
+        raise ValueError(f"ipdm coil_apply_rows: A {tuple(A.shape)} does not match y {tuple(y.shape)}; (B, H, nv, n) or "
+                         "(H, nv, n) expected")
+    nv = _coilcomp_counts(n, A.shape[-2], "coil_apply_rows")
+    shape = (nv,) + tuple(y.shape[1:])
+    if out is None:
+        out = torch.empty(shape, dtype=torch.complex64, device=y.device)
+    else:
+        _c64_operand(out, "out", "coil_apply_rows")
+        if tuple(out.shape) != shape:
+            raise ValueError(f"ipdm coil_apply_rows: out {tuple(out.shape)}, expected {shape}")
+    call("ipdm_coil_apply_rows_c64", _ptr(y), _ptr(A), int(A.dim() == 4), _ptr(out), B, n, nv, H, W, _stream())
+    _written(out)
+    return out
+
+
+def coil_compress_geometric(y, aw, n_virtual, win=2, noise_cov=None, return_matrix=False, *, work=None):
+    """geometric coil compression of multi-coil k-space y ((n, H, W), (n, B, H, W) or (n, B, 1, H, W) complex64) whose
+    axis H is fully sampled: one matrix per readout position from the calibration columns [W//2-aw, W//2+aw] and the rows
+    [x-win, x+win] of the hybrid space, aligned along x (ipdm.h, ipdm_gcc_compress_c64) -> y' of y's shape with n_virtual
+    coils; return_matrix: -> (y', A (B, H, n_virtual, n), eig (B, H, n), status (B,)).  Asynchronous; no host
+    synchronisation."""
+    n, B, H, W = _csm_measurement(y, "coil_compress_geometric")
+    aw = _csm_box(0, aw)[1]
+    n_virtual, win = gcc_check(n, n_virtual, H, W, aw, win, "coil_compress_geometric")
+    psi = _noise_cov_dev(noise_cov, n, y.device, "coil_compress_geometric")
+    need = _lib.lib.ipdm_gcc_workspace_bytes(B, n, n_virtual, H, W)
+    if work is None:
+        work = gcc_workspace(B, n, n_virtual, H, W, y.device)
+    elif (not isinstance(work, torch.Tensor) or not work.is_cuda or work.dtype != torch.float32 or not work.is_contiguous()
+            or work.numel() * 4 < need):
+        raise ValueError(f"coil_compress_geometric: `work` must be a contiguous float32 GPU tensor of >= {need} bytes "
+                         f"(ops.gcc_workspace({B}, {n}, {n_virtual}, {H}, {W}, device))")
+    out = torch.empty((n_virtual,) + tuple(y.shape[1:]), dtype=torch.complex64, device=y.device)
+    A = torch.empty((B, H, n_virtual, n), dtype=torch.complex64, device=y.device)
+    eig = torch.empty((B, H, n), dtype=torch.float32, device=y.device)
+    status = torch.empty(B, dtype=torch.int32, device=y.device)
+    call("ipdm_gcc_compress_c64", _ptr(y), aw, win, n_virtual, _ptr(psi), _ptr(A), _ptr(eig), _ptr(status), _ptr(out),
+         _ptr(work), B, n, H, W, _stream())
+    return (out, A, eig, status) if return_matrix else out
+
+
 # ---- ESPIRiT coil sensitivity maps from the calibration region (csrc/espirit.hip) ------------------------------------------
 ESPIRIT_MAX_COILS, ESPIRIT_MAX_COLUMNS = 16, 432
 

@@ -5,8 +5,8 @@ reconstructions.pt, ZF.pt, mask.pt, args_dict.pkl).  Data and weights are synthe
 unless --ckpt points at a Lightning checkpoint of the reference and --kspace at measured multi-coil k-space (with its
 --mask; no ground truth then: original.pt and the RMSE line are skipped); --estimate_maps takes the coil maps from the
 measurement's own calibration region (sens_maps.pt); --coil_compress N whitens (--noise_cov PATH) and compresses the
-measurement to N virtual coils first (coil_matrix.pt).  Samples are sharded over the launched ranks (torchrun) and rank 0
-writes the posterior mean / std next to the reconstructions.
+measurement to N virtual coils first (coil_matrix.pt; --coil_compress_mode geometric: one matrix per readout position).
+Samples are sharded over the launched ranks (torchrun) and rank 0 writes the posterior mean / std next to the reconstructions.
 A stack of slices in ONE batch: --n_slices S simulates S slices (phantom seeds seed .. seed + S - 1, coil maps per slice),
 --kspace PATH --slices reads a measured stack (S, n_coils, H, W).  --num_samples then counts samples PER SLICE: the batch
 axis of reconstructions.pt has num_samples * S rows in the order sample * S + slice, sens_maps.pt is (S, n, H, W), and
@@ -76,6 +76,11 @@ if __name__ == '__main__':
     parser.add_argument("--coil_compress", type=int, default=None, metavar="N",
                         help="whiten and compress the measurement (up to 64 coils) to N <= 32 virtual coils by PCA of its "
                              "calibration region; the maps are estimated on, or compressed to, the virtual coils")
+    parser.add_argument("--coil_compress_mode", choices=["pca", "geometric"], default="pca",
+                        help="--coil_compress: pca: one matrix per image; geometric: one per readout position (the readout "
+                             "axis H must be fully sampled, as with every line mask), aligned along the readout")
+    parser.add_argument("--coil_compress_window", type=int, default=2, metavar="K",
+                        help="--coil_compress_mode geometric: readout positions on either side of a position (0..8)")
     parser.add_argument("--noise_cov", default=None,
                         help="--coil_compress: .npy / .pt file with the (n_coils, n_coils) coil noise covariance of the prescan")
     parser.add_argument("--kspace_scale", default="auto",
@@ -152,6 +157,17 @@ if __name__ == '__main__':
                                   H, W, args_dict["calib_max"])
         except ValueError as e:
             sys.exit(f"--estimate_maps / --coil_compress / --kspace: {e}")
+    geometric = args_dict["coil_compress_mode"] == "geometric"
+    if geometric and args_dict["coil_compress"] is None:
+        sys.exit("--coil_compress_mode geometric goes with --coil_compress N")
+    if geometric:                                                         # refused here, before the score network is built
+        try:
+            uf.geometric_compression_check(mask if mask is not None else
+                                           uf.RandomUndersamplingFourier(args_dict["R"], 0.04, (1, H, W), args_dict["seed"]).mask,
+                                           args_dict["num_sens"], args_dict["coil_compress"], H, W, args_dict["calib_max"],
+                                           args_dict["coil_compress_window"], "--coil_compress_mode geometric")
+        except (ValueError, NotImplementedError) as e:
+            sys.exit(str(e))
     maps_method, maps_kwargs = driver_maps_method(
         args_dict, args_dict["estimate_maps"],
         args_dict["num_sens"] if args_dict["coil_compress"] is None else args_dict["coil_compress"], H, W, region)
@@ -180,6 +196,8 @@ if __name__ == '__main__':
                                 sens_maps=sens_maps, mask=mask, estimate_maps=args_dict["estimate_maps"], measurement=kspace,
                                 calib_max=args_dict["calib_max"], kspace_scale=kspace_scale,
                                 coil_compress=args_dict["coil_compress"], noise_cov=noise_cov,
+                                coil_compress_mode=args_dict["coil_compress_mode"],
+                                coil_compress_window=args_dict["coil_compress_window"],
                                 n_slices=None if kspace is not None else args_dict["n_slices"],
                                 maps_method=maps_method, maps_kwargs=maps_kwargs,
                                 proximal=args_dict["proximal_type"],
