@@ -500,6 +500,20 @@ int ipdm_conv3x3_thin_f32(const float* x, const float* w, const float* bias,
                           const float* coef /* NULL, or [B][Cin][3] = (c0, c1, c2): the input is (x - c0) * c1 + c2 inside the
                                                image (few-input-channel form only: `h = 2x - 1`, ncsnv2.py:64) */,
                           float* out, int B, int Cin, int Cout, int H, int W, void* stream);
+/* The few-input-channel form with the statistics epilogue of the Winograd entries (ipdm_conv2d_wino1d_stats_f32): part
+ * [B][Cout][P][3] = (count, mean, sum of squared deviations) of the stored values per group of 64 quads of a plane, P =
+ * ipdm_conv3x3_thin_stats_partials (0: this shape has no such epilogue, the _stats entry answers IPDM_EUNSUPPORTED) -- what
+ * ipdm_instnorm_plus_coef_partials_f32 takes instead of a pass over the tensor.  `out` has the bits of ipdm_conv3x3_thin_f32. */
+int ipdm_conv3x3_thin_stats_partials(int Cin, int Cout, int H, int W);
+int ipdm_conv3x3_thin_stats_f32(const float* x, const float* w, const float* bias, const float* coef, float* out, float* part,
+                                int B, int Cin, int Cout, int H, int W, void* stream);
+/* The few-output-channel form (Cout <= 3) on act(InstanceNorm++(x)) given as the RAW x and coef [B][Cin][3] (mu, scale, shift
+ * from ipdm_instnorm_plus_coef_*): end_conv(act(normalizer(x))) of ncsn/models/ncsnv2.py:270-271 in one pass over x.  act:
+ * IPDM_ACT_ELU only (else IPDM_EUNSUPPORTED).  The result equals ipdm_affine_act_f32 followed by ipdm_conv3x3_thin_f32 bit
+ * for bit.  W % 4 == 0, 16-byte aligned x / out (else IPDM_EUNSUPPORTED). */
+int ipdm_conv3x3_fewout_fin_supported(int Cin, int Cout, int H, int W);
+int ipdm_conv3x3_fewout_fin_f32(const float* x, const float* w, const float* bias, const float* coef, int act, float* out,
+                                int B, int Cin, int Cout, int H, int W, void* stream);
 /* MaxPool2d(kernel 5, stride 1, padding 2) on [planes][H][W] */
 int ipdm_maxpool5_f32(const float* x, float* y, int planes, int H, int W, void* stream);
 /* CondCRPBlock's norm + AvgPool2d(5, stride 1, padding 2) (ncsn/models/layers.py:86-110) in one pass:

@@ -112,6 +112,10 @@ SIGNATURES = {
     "ipdm_bilinear_f32": [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P],
     "ipdm_conv3x3_thin_supported": [c_int, c_int, c_int, c_int],
     "ipdm_conv3x3_thin_f32": [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P],
+    "ipdm_conv3x3_thin_stats_partials": [c_int, c_int, c_int, c_int],
+    "ipdm_conv3x3_thin_stats_f32": [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P],
+    "ipdm_conv3x3_fewout_fin_supported": [c_int, c_int, c_int, c_int],
+    "ipdm_conv3x3_fewout_fin_f32": [P, P, P, P, c_int, P, c_int, c_int, c_int, c_int, c_int, P],
     "ipdm_trilinear_f32": [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P],
     "ipdm_groupnorm_coef_f32": [P, P, P, P, c_int, c_int, c_int, c_int, c_float, P, P],
     "ipdm_groupnorm_coef_partials_f32": [P, c_int, P, c_int, c_int, P, P, P, c_int, c_int, c_float, P],

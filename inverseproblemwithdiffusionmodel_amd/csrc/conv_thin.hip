@@ -10,20 +10,29 @@
 namespace {
 
 // ---- few input channels: out[b][co][y][4q..4q+3], one thread per (b, y, quad) and CO_BLK output channels -------------------
-template <int CIN>
+// STATS: the statistics epilogue of the Winograd kernels (conv_wino1d.hip) for the InstanceNorm++ that reads the result next:
+// part [B][Cout][P][3] = (count, mean, sum of squared deviations) of the STORED values per group of 64 items, which
+// plane_stats_from_partials_kernel merges -- the 128-channel tensor is not read a second time.  An image's items are padded to
+// P * 64, so that a wave (= one group) never straddles two images; a padding lane repeats the image's last item, stores nothing
+// and counts for nothing.  One-pass sums about a shift taken from the data (the wave's first value), as the Winograd epilogue.
+template <int CIN, bool STATS>
 __global__ __launch_bounds__(256) void conv3x3_fewin_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                             const float* __restrict__ bias, const float* __restrict__ coef,
                                                             float* __restrict__ out, int B, int Cout, int H, int W,
-                                                            int co_blk) {
+                                                            int co_blk, float* __restrict__ part, int P) {
   const int Q = W >> 2;
-  const long long items = (long long)B * H * Q;
+  const int HQ = H * Q;
+  const long long per = STATS ? (long long)P * 64 : (long long)HQ;       // items per image
+  const long long items = (long long)B * per;
   const int co0 = blockIdx.y * co_blk;
   const int co1 = min(Cout, co0 + co_blk);
   for (long long it = (long long)blockIdx.x * 256 + threadIdx.x; it < items; it += (long long)gridDim.x * 256) {
-    const int q = (int)(it % Q);
-    const long long t = it / Q;
-    const int y = (int)(t % H);
-    const int b = (int)(t / H);
+    const int b = (int)(it / per);
+    const int rit = (int)(it % per);
+    const bool live = !STATS || rit < HQ;
+    const int ric = live ? rit : HQ - 1;
+    const int q = ric % Q;
+    const int y = ric / Q;
     float in[CIN][3][6];                               // columns 4q-1 .. 4q+4 of rows y-1 .. y+1
 #pragma unroll
     for (int ci = 0; ci < CIN; ++ci) {
@@ -66,7 +75,27 @@ __global__ __launch_bounds__(256) void conv3x3_fewin_kernel(const float* __restr
             a2 = fmaf(wv, in[ci][r][c + 2], a2);
             a3 = fmaf(wv, in[ci][r][c + 3], a3);
           }
-      *reinterpret_cast<float4*>(op) = make_float4(a0, a1, a2, a3);
+      if (live) *reinterpret_cast<float4*>(op) = make_float4(a0, a1, a2, a3);
+      if constexpr (STATS) {
+        // (every lane of the wave is here: `items` is a multiple of 64 and the channel loop is uniform; lane 0 is live)
+        const int lane = threadIdx.x & 63;
+        const float K = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, a0)));
+        const float d0 = live ? a0 - K : 0.f, d1 = live ? a1 - K : 0.f, d2 = live ? a2 - K : 0.f, d3 = live ? a3 - K : 0.f;
+        const float s1 = (d0 + d1) + (d2 + d3), s2 = (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+        // both sums in one butterfly: even lanes gather the sums, odd lanes the squares
+        const bool odd = lane & 1;
+        float v = odd ? s2 : s1;
+        v += __shfl_xor(odd ? s1 : s2, 1, 64);
+#pragma unroll
+        for (int m = 2; m < 64; m <<= 1) v += __shfl_xor(v, m, 64);
+        const float t2 = __shfl(v, 1, 64);
+        const float cnt = 4.f * (float)__popcll(__ballot(live));
+        if (lane == 0) {
+          const float dm = v / cnt;
+          float* sp = part + (((size_t)b * Cout + co) * P + rit / 64) * 3;
+          sp[0] = cnt; sp[1] = K + dm; sp[2] = fmaxf(t2 - v * dm, 0.f);
+        }
+      }
     }
   }
 }
@@ -193,26 +222,32 @@ extern "C" int ipdm_conv3x3_thin_supported(int Cin, int Cout, int H, int W) {
   return (W % 4 == 0 && H > 0 && ((Cin >= 1 && Cin <= 3 && Cout >= 1) || (Cout >= 1 && Cout <= 3 && Cin >= 1))) ? 1 : 0;
 }
 
-extern "C" int ipdm_conv3x3_thin_f32(const float* x, const float* w, const float* bias, const float* coef, float* out, int B,
-                                     int Cin, int Cout, int H, int W, void* stream) {
+static int thin_launch(const float* x, const float* w, const float* bias, const float* coef, float* out, float* part, int B,
+                       int Cin, int Cout, int H, int W, void* stream) {
   IPDM_REQUIRE(B >= 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0);
   if (!ipdm_conv3x3_thin_supported(Cin, Cout, H, W)) return IPDM_EUNSUPPORTED;
+  if (part && !ipdm_conv3x3_thin_stats_partials(Cin, Cout, H, W)) return IPDM_EUNSUPPORTED;
   if (B == 0) return IPDM_OK;
   IPDM_REQUIRE(x && w && out && x != out);
   // float4 rows: a tensor off a 16-byte boundary is a valid argument this kernel has no form for (the callers fall through
   // to the matrix-core kernels, as for an unsupported shape)
   if (((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 15) != 0) return IPDM_EUNSUPPORTED;
   hipStream_t s = ipdm_stream(stream);
-  const long long items = (long long)B * H * (W / 4);
+  const int P = part ? ipdm_conv3x3_thin_stats_partials(Cin, Cout, H, W) : 0;
+  const long long items = part ? (long long)B * P * 64 : (long long)B * H * (W / 4);
   const int gx = ipdm_ew_grid(items, 256);
   if (Cin <= 3 && Cin <= Cout) {
     // enough (item block, channel block) pairs to fill the chip several times over, at least 8 channels per thread
     int co_blk = Cout;
     while (co_blk > 8 && (long long)gx * ((Cout + co_blk - 1) / co_blk) < 2048) co_blk = (co_blk + 1) / 2;
     const dim3 grid(gx, (Cout + co_blk - 1) / co_blk);
-    if (Cin == 1) hipLaunchKernelGGL(conv3x3_fewin_kernel<1>, grid, dim3(256), 0, s, x, w, bias, coef, out, B, Cout, H, W, co_blk);
-    else if (Cin == 2) hipLaunchKernelGGL(conv3x3_fewin_kernel<2>, grid, dim3(256), 0, s, x, w, bias, coef, out, B, Cout, H, W, co_blk);
-    else hipLaunchKernelGGL(conv3x3_fewin_kernel<3>, grid, dim3(256), 0, s, x, w, bias, coef, out, B, Cout, H, W, co_blk);
+#define IPDM_FEWIN(CI)                                                                                                        \
+  if (part) hipLaunchKernelGGL((conv3x3_fewin_kernel<CI, true>), grid, dim3(256), 0, s, x, w, bias, coef, out, B, Cout, H, W, co_blk, part, P); \
+  else hipLaunchKernelGGL((conv3x3_fewin_kernel<CI, false>), grid, dim3(256), 0, s, x, w, bias, coef, out, B, Cout, H, W, co_blk, part, P)
+    if (Cin == 1) { IPDM_FEWIN(1); }
+    else if (Cin == 2) { IPDM_FEWIN(2); }
+    else { IPDM_FEWIN(3); }
+#undef IPDM_FEWIN
   } else {
     if (coef) return IPDM_EUNSUPPORTED;          // an input affine on the wide side belongs to the producing layer
     const int Q = W / 4;
@@ -227,4 +262,21 @@ extern "C" int ipdm_conv3x3_thin_f32(const float* x, const float* w, const float
 #undef IPDM_FEWOUT
   }
   return ipdm_launch_status();
+}
+
+// number of statistics partials per (image, channel) plane the few-input-channel form writes; 0: no statistics epilogue
+extern "C" int ipdm_conv3x3_thin_stats_partials(int Cin, int Cout, int H, int W) {
+  if (!ipdm_conv3x3_thin_supported(Cin, Cout, H, W) || !(Cin <= 3 && Cin <= Cout)) return 0;
+  return (int)(((long long)H * (W / 4) + 63) / 64);
+}
+
+extern "C" int ipdm_conv3x3_thin_f32(const float* x, const float* w, const float* bias, const float* coef, float* out, int B,
+                                     int Cin, int Cout, int H, int W, void* stream) {
+  return thin_launch(x, w, bias, coef, out, nullptr, B, Cin, Cout, H, W, stream);
+}
+
+extern "C" int ipdm_conv3x3_thin_stats_f32(const float* x, const float* w, const float* bias, const float* coef, float* out,
+                                           float* part, int B, int Cin, int Cout, int H, int W, void* stream) {
+  IPDM_REQUIRE(part);
+  return thin_launch(x, w, bias, coef, out, part, B, Cin, Cout, H, W, stream);
 }

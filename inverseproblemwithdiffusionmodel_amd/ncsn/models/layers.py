@@ -98,6 +98,16 @@ class Conv2d(ops.PackedWeightMixin, nn.Module):
         ELU to the raw rows in its producer, so the normalised tensor is never written (IPDM_WINO1D_FIN=0: the separate pass)"""
         return self.route(x, coef=coef, act=ops.ACT_ELU) == ops.ROUTE_WINO1D
 
+    def streams_norm_input(self, x, act):
+        """True when this layer (a network's last: few output channels) takes act(InstanceNorm++(x)) as (raw x, coefficients) on
+        the streaming kernel, so that the normalised tensor is neither written nor read back (IPDM_THIN_FIN=0: the two passes)"""
+        return (self.ndim == 2 and self.kernel_size == 3 and self.dilation == 1 and x.dim() == 4
+                and ops.conv3x3_fewout_fin_ok(self.in_planes, self.out_planes, x.shape[2], x.shape[3], x, act))
+
+    def stream_norm_input(self, x, coef, act):
+        """conv(act(norm(x))) where streams_norm_input(): the bits of self(ops.affine_act(x, coef, act))"""
+        return ops.conv3x3_fewout_fin(x, self.weight.data, None if self.bias is None else self.bias.data, coef, act)
+
     def packed_conv1d(self):
         return self._cached("conv1d", ops.conv1d_weight)
 
@@ -117,9 +127,10 @@ class Conv2d(ops.PackedWeightMixin, nn.Module):
         return self._cached("direct_" + ops.CONV_IMPL, ops.conv_weight)
 
     def forward(self, x, coef=None, act=ops.ACT_NONE, residual=None, out=None, act_out=ops.ACT_NONE, raw=True,
-                want_stats=False, in_amax=None, feeds_conv=True, res_second=False):
+                want_stats=False, in_amax=None, feeds_conv=True, res_second=False, thin_stats=False):
         """want_stats: the result goes into an InstanceNorm++ next (the Winograd kernel's statistics epilogue then spares
         that normalisation its pass over the tensor; ignored by the other kernels).
+        thin_stats: the same request to the streaming first layer (ops.conv3x3_thin(want_stats=True); read on that route only).
         f16x2 family: the input's per-image maxima come with the tensor from its producer (ops.in_amax_for; `in_amax` overrides)
         and this layer's epilogue accumulates the maxima of what it stores for ITS consumer -- every convolution of the network
         then runs with the dynamic range (any fp32 input is in range) at no pass over any tensor.
@@ -146,6 +157,8 @@ class Conv2d(ops.PackedWeightMixin, nn.Module):
                                        in_amax=getattr(coef, "_ipdm_amax_bound", None) if dyn else None, want_amax=produce,
                                        res_second=res_second, coef=coef, act=act)
         if route == ops.ROUTE_THIN:
+            if thin_stats:
+                return ops.conv3x3_thin(x, self.weight.data, bias, coef, want_stats=True)
             return ops.conv3x3_thin(x, self.weight.data, bias, coef)   # first / last layer: streaming kernels
         if route == ops.ROUTE_WINO_F32:
             return ops.conv2d_wino(x, self.packed_wino(), bias, residual, act_out=act_out, raw=raw,
@@ -270,10 +283,11 @@ class RCUBlock(nn.Module):
         self.n_stages = n_stages
         self.act = act
 
-    def forward(self, x, x_act=None, want_act=False, feeds_conv=True):
+    def forward(self, x, x_act=None, want_act=False, feeds_conv=True, want_stats=False):
         """reference: per block  residual = x; (x = act(x); x = conv(x)) x n_stages; x += residual.
         Inner stages only ever feed the next activation, so they write just the activated copy.
-        feeds_conv=False: the block's RESULT is normalised next (the network's last RCU): no maxima for it."""
+        feeds_conv=False: the block's RESULT is normalised next (the network's last RCU): no maxima for it.
+        want_stats: ... and its last convolution leaves the statistics partials for that normalisation."""
         code = _act_code(self.act)
         for i in range(self.n_blocks):
             residual = x
@@ -284,6 +298,8 @@ class RCUBlock(nn.Module):
                     _, a = conv(a, act_out=code, raw=False)
                 elif i < self.n_blocks - 1 or want_act:
                     x, x_act = conv(a, residual=residual, act_out=code)
+                elif want_stats:
+                    x, x_act = conv(a, residual=residual, feeds_conv=feeds_conv, want_stats=True), None
                 else:
                     x, x_act = conv(a, residual=residual, feeds_conv=feeds_conv), None
         return x, x_act
@@ -332,10 +348,11 @@ class RefineBlock(nn.Module):
         self.crp = CRPBlock(features, 2, act, maxpool=maxpool, spec_norm=spec_norm, ndim=ndim)
         self.act = act
 
-    def forward(self, xs, output_shape, xs_act=None, want_act=False, feeds_conv=None):
+    def forward(self, xs, output_shape, xs_act=None, want_act=False, feeds_conv=None, want_stats=False):
         """xs: raw inputs; xs_act: their activated copies where a producer emitted them (else None entries).
         Returns the raw output, or (raw, activated) when want_act.  feeds_conv (default: want_act): a convolution reads the result
-        (another refine block, a temporal convolution) -- otherwise it is normalised next and carries no maxima."""
+        (another refine block, a temporal convolution) -- otherwise it is normalised next and carries no maxima.
+        want_stats (with want_act=False): the result carries its statistics partials for that normalisation."""
         assert isinstance(xs, (tuple, list))
         code = _act_code(self.act)
         xs_act = [None] * len(xs) if xs_act is None else xs_act
@@ -346,7 +363,8 @@ class RefineBlock(nn.Module):
         else:
             a = self.msf([h[0] for h in hs], output_shape, act_out=code)
             h, h_act = self.crp(None, a, want_act=True)
-        out, out_act = self.output_convs(h, h_act, want_act=want_act, feeds_conv=want_act if feeds_conv is None else feeds_conv)
+        out, out_act = self.output_convs(h, h_act, want_act=want_act, feeds_conv=want_act if feeds_conv is None else feeds_conv,
+                                         want_stats=want_stats and not want_act)
         return (out, out_act) if want_act else out
 
 

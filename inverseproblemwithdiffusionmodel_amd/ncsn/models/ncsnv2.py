@@ -5,7 +5,7 @@ import torch
 import torch.nn as nn
 
 from . import get_sigmas
-from .layers import ResidualBlock, RefineBlock, Conv2d, get_act, get_normalization
+from .layers import ResidualBlock, RefineBlock, Conv2d, get_act, get_normalization, InstanceNorm2dPlus
 from ... import ops
 
 
@@ -45,16 +45,23 @@ class _NCSNv2Base(nn.Module):
             key = (x.shape[0], x.shape[1], str(x.device))
             if key not in self._in_coef:
                 self._in_coef[key] = torch.tensor([0.5, 2.0, 0.0], device=x.device).repeat(x.shape[0], x.shape[1], 1)
-            return self.begin_conv(x, self._in_coef[key])
-        return self.begin_conv(x)
+            return self.begin_conv(x, self._in_coef[key], thin_stats=ops.THIN_STATS)
+        return self.begin_conv(x, thin_stats=ops.THIN_STATS)     # (res1 normalises the result first)
 
     def _end(self, output, x, y):
-        output = self.end_conv(self.normalizer(output, self.act.code))
+        code = self.act.code
+        if isinstance(self.normalizer, InstanceNorm2dPlus) and self.end_conv.streams_norm_input(output, code):
+            output = self.end_conv.stream_norm_input(output, self.normalizer.coef(output), code)     # one pass over `output`
+        else:
+            output = self.end_conv(self.normalizer(output, code))
         sig = self.sigmas if self.sigmas.dtype == torch.float32 else self.sigmas.to(torch.float32)
         return ops.div_sigma(output, sig, y.to(torch.int64))
 
     @staticmethod
     def _refine(block, pairs, shape, want_act=True):
+        """want_act=False: the network's last block, which the normaliser reads next (statistics partials: IPDM_END_STATS)"""
+        if not want_act and ops.END_STATS:
+            return block([p[0] for p in pairs], shape, [p[1] for p in pairs], want_act=False, want_stats=True)
         return block([p[0] for p in pairs], shape, [p[1] for p in pairs], want_act=want_act)
 
 

@@ -1774,9 +1774,52 @@ def conv3x3_thin_ok(Cin, Cout, H, W, x=None):
     return USE_THIN_CONV and bool(_lib.lib.ipdm_conv3x3_thin_supported(int(Cin), int(Cout), int(H), int(W)))
 
 
-def conv3x3_thin(x, weight, bias=None, coef=None):
+# the streaming layers leave nothing for a second pass (IPDM_THIN_STATS, IPDM_THIN_FIN; 0: the separate passes, launch for launch):
+# the first layer hands its statistics partials to the InstanceNorm++ that reads it next, as the Winograd epilogues do ...
+THIN_STATS = os.environ.get("IPDM_THIN_STATS", "1") != "0"
+# ... and the last layer takes act(InstanceNorm++(x)) as (raw x, coefficients): no normalised tensor written and read back
+THIN_FIN = os.environ.get("IPDM_THIN_FIN", "1") != "0"
+# the network's last refine block is normalised next: its last convolution takes the statistics epilogue (IPDM_END_STATS)
+END_STATS = os.environ.get("IPDM_END_STATS", "1") != "0"
+
+
+def conv3x3_thin_stats_ok(Cin, Cout, H, W, x=None):
+    """True where conv3x3_thin(want_stats=True) writes statistics partials (the few-input-channel form, IPDM_THIN_STATS)"""
+    return (THIN_STATS and USE_STATS_EPILOGUE and conv3x3_thin_ok(Cin, Cout, H, W, x)
+            and int(_lib.lib.ipdm_conv3x3_thin_stats_partials(int(Cin), int(Cout), int(H), int(W))) > 0)
+
+
+def conv3x3_fewout_fin_ok(Cin, Cout, H, W, x, act=ACT_ELU):
+    """True where conv3x3_fewout_fin takes the layer: a thin output side, ELU, 16-byte rows (IPDM_THIN_FIN; IPDM_THIN_CONV=0
+    switches every streaming layer off, this one included)"""
+    return (THIN_FIN and act == ACT_ELU and x.dim() == 4 and Cout <= 3 < Cin and conv3x3_thin_ok(Cin, Cout, H, W, x)
+            and bool(_lib.lib.ipdm_conv3x3_fewout_fin_supported(int(Cin), int(Cout), int(H), int(W))))
+
+
+def conv3x3_fewout_fin(x, weight, bias, coef, act=ACT_ELU):
+    """last layer of a score network on act(InstanceNorm++(x)): x [B,Cin,H,W] RAW, coef [B,Cin,3] from instnorm_plus_coef,
+    weight [Cout,Cin,3,3], Cout <= 3.  The bits of conv3x3_thin(affine_act(x, coef, act), weight, bias) in one pass over x.
+    Raises IpdmUnsupported outside conv3x3_fewout_fin_ok()."""
+    x = _gpu(x, torch.float32, "x")
+    weight = _gpu(weight, torch.float32, "weight")
+    coef = _gpu(coef, torch.float32, "coef")
+    B, Cin, H, W = x.shape
+    Cout = weight.shape[0]
+    if tuple(weight.shape) != (Cout, Cin, 3, 3):
+        raise ValueError(f"conv3x3_fewout_fin: weight {tuple(weight.shape)} does not match input channels {Cin}")
+    if tuple(coef.shape) != (B, Cin, 3):
+        raise ValueError(f"conv3x3_fewout_fin: coef {tuple(coef.shape)} != {(B, Cin, 3)}")
+    out = torch.empty((B, Cout, H, W), dtype=torch.float32, device=x.device)
+    e0 = _trace_open()
+    call("ipdm_conv3x3_fewout_fin_f32", _ptr(x), _ptr(weight), _ptr(bias), _ptr(coef), act, _ptr(out), B, Cin, Cout, H, W, _stream())
+    return _conv_done(e0, out, None, B=B, Cin=Cin, Cout=Cout, H=H, W=W, k=3, dil=1, res=False, thin=True, fin=True)
+
+
+def conv3x3_thin(x, weight, bias=None, coef=None, want_stats=False):
     """first / last layer of a score network: x [B,Cin,H,W], weight [Cout,Cin,3,3] (the reference's layout), Cin <= 3 or
     Cout <= 3; coef [B,Cin,3]: input affine (x - c0) * c1 + c2 inside the image (Cin <= 3 form).
+    want_stats: the result feeds an InstanceNorm++ -- where conv3x3_thin_stats_ok(), the statistics partials [B, Cout, P, 3] ride
+    on it as `_ipdm_partials` (as conv2d_wino_bx3(want_stats=True)); the stored bits do not change.
     Raises IpdmUnsupported for a shape outside conv3x3_thin_ok() and for an x that is not 16-byte aligned."""
     x = _gpu(x, torch.float32, "x")
     weight = _gpu(weight, torch.float32, "weight")
@@ -1790,6 +1833,13 @@ def conv3x3_thin(x, weight, bias=None, coef=None):
         coef = _gpu(coef, torch.float32, "coef")
         if tuple(coef.shape) != (B, Cin, 3):
             raise ValueError(f"conv3x3_thin: coef {tuple(coef.shape)} != {(B, Cin, 3)}")
+    if want_stats and conv3x3_thin_stats_ok(Cin, Cout, H, W, x):
+        P = int(_lib.lib.ipdm_conv3x3_thin_stats_partials(Cin, Cout, H, W))
+        part = torch.empty((B, Cout, P, 3), dtype=torch.float32, device=x.device)
+        call("ipdm_conv3x3_thin_stats_f32", _ptr(x), _ptr(weight), _ptr(bias), _ptr(coef), _ptr(out), _ptr(part), B, Cin, Cout, H, W,
+             _stream())
+        out._ipdm_partials = (part, (out._version, out.data_ptr()))
+        return _conv_done(e0, out, None, B=B, Cin=Cin, Cout=Cout, H=H, W=W, k=3, dil=1, res=False, thin=True, stats=True)
     call("ipdm_conv3x3_thin_f32", _ptr(x), _ptr(weight), _ptr(bias), _ptr(coef), _ptr(out), B, Cin, Cout, H, W, _stream())
     return _conv_done(e0, out, None, B=B, Cin=Cin, Cout=Cout, H=H, W=W, k=3, dil=1, res=False, thin=True)
 
