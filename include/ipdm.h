@@ -444,6 +444,48 @@ int ipdm_ald_singlecoil_step_f32(float* x_re, float* x_im, const float* g_re, co
                                  float coef, int mode, float* workspace /* as ipdm_singlecoil_prox_f32 */, int B, int H,
                                  int W, void* stream);
 
+/* Predictor-corrector sampling with data consistency (sde/inverse.py): one schedule record PER SAMPLE.
+ *
+ * ipdm_pc_langevin_coef_f32 forms the Langevin corrector's step of each complex sample on the device (score_sde's
+ * LangevinCorrector, sampling.py, with its two batch means replaced by per-sample norms, so that a sample does not
+ * depend on its batch or on sharding).  For sample b of the planar score g_re / g_im [B][sample_elems]:
+ *   ng = sqrt(sum g_re^2 + sum g_im^2),  nz = the same norm of the noise z the following tail applies to sample b:
+ *        noise_re / noise_im when given, else the Philox normals of (seed, sample_offset + b, step_id, plane 0 / 1),
+ *        regenerated here (no noise tensor exists in memory)
+ *   sample_sched[b] = { step = 2 alpha (snr nz / ng)^2, noise_scale = sqrt(2 step), coef, sigma, step_id, seg_scale = 0 }
+ * coef, sigma and step_id come from *dev_sched when it is non-NULL (a shared device record), else from the arguments.
+ * Sums are accumulated in double in a fixed order without atomics (bit-reproducible; independent of B), the
+ * coefficients formed in double and rounded once.  ng == 0: step = noise_scale = 0 (the tail then only applies data
+ * consistency); a NaN or infinite norm: NaN in that sample's record only.
+ * work: ipdm_pc_langevin_coef_workspace_bytes(B) bytes of device memory.  B <= 65535, 0 < sample_elems <= 2^31. */
+int64_t ipdm_pc_langevin_coef_workspace_bytes(int B);
+int ipdm_pc_langevin_coef_f32(const float* g_re, const float* g_im, const float* noise_re, const float* noise_im,
+                              double snr, double alpha, uint64_t seed, int64_t sample_offset, int64_t step_id,
+                              const ipdm_sched_t* dev_sched, float coef, float sigma, ipdm_sched_t* sample_sched,
+                              double* work, int B, int64_t sample_elems, void* stream);
+/* The fused tails ipdm_ald_sense_step_sets_f32, ipdm_ald_sense_cg_step_sets_f32 and ipdm_ald_singlecoil_step_f32 with
+ * sched_stride records between consecutive samples: 0 is those entry points (one shared record or the host scalars;
+ * the same kernels, the same bits), 1 makes sample b read dev_sched[b] (step, noise_scale, coef and step_id; B
+ * records, dev_sched non-NULL).  Any other stride: IPDM_EINVAL.  Every other argument as in those entry points. */
+int ipdm_pc_sense_step_f32(float* x_re, float* x_im, const float* g_re, const float* g_im,
+                           const float* noise_re, const float* noise_im,
+                           float step, float noise_scale, uint64_t seed, int64_t sample_offset, int64_t step_id,
+                           const ipdm_sched_t* dev_sched, int sched_stride, const float* y, const float* sens,
+                           int sens_complex, int sens_sets, const uint8_t* mask, int mask_t, float coef, float* work, int B,
+                           int n_coils, int H, int W, void* stream);
+int ipdm_pc_sense_cg_step_f32(float* x_re, float* x_im, const float* g_re, const float* g_im,
+                              const float* noise_re, const float* noise_im,
+                              float step, float noise_scale, uint64_t seed, int64_t sample_offset, int64_t step_id,
+                              const ipdm_sched_t* dev_sched, int sched_stride, const float* y, const float* sens,
+                              int sens_complex, int sens_sets, const uint8_t* mask, int mask_t, float coef, float* work,
+                              const float* ahy, int max_iter, float tol, int32_t* iters_out, int B, int n_coils, int H,
+                              int W, void* stream);
+int ipdm_pc_singlecoil_step_f32(float* x_re, float* x_im, const float* g_re, const float* g_im,
+                                const float* noise_re, const float* noise_im,
+                                float step, float noise_scale, uint64_t seed, int64_t sample_offset, int64_t step_id,
+                                const ipdm_sched_t* dev_sched, int sched_stride, const float* y, const uint8_t* mask,
+                                int mask_t, float coef, int mode, float* workspace, int B, int H, int W, void* stream);
+
 /* Langevin update alone (ALD_optimizers.py:117): x += step*g + noise_scale*noise ; noise NULL -> Philox. */
 int ipdm_langevin_step_f32(float* x, const float* g, const float* noise, float step, float noise_scale,
                            uint64_t seed, int64_t sample_offset, int64_t step_id, const ipdm_sched_t* dev_sched,

@@ -96,6 +96,17 @@ SIGNATURES = {
     "ipdm_singlecoil_prox_f32": [P, P, P, P, c_int, c_float, c_int, P, P, P, c_int, c_int, c_int, P],
     "ipdm_ald_singlecoil_step_f32": [P, P, P, P, P, P, c_float, c_float, c_uint64, c_int64, c_int64, P,
                                      P, P, c_int, c_float, c_int, P, c_int, c_int, c_int, P],
+    # one schedule record per sample: sched_stride directly after dev_sched
+    "ipdm_pc_langevin_coef_workspace_bytes": [c_int],
+    "ipdm_pc_langevin_coef_f32": [P, P, P, P, c_double, c_double, c_uint64, c_int64, c_int64, P, c_float, c_float, P, P,
+                                  c_int, c_int64, P],
+    "ipdm_pc_sense_step_f32": [P, P, P, P, P, P, c_float, c_float, c_uint64, c_int64, c_int64, P, c_int,
+                               P, P, c_int, c_int, P, c_int, c_float, P, c_int, c_int, c_int, c_int, P],
+    "ipdm_pc_sense_cg_step_f32": [P, P, P, P, P, P, c_float, c_float, c_uint64, c_int64, c_int64, P, c_int,
+                                  P, P, c_int, c_int, P, c_int, c_float, P, P, c_int, c_float, P,
+                                  c_int, c_int, c_int, c_int, P],
+    "ipdm_pc_singlecoil_step_f32": [P, P, P, P, P, P, c_float, c_float, c_uint64, c_int64, c_int64, P, c_int,
+                                    P, P, c_int, c_float, c_int, P, c_int, c_int, c_int, P],
     "ipdm_langevin_step_f32": [P, P, P, c_float, c_float, c_uint64, c_int64, c_int64, P, c_int64, c_int64, P],
     "ipdm_philox_normal_f32": [P, c_uint64, c_int64, c_int64, c_int, c_int64, c_int64, P],
     "ipdm_philox_block_host": [c_uint64, c_int64, c_int64, c_int, ctypes.c_uint32, P],
@@ -196,6 +207,7 @@ SIGNATURES = {
     "ipdm_ssim_f32": [P, P, P, c_int, c_int, c_int, c_int, ctypes.c_double, P],
 }
 _RESTYPES = {"ipdm_build_arch": c_char_p, "ipdm_debug_lds_optin_count": c_int64, "ipdm_fft2c_workspace_bytes": c_int64, "ipdm_sense_workspace_bytes": c_int64, "ipdm_sense_cg_workspace_bytes": c_int64,
+             "ipdm_pc_langevin_coef_workspace_bytes": c_int64,
              "ipdm_conv_bx3_weight_bytes": c_int64,
              "ipdm_conv_wino_bx3_weight_bytes": c_int64, "ipdm_conv_hx2_weight_bytes": c_int64,
              "ipdm_conv_wino_hx2_weight_bytes": c_int64, "ipdm_conv_wino1d_weight_bytes": c_int64, "ipdm_conv_wino1d_weight_bytes3d": c_int64,

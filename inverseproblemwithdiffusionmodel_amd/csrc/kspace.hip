@@ -177,9 +177,9 @@ __global__ __launch_bounds__(FFT_THREADS) void ald_sense_step_kernel(float* x_re
   const float2* __restrict__ y = pb.y;
   const uint8_t* __restrict__ mask = pb.mask;
   FFT_LDS_SETUP(H, W, MIXED)
-  coef = sched_override(lg, coef);
   const int HW = H * W;
   const int b = blockIdx.x;
+  coef = sched_override(lg, b, coef);
   const SensT* __restrict__ sens = sens_at(pb.sens, pb.sens_sets, b, (size_t)n_coils * HW);
   const float scale = rsqrtf((float)HW);
   float* xr = x_re + (size_t)b * HW;
@@ -249,7 +249,7 @@ __global__ __launch_bounds__(FFT_THREADS) void sense_normal_coil_kernel(const fl
     if (state[b].frozen) return;
   } else {
     // the tail's combine pass then only applies the Langevin update; the CG init pass leaves x = z and freezes the sample
-    if (sched_override(lg, coef) == 0.f) return;
+    if (sched_override(lg, b, coef) == 0.f) return;
   }
   FFT_LDS_SETUP(H, W, MIXED)
   const int HW = H * W;
@@ -291,8 +291,8 @@ __global__ __launch_bounds__(FFT_THREADS) void sense_normal_coil_kernel(const fl
 template <bool LANGEVIN>
 __global__ __launch_bounds__(256) void ald_sense_combine_kernel(float* x_re, float* x_im, LangevinArgs lg, float coef,
                                                                 const float2* __restrict__ work, int n_coils, int HW) {
-  coef = sched_override(lg, coef);
   const int b = blockIdx.y;
+  coef = sched_override(lg, b, coef);
   float* xr = x_re + (size_t)b * HW;
   float* xi = x_im + (size_t)b * HW;
   for (int e = blockIdx.x * 256 + threadIdx.x; e < HW; e += gridDim.x * 256) {
@@ -321,9 +321,9 @@ __global__ __launch_bounds__(FFT_THREADS) void ald_singlecoil_step_kernel(float*
   const float2* __restrict__ y = pb.y;
   const uint8_t* __restrict__ mask = pb.mask;
   FFT_LDS_SETUP(H, W, MIXED)
-  coef = sched_override(lg, coef);
   const int HW = H * W;
   const int b = blockIdx.x;
+  coef = sched_override(lg, b, coef);
   const float scale = rsqrtf((float)HW);
   float* xr = x_re + (size_t)b * HW;
   float* xi = x_im + (size_t)b * HW;
@@ -733,6 +733,34 @@ extern "C" int ipdm_ald_singlecoil_step_f32(float* x_re, float* x_im, const floa
   const LangevinArgs lg{g_re, g_im, noise_re, noise_im, step, noise_scale, seed, sample_offset, step_id, dev_sched};
   const SenseProblem<float> pb = sense_problem<float>(y, nullptr, mask, mask_t, B, 1, H, W);
   IPDM_REQUIRE(dims_ok(pb) && mode >= 0 && mode <= 2);
+  if (B == 0) return IPDM_OK;
+  IPDM_REQUIRE(step_ptrs_ok(x_re, x_im, lg, pb));
+  return singlecoil_step(x_re, x_im, lg, pb, coef, mode, workspace, ipdm_stream(stream));
+}
+
+// ---- one schedule record per sample (the predictor-corrector samplers: a step per sample, pc_coef.hip) ----------------------
+// The `_sets_` / single-coil tails above with sched_stride records between consecutive samples: 0 is their shared record
+// (same kernels, same bits), 1 lets sample b read dev_sched[b].
+extern "C" int ipdm_pc_sense_step_f32(float* x_re, float* x_im, const float* g_re, const float* g_im, const float* noise_re,
+                                      const float* noise_im, float step, float noise_scale, uint64_t seed,
+                                      int64_t sample_offset, int64_t step_id, const ipdm_sched_t* dev_sched, int sched_stride,
+                                      const float* y, const float* sens, int sens_complex, int sens_sets, const uint8_t* mask,
+                                      int mask_t, float coef, float* work, int B, int n_coils, int H, int W, void* stream) {
+  IPDM_REQUIRE(sens && sens_sets >= 1 && sched_stride_ok(dev_sched, sched_stride));
+  const LangevinArgs lg{g_re, g_im, noise_re, noise_im, step, noise_scale, seed, sample_offset, step_id, dev_sched, sched_stride};
+  return sens_dispatch(sens_complex, y, sens, mask, mask_t, B, n_coils, H, W, sens_sets,
+                       [&](const auto& pb) { return ald_sense_step_impl(x_re, x_im, lg, pb, coef, work, stream); });
+}
+
+extern "C" int ipdm_pc_singlecoil_step_f32(float* x_re, float* x_im, const float* g_re, const float* g_im,
+                                           const float* noise_re, const float* noise_im, float step, float noise_scale,
+                                           uint64_t seed, int64_t sample_offset, int64_t step_id,
+                                           const ipdm_sched_t* dev_sched, int sched_stride, const float* y, const uint8_t* mask,
+                                           int mask_t, float coef, int mode, float* workspace, int B, int H, int W,
+                                           void* stream) {
+  const LangevinArgs lg{g_re, g_im, noise_re, noise_im, step, noise_scale, seed, sample_offset, step_id, dev_sched, sched_stride};
+  const SenseProblem<float> pb = sense_problem<float>(y, nullptr, mask, mask_t, B, 1, H, W);
+  IPDM_REQUIRE(dims_ok(pb) && mode >= 0 && mode <= 2 && sched_stride_ok(dev_sched, sched_stride));
   if (B == 0) return IPDM_OK;
   IPDM_REQUIRE(step_ptrs_ok(x_re, x_im, lg, pb));
   return singlecoil_step(x_re, x_im, lg, pb, coef, mode, workspace, ipdm_stream(stream));

@@ -58,8 +58,8 @@ __global__ __launch_bounds__(FFT_THREADS) void cg_init_kernel(float* x_re, float
                                                               const float2* __restrict__ ahy, float2* r, float2* p,
                                                               CgState* state, int32_t* iters_out, int HW) {
   __shared__ float red[2][FFT_THREADS / 64];
-  a = sched_override(lg, a);
   const int b = blockIdx.x;
+  a = sched_override(lg, b, a);
   float* xr = x_re + (size_t)b * HW;
   float* xi = x_im + (size_t)b * HW;
   const float2* pl = planes + (size_t)b * n_planes * HW;
@@ -103,14 +103,14 @@ __global__ __launch_bounds__(FFT_THREADS) void cg_init_kernel(float* x_re, float
 // REG: the image fits FFT_EPT elements per thread and q stays in registers; otherwise q is formed twice from the planes.
 template <bool REG>
 __global__ __launch_bounds__(FFT_THREADS) void cg_update_kernel(float* x_re, float* x_im, const ipdm_sched_t* __restrict__ sched,
-                                                                float a, float tol, const float2* __restrict__ planes,
+                                                                int sched_stride, float a, float tol, const float2* __restrict__ planes,
                                                                 int n_planes, float2* r, float2* p, CgState* state,
                                                                 int32_t* iters_out, int HW) {
   __shared__ float red[2][FFT_THREADS / 64];
   const int b = blockIdx.x;
   const CgState s = state[b];
   if (s.frozen) return;                                        // uniform over the workgroup
-  a = sched_coef(sched, a);
+  a = sched_coef(sched, sched_stride, b, a);
   float* xr = x_re + (size_t)b * HW;
   float* xi = x_im + (size_t)b * HW;
   const float2* pl = planes + (size_t)b * n_planes * HW;
@@ -233,13 +233,13 @@ static int cg_solve(float* x_re, float* x_im, const LangevinArgs& lg, const Sens
       // (the strip passes have no per-sample exit: a frozen sample's planes are computed and ignored)
       rc = ipdm_kspace_large::normal_op(w.p, nullptr, nullptr, no_y, w.nout, w.planes, st);
       if (rc) return rc;
-      hipLaunchKernelGGL(cg_update_kernel<false>, dim3(B), dim3(FFT_THREADS), 0, st, x_re, x_im, lg.sched, a, tol, planes,
-                         n_planes, w.r, w.p, w.state, iters_out, HW);
+      hipLaunchKernelGGL(cg_update_kernel<false>, dim3(B), dim3(FFT_THREADS), 0, st, x_re, x_im, lg.sched, lg.sched_stride, a, tol,
+                         planes, n_planes, w.r, w.p, w.state, iters_out, HW);
     } else {
       rc = launch_normal_coils(0, x_re, x_im, lg, a, w.p, w.state, no_y, w.planes, st);
       if (rc) return rc;
-      hipLaunchKernelGGL(cg_update_kernel<true>, dim3(B), dim3(FFT_THREADS), 0, st, x_re, x_im, lg.sched, a, tol, planes,
-                         n_planes, w.r, w.p, w.state, iters_out, HW);
+      hipLaunchKernelGGL(cg_update_kernel<true>, dim3(B), dim3(FFT_THREADS), 0, st, x_re, x_im, lg.sched, lg.sched_stride, a, tol,
+                         planes, n_planes, w.r, w.p, w.state, iters_out, HW);
     }
     rc = ipdm_launch_status();
     if (rc) return rc;
@@ -340,6 +340,21 @@ extern "C" int ipdm_ald_sense_cg_step_sets_f32(float* x_re, float* x_im, const f
                                                int B, int n_coils, int H, int W, void* stream) {
   IPDM_REQUIRE(sens && sens_sets >= 1);
   const LangevinArgs lg{g_re, g_im, noise_re, noise_im, step, noise_scale, seed, sample_offset, step_id, dev_sched};
+  return sens_dispatch(sens_complex, y, sens, mask, mask_t, B, n_coils, H, W, sens_sets, [&](const auto& pb) {
+    return cg_step_impl(x_re, x_im, lg, pb, coef, work, ahy, max_iter, tol, iters_out, stream);
+  });
+}
+
+// one schedule record per sample: sched_stride as ipdm_pc_sense_step_f32 (kspace.hip); 0 is the entry point above
+extern "C" int ipdm_pc_sense_cg_step_f32(float* x_re, float* x_im, const float* g_re, const float* g_im,
+                                         const float* noise_re, const float* noise_im, float step, float noise_scale,
+                                         uint64_t seed, int64_t sample_offset, int64_t step_id, const ipdm_sched_t* dev_sched,
+                                         int sched_stride, const float* y, const float* sens, int sens_complex, int sens_sets,
+                                         const uint8_t* mask, int mask_t, float coef, float* work, const float* ahy,
+                                         int max_iter, float tol, int32_t* iters_out, int B, int n_coils, int H, int W,
+                                         void* stream) {
+  IPDM_REQUIRE(sens && sens_sets >= 1 && sched_stride_ok(dev_sched, sched_stride));
+  const LangevinArgs lg{g_re, g_im, noise_re, noise_im, step, noise_scale, seed, sample_offset, step_id, dev_sched, sched_stride};
   return sens_dispatch(sens_complex, y, sens, mask, mask_t, B, n_coils, H, W, sens_sets, [&](const auto& pb) {
     return cg_step_impl(x_re, x_im, lg, pb, coef, work, ahy, max_iter, tol, iters_out, stream);
   });

@@ -275,6 +275,7 @@ struct LangevinArgs {
   uint64_t seed;
   int64_t sample_offset, step_id;
   const ipdm_sched_t* sched;       // device schedule: overrides step / noise_scale / step_id and the coefficient
+  int sched_stride;                // records between consecutive samples: 0 one shared record, 1 sample b reads sched[b]
 };
 constexpr LangevinArgs NO_LANGEVIN{};
 
@@ -309,18 +310,22 @@ __device__ __forceinline__ const SensT* sens_at(const SensT* sens, int sens_sets
   return (sens_sets == 1 || !sens) ? sens : sens + (size_t)(b % sens_sets) * set_elems;
 }
 
-// The device schedule, the only place it is read: the coefficient alone, or with the Langevin scalars as well.
-__device__ __forceinline__ float sched_coef(const ipdm_sched_t* __restrict__ sched, float coef) {
-  return sched ? sched->coef : coef;
+// The device schedule, the only place it is read: the coefficient alone, or with the Langevin scalars as well.  Sample b
+// reads record b * stride (stride 0: one record shared by the batch).  b is a block index in every kernel, so the record's
+// address is uniform over the workgroup and the reads stay scalar loads.
+__device__ __forceinline__ float sched_coef(const ipdm_sched_t* __restrict__ sched, int stride, int b, float coef) {
+  return sched ? sched[(size_t)b * stride].coef : coef;
 }
-__device__ __forceinline__ float sched_override(LangevinArgs& lg, float coef) {
+__device__ __forceinline__ float sched_override(LangevinArgs& lg, int b, float coef) {
   const ipdm_sched_t* __restrict__ sched = lg.sched;
   if (sched) {
+    sched += (size_t)b * lg.sched_stride;
     lg.step = sched->step;
     lg.noise_scale = sched->noise_scale;
     lg.step_id = sched->step_id;
+    return sched->coef;
   }
-  return sched_coef(sched, coef);
+  return coef;
 }
 
 // ---- the Langevin update, the only place it is written ---------------------------------------------------------------------
@@ -402,6 +407,9 @@ template <typename SensT>
 static inline bool step_ptrs_ok(const float* x_re, const float* x_im, const LangevinArgs& lg, const SenseProblem<SensT>& pb) {
   return x_re && x_im && lg.g_re && lg.g_im && pb.y && pb.mask && (lg.n_re == nullptr) == (lg.n_im == nullptr);
 }
+
+// a record per sample needs records to read
+static inline bool sched_stride_ok(const ipdm_sched_t* sched, int stride) { return stride == 0 || (stride == 1 && sched); }
 
 // out-of-place entry points: z -> out, plane by plane, unless the caller passed the same plane
 static inline int copy_planes(float* out_re, float* out_im, const float* z_re, const float* z_im, size_t n, hipStream_t st) {

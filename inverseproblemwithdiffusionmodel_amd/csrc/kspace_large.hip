@@ -183,6 +183,7 @@ struct ColsProx {
   int mask_t, mode;
   float scale, coef_host;
   const ipdm_sched_t* sched;       // device schedule: overrides coef_host (modes 1, 2 use it in k-space)
+  int sched_stride;                // sched_coef()
   __device__ __forceinline__ float2 load(int b, int coil, int r, int c) const { return tmp[g.at(coil, b, r, c)]; }
   __device__ __forceinline__ void store(int b, int coil, int r, int c, float2 v) const { tmp[g.at(coil, b, r, c)] = v; }
   // Called by every thread of the workgroup, before any divergence; the answer is the same in all of them.
@@ -211,7 +212,7 @@ struct ColsProx {
     const float2 yy = y ? y[g.at(coil, b, r, c)] : make_float2(0.f, 0.f);
     const float sg = sign_rc(r, c);
     if (mode <= 0) return masked_residual(m, v, sg, yy);
-    const float coef = sched_coef(sched, coef_host);
+    const float coef = sched_coef(sched, sched_stride, b, coef_host);
     if (mode == 1) {
       const float inv = m ? 1.f / (1.f + coef) : 1.f;
       return make_float2((v.x + coef * sg * yy.x) * inv, (v.y + coef * sg * yy.y) * inv);
@@ -231,13 +232,13 @@ template <int FIN, typename SensT, bool MIXED>
 __global__ __launch_bounds__(FFT_THREADS) void rows_inv_accum_kernel(const float2* __restrict__ tmp,
                                                                      const SensT* __restrict__ sens_all, int sens_sets,
                                                                      float2* out_c, float* out_f, float* x_re, float* x_im,
-                                                                     const ipdm_sched_t* __restrict__ sched, float coef,
-                                                                     int B, int n_coils, int H, int W) {
+                                                                     const ipdm_sched_t* __restrict__ sched, int sched_stride,
+                                                                     float coef, int B, int n_coils, int H, int W) {
   STRIP_LDS_SETUP(W)
-  coef = sched_coef(sched, coef);
   const ImgGeo g{B, H, W};
   const int RS = strip_lines<MIXED>(H, W);
   const int r0 = blockIdx.x * RS, b = blockIdx.y;
+  coef = sched_coef(sched, sched_stride, b, coef);
   const SensT* __restrict__ sens = sens_at(sens_all, sens_sets, b, (size_t)n_coils * H * W);
   const int n = RS * W;
   const float scale = rsqrtf((float)H * (float)W);
@@ -296,12 +297,12 @@ __global__ __launch_bounds__(FFT_THREADS) void rows_inv_accum_kernel(const float
 // Langevin update of both planes in place, a quad of elements per thread: the update and the Philox keying are
 // langevin_update / langevin_quad of kspace_fft.h, as in the fused 128x128 kernels
 __global__ __launch_bounds__(256) void langevin_planes_kernel(float* x_re, float* x_im, LangevinArgs lg, int HW) {
-  (void)sched_override(lg, 0.f);                               // the Langevin scalars only: no coefficient here
   const float* __restrict__ g_re = lg.g_re;
   const float* __restrict__ g_im = lg.g_im;
   const float* __restrict__ n_re = lg.n_re;
   const float* __restrict__ n_im = lg.n_im;
   const int b = blockIdx.y;
+  (void)sched_override(lg, b, 0.f);                            // the Langevin scalars only: no coefficient here
   const int quads = HW / 4;                                    // HW is a multiple of 4 (of 16, for every served size)
   // float4 access only where all the caller's planes sit on 16-byte boundaries; otherwise element by element (same
   // arithmetic, same Philox quad per four elements)
@@ -368,7 +369,7 @@ static int launch_cols(const F& f, int B, int coils, int H, int W, int inverse, 
 // tmp: pb.n_coils * pb.B column-transformed images; the coil sum weighted by pb.sens (NULL: unweighted)
 template <int FIN, typename SensT>
 static int launch_accum(const float2* tmp, const SenseProblem<SensT>& pb, float2* out_c, float* out_f, float* x_re, float* x_im,
-                        const ipdm_sched_t* sched, float coef, hipStream_t s) {
+                        const ipdm_sched_t* sched, int sched_stride, float coef, hipStream_t s) {
   const size_t lds = strip_lds_bytes(pb.W);
   const int RS = strip_lines(pb.H, pb.W);
   return fft_dispatch(fft_mixed(pb.H, pb.W), [&](auto mixed) {
@@ -376,7 +377,7 @@ static int launch_accum(const float2* tmp, const SenseProblem<SensT>& pb, float2
     int rc = ipdm_lds_optin((rows_inv_accum_kernel<FIN, SensT, MIXED>), lds);
     if (rc) return rc;
     hipLaunchKernelGGL((rows_inv_accum_kernel<FIN, SensT, MIXED>), dim3(pb.H / RS, pb.B), dim3(FFT_THREADS), lds, s, tmp, pb.sens,
-                       pb.sens_sets, out_c, out_f, x_re, x_im, sched, coef, pb.B, pb.n_coils, pb.H, pb.W);
+                       pb.sens_sets, out_c, out_f, x_re, x_im, sched, sched_stride, coef, pb.B, pb.n_coils, pb.H, pb.W);
     return ipdm_launch_status();
   });
 }
@@ -416,9 +417,9 @@ int sense_adjoint(const SenseProblem<SensT>& pb, int apply_mask, float2* x_out, 
   if (rc) return rc;
   if (ssos_out) {                                              // no maps in a sum of squares: one kernel for both SensT
     const SenseProblem<float> np{nullptr, nullptr, nullptr, 1, pb.B, pb.n_coils, pb.H, pb.W, 1};
-    return launch_accum<FIN_SSOS>(ws, np, nullptr, ssos_out, nullptr, nullptr, nullptr, 0.f, s);
+    return launch_accum<FIN_SSOS>(ws, np, nullptr, ssos_out, nullptr, nullptr, nullptr, 0, 0.f, s);
   }
-  return launch_accum<FIN_ADJOINT>(ws, pb, x_out, nullptr, nullptr, nullptr, nullptr, 0.f, s);
+  return launch_accum<FIN_ADJOINT>(ws, pb, x_out, nullptr, nullptr, nullptr, nullptr, 0, 0.f, s);
 }
 template int sense_adjoint(const SenseProblem<float>&, int, float2*, float*, float2*, hipStream_t);
 template int sense_adjoint(const SenseProblem<float2>&, int, float2*, float*, float2*, hipStream_t);
@@ -433,12 +434,13 @@ int langevin(float* x_re, float* x_im, const LangevinArgs& lg, int B, int H, int
 // forward rows, then columns forward + data-consistency operator + columns inverse, in place on ws[coil][b]
 template <typename SensT>
 static int rows_cols_prox(const float2* xc, const float* x_re, const float* x_im, const SenseProblem<SensT>& pb, int mode,
-                          float coef, const ipdm_sched_t* sched, float2* ws, hipStream_t s) {
+                          float coef, const ipdm_sched_t* sched, int sched_stride, float2* ws, hipStream_t s) {
   const ImgGeo g{pb.B, pb.H, pb.W};
   RowsFwd<SensT> rf{g, xc, x_re, x_im, pb.sens, ws, pb.sens_sets, pb.n_coils};
   int rc = launch_rows(rf, pb.B, pb.n_coils, pb.H, pb.W, 0, s);
   if (rc) return rc;
-  ColsProx cp{g, ws, pb.y, pb.mask, pb.mask_t, mode, 1.f / sqrtf((float)pb.H * (float)pb.W), coef, sched};
+  ColsProx cp{g, ws, pb.y, pb.mask, pb.mask_t, mode, 1.f / sqrtf((float)pb.H * (float)pb.W), coef, sched,
+              sched_stride};
   return launch_cols<ColsProx, true>(cp, pb.B, pb.n_coils, pb.H, pb.W, 0, s);
 }
 
@@ -446,9 +448,9 @@ static int rows_cols_prox(const float2* xc, const float* x_re, const float* x_im
 template <typename SensT>
 int normal_op(const float2* xc, const float* x_re, const float* x_im, const SenseProblem<SensT>& pb, float2* out, float2* ws,
               hipStream_t s) {
-  int rc = rows_cols_prox(xc, x_re, x_im, pb, 0, 0.f, nullptr, ws, s);
+  int rc = rows_cols_prox(xc, x_re, x_im, pb, 0, 0.f, nullptr, 0, ws, s);
   if (rc) return rc;
-  return launch_accum<FIN_ADJOINT>(ws, pb, out, nullptr, nullptr, nullptr, nullptr, 0.f, s);
+  return launch_accum<FIN_ADJOINT>(ws, pb, out, nullptr, nullptr, nullptr, nullptr, 0, 0.f, s);
 }
 template int normal_op(const float2*, const float*, const float*, const SenseProblem<float>&, float2*, float2*, hipStream_t);
 template int normal_op(const float2*, const float*, const float*, const SenseProblem<float2>&, float2*, float2*, hipStream_t);
@@ -462,10 +464,11 @@ int prox_step(float* x_re, float* x_im, const LangevinArgs& lg, const SenseProbl
   }
   // (the 128x128 kernel returns early when coef == 0; here the schedule value lives on the device, so the chain always
   //  runs -- with coef == 0 it adds exactly zero for the L2 modes)
-  int rc = rows_cols_prox(nullptr, x_re, x_im, pb, mode, coef, lg.sched, ws, s);
+  int rc = rows_cols_prox(nullptr, x_re, x_im, pb, mode, coef, lg.sched, lg.sched_stride, ws, s);
   if (rc) return rc;
-  if (mode <= 0) return launch_accum<FIN_L2>(ws, pb, nullptr, nullptr, x_re, x_im, lg.sched, coef, s);
-  return launch_accum<FIN_REPLACE>(ws, pb, nullptr, nullptr, x_re, x_im, nullptr, 0.f, s);
+  if (mode <= 0)
+    return launch_accum<FIN_L2>(ws, pb, nullptr, nullptr, x_re, x_im, lg.sched, lg.sched_stride, coef, s);
+  return launch_accum<FIN_REPLACE>(ws, pb, nullptr, nullptr, x_re, x_im, nullptr, 0, 0.f, s);
 }
 template int prox_step(float*, float*, const LangevinArgs&, const SenseProblem<float>&, float, int, float2*, hipStream_t);
 template int prox_step(float*, float*, const LangevinArgs&, const SenseProblem<float2>&, float, int, float2*, hipStream_t);

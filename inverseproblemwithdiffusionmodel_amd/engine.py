@@ -191,6 +191,16 @@ def build_problem(device, n_samples, R=40, H=128, W=128, num_sens=4, seed=0, sco
                      estimate_maps, kspace_scale, coil_matrix, eigval)
 
 
+def build_pc_sampler(prob, sde, **kw):
+    """predictor-corrector reconstruction with a VE-SDE score network (NCSN++) on a build_problem Namespace: its operator
+    and measurement -- measured k-space, estimated maps, compression and stacks included (row b = sample b // n_slices of
+    slice b % n_slices) -- with sde.inverse.get_pc_inverse_sampler's keywords -> sampler(model, ...) -> (x, nfe).
+    build_problem(scorenet=...) takes the NCSN++ (it is only stored), which spares building the NCSNv2 network."""
+    from .sde.inverse import get_pc_inverse_sampler
+    kw.setdefault("device", prob.measurement.device)
+    return get_pc_inverse_sampler(sde, prob.op, prob.measurement, **kw)
+
+
 def _check_maps(maps_method, maps_kwargs, n_coils, H, W, region):
     """host-side check of the estimator choice; while the region is unknown (a mask still to be simulated) the box test
     waits for it: 9 x 9 passes every ksize"""

@@ -1027,6 +1027,140 @@ def philox_normal(shape, device, seed=0, sample_offset=0, step_id=0, plane=0):
     return out
 
 
+# ---- predictor-corrector sampling with data consistency: one schedule record per sample (ipdm.h) ---------------------
+SCHED_BYTES = 32                                 # sizeof(ipdm_sched_t)
+
+
+def _sched_records(t, n, name, what):
+    """a device tensor holding at least n ipdm_sched_t records (the kernels read / write it through a raw pointer)"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"ipdm: {name} must be a GPU tensor (the HIP path has no CPU fallback)")
+    if not t.is_contiguous():
+        raise ValueError(f"{what}: {name} must be contiguous")
+    if t.numel() * t.element_size() < n * SCHED_BYTES:
+        raise ValueError(f"{what}: {name} holds {t.numel() * t.element_size()} bytes < {n} records of {SCHED_BYTES} bytes")
+    if t.data_ptr() % 8:
+        raise ValueError(f"{what}: {name} must be 8-byte aligned")
+    return t
+
+
+def pc_langevin_coef(g_re, g_im, sample_sched, snr, alpha=1.0, noise_re=None, noise_im=None, seed=0, sample_offset=0,
+                     step_id=0, dev_sched=None, coef=0.0, sigma=0.0, work=None):
+    """Langevin-corrector step of every complex sample, on the device (ipdm.h, ipdm_pc_langevin_coef_f32): record b of
+    sample_sched receives step = 2 alpha (snr |z_b| / |g_b|)^2 and noise_scale = sqrt(2 step), z the injected noise or
+    (noise None) the Philox normals the following per-sample tail will draw with the same (seed, sample_offset,
+    step_id); coef, sigma and step_id come from the device record dev_sched when given.  g_re / g_im: [B, ...]."""
+    for t, n in ((g_re, "g_re"), (g_im, "g_im")):
+        _inplace_operand(t, torch.float32, n)
+    if (noise_re is None) != (noise_im is None):
+        raise ValueError("pc_langevin_coef: noise_re and noise_im come together")
+    B = g_re.shape[0] if g_re.dim() else 0
+    elems = g_re.numel() // max(B, 1)
+    if g_im.numel() != g_re.numel() or B < 1 or elems < 1:
+        raise ValueError("pc_langevin_coef: g_re / g_im must be two equal non-empty [B, ...] planes")
+    if B > 65535:
+        raise ValueError(f"pc_langevin_coef: {B} samples exceed the 65535 of one launch")
+    for t, n in ((noise_re, "noise_re"), (noise_im, "noise_im")):
+        if t is not None:
+            _inplace_operand(t, torch.float32, n)
+            if t.numel() != g_re.numel():
+                raise ValueError(f"pc_langevin_coef: {n} does not match the score")
+    _sched_records(sample_sched, B, "sample_sched", "pc_langevin_coef")
+    if dev_sched is not None:
+        _sched_records(dev_sched, 1, "dev_sched", "pc_langevin_coef")
+    snr, alpha = float(snr), float(alpha)
+    if not (snr >= 0.0 and alpha >= 0.0 and snr < float("inf") and alpha < float("inf")):
+        raise ValueError(f"pc_langevin_coef: snr and alpha must be finite and >= 0, got {snr}, {alpha}")
+    need = _lib.lib.ipdm_pc_langevin_coef_workspace_bytes(B)
+    if work is None:
+        work = torch.empty(need // 8, dtype=torch.float64, device=g_re.device)
+    elif (not isinstance(work, torch.Tensor) or not work.is_cuda or work.dtype != torch.float64 or not work.is_contiguous()
+            or work.numel() * 8 < need):
+        raise ValueError(f"pc_langevin_coef: `work` must be a contiguous float64 GPU tensor of >= {need} bytes")
+    call("ipdm_pc_langevin_coef_f32", _ptr(g_re), _ptr(g_im), _ptr(noise_re), _ptr(noise_im), snr, alpha, int(seed),
+         int(sample_offset), int(step_id), _ptr(dev_sched), float(coef), float(sigma), _ptr(sample_sched), _ptr(work), B, elems,
+         _stream())
+    _written(sample_sched)
+    return sample_sched
+
+
+def pc_langevin_coef_workspace(B, device):
+    return torch.empty(_lib.lib.ipdm_pc_langevin_coef_workspace_bytes(B) // 8, dtype=torch.float64, device=device)
+
+
+def _pc_head(what, head, B, dev_sched, sample_sched):
+    """the leading C arguments of a per-sample tail: _fused_step's head with (records, stride) in place of dev_sched.
+    sample_sched given: sample b reads record b; otherwise dev_sched (or the host scalars) serves every sample"""
+    if sample_sched is not None:
+        if dev_sched is not None:
+            raise ValueError(f"{what}: pass sample_sched (a record per sample) or dev_sched (one shared record), not both")
+        _sched_records(sample_sched, B, "sample_sched", what)
+        return head[:-1] + (_ptr(sample_sched), 1)
+    if dev_sched is not None:
+        _sched_records(dev_sched, 1, "dev_sched", what)
+    return head + (0,)
+
+
+def _pc_sens_tail(sens):
+    return (int(sens.dtype == torch.complex64), sens.shape[0] if sens.dim() == 4 else 1)
+
+
+def pc_sense_step(x_re, x_im, g_re, g_im, y, sens_f32, mask_u8, work, step=0.0, noise_scale=0.0, coef=0.0, noise_re=None,
+                  noise_im=None, seed=0, sample_offset=0, step_id=0, dev_sched=None, sample_sched=None):
+    """ald_sense_step with a schedule record per sample: sample b takes step, noise_scale, coef and step_id from record b
+    of sample_sched (ipdm_sched_t[B] on the device, e.g. written by pc_langevin_coef).  sample_sched None: dev_sched or
+    the scalars, ald_sense_step's bits.  In place on x_re / x_im."""
+    name = "ipdm_pc_sense_step_f32"
+    fn, B, H, W, head = _fused_step("pc_sense_step", x_re, x_im, g_re, g_im, y, noise_re, noise_im, step, noise_scale, seed,
+                                    sample_offset, step_id, dev_sched, sens_f32, (name, name, name))
+    head = _pc_head("pc_sense_step", head, B, dev_sched, sample_sched)
+    n = sens_f32.shape[-3]
+    _check_work(work, B, n, H, W, "pc_sense_step")
+    mask_t = _mask_t(mask_u8, H, W, "pc_sense_step")
+    call(fn, *head, _ptr(y), _ptr(sens_f32), *_pc_sens_tail(sens_f32), _ptr(mask_u8), mask_t, float(coef), _ptr(work), B, n,
+         H, W, _stream())
+    _written(x_re, x_im)
+
+
+def pc_sense_cg_step(x_re, x_im, g_re, g_im, y, sens_f32, mask_u8, work, step=0.0, noise_scale=0.0, coef=0.0, noise_re=None,
+                     noise_im=None, seed=0, sample_offset=0, step_id=0, dev_sched=None, sample_sched=None, ahy=None,
+                     max_iter=10, tol=1e-5, iters_out=None):
+    """ald_sense_cg_step with a schedule record per sample (pc_sense_step).  -> iters (device int32 [B])"""
+    max_iter, tol = _check_cg_scalars(max_iter, tol, "pc_sense_cg_step")
+    name = "ipdm_pc_sense_cg_step_f32"
+    fn, B, H, W, head = _fused_step("pc_sense_cg_step", x_re, x_im, g_re, g_im, y, noise_re, noise_im, step, noise_scale, seed,
+                                    sample_offset, step_id, dev_sched, sens_f32, (name, name, name))
+    head = _pc_head("pc_sense_cg_step", head, B, dev_sched, sample_sched)
+    nc = sens_f32.shape[-3]
+    work, iters_out = _check_cg_args(work, ahy, iters_out, B, nc, H, W, x_re.device, "pc_sense_cg_step")
+    mask_t = _mask_t(mask_u8, H, W, "pc_sense_cg_step")
+    call(fn, *head, _ptr(y), _ptr(sens_f32), *_pc_sens_tail(sens_f32), _ptr(mask_u8), mask_t, float(coef), _ptr(work),
+         _ptr(ahy), max_iter, tol, _ptr(iters_out), B, nc, H, W, _stream())
+    _written(x_re, x_im, iters_out)
+    return iters_out
+
+
+def pc_singlecoil_step(x_re, x_im, g_re, g_im, y, mask_u8, mode, step=0.0, noise_scale=0.0, coef=0.0, noise_re=None,
+                       noise_im=None, seed=0, sample_offset=0, step_id=0, dev_sched=None, sample_sched=None, work=None):
+    """ald_singlecoil_step with a schedule record per sample (pc_sense_step); in place on x_re / x_im"""
+    _, B, H, W, head = _fused_step("pc_singlecoil_step", x_re, x_im, g_re, g_im, y, noise_re, noise_im, step, noise_scale,
+                                   seed, sample_offset, step_id, dev_sched)
+    for t, n in ((noise_re, "noise_re"), (noise_im, "noise_im")):
+        if t is not None:
+            _inplace_operand(t, torch.float32, n)
+    if g_re.numel() != x_re.numel() or g_im.numel() != x_im.numel() or y.numel() != B * H * W:
+        raise ValueError("pc_singlecoil_step: operand sizes do not match the state")
+    head = _pc_head("pc_singlecoil_step", head, B, dev_sched, sample_sched)
+    if work is None and _large_image(H, W):
+        work = sense_workspace(B, 1, H, W, x_re.device)
+    if work is not None or _large_image(H, W):
+        _check_work(work, B, 1, H, W, "pc_singlecoil_step")
+    mask_t = _mask_t(mask_u8, H, W, "pc_singlecoil_step")
+    call("ipdm_pc_singlecoil_step_f32", *head, _ptr(y), _ptr(mask_u8), mask_t, float(coef), int(mode), _ptr(work), B, H, W,
+         _stream())
+    _written(x_re, x_im)
+
+
 # ---- segmentation-likelihood guidance glue ----------------------------------------------------------
 def zero_insert2(x):
     """(..., H, W) -> (..., 2H, 2W): x at the even positions, zeros elsewhere"""
