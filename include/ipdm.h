@@ -486,6 +486,52 @@ int ipdm_pc_singlecoil_step_f32(float* x_re, float* x_im, const float* g_re, con
                                 const ipdm_sched_t* dev_sched, int sched_stride, const float* y, const uint8_t* mask,
                                 int mask_t, float coef, int mode, float* workspace, int B, int H, int W, void* stream);
 
+/* Non-Cartesian SENSE: samples at arbitrary k-space positions (radial, spiral, ...), DESIGN.md 4.4l.
+ *   traj      device float64 [M][2] = (k_y, k_x) in cycles per field of view, |k_y| <= H/2, |k_x| <= W/2 (by the caller)
+ *   weights   device float32 [M], w_m >= 0; NULL: 1 (the likelihood of i.i.d. noise; density compensation is for the
+ *             zero-filled image alone)
+ *   sens      interleaved complex64 [n_coils][H][W]; NULL: S = 1 (see each entry point)
+ *   forward   y[c,b,m] = (HW)^-1/2 sum_{r,col} S_c[r,col] x[b,r,col] exp(-2 pi i (k_y,m (r - H/2)/H + k_x,m (col - W/2)/W))
+ *             -- the package's centred orthonormal convention: a sample on the integer grid point (k_y, k_x) is
+ *             ipdm_fft2c_c64's value at index (k_y + H/2, k_x + W/2) --, adjoint its conjugate transpose after w.
+ * The transforms are exact direct sums (no gridding, no interpolation), accumulated in double in a fixed order, and
+ * are meant to run once per reconstruction.  The per-iteration operator A^H W A is Toeplitz:
+ *   T[dr + H, dc + W] = sum_m w_m exp(2 pi i (k_y,m dr/H + k_x,m dc/W)), |dr| < H, |dc| < W (row 0 / column 0: zero),
+ *   psf = centred unnormalised DFT of T, over HW: real, float32 [2H][2W], may be negative
+ *   A^H W A v = sum_c conj(S_c) crop(F^-1(psf . F(pad(S_c v)))),  v at rows [H/2, H/2 + H), columns [W/2, W/2 + W) of 2H x 2W.
+ * Sizes: every (H, W) whose padded grid 2H x 2W is a size of ipdm_kspace_size_class (ipdm_nc_supported tells, without a
+ * GPU), B and n_coils <= 65535 (n_coils * B <= 65535 for the two transforms); otherwise IPDM_EUNSUPPORTED.  IPDM_EINVAL:
+ * a non-positive size, a NULL operand.  All calls are asynchronous, allocation-free and deterministic. */
+int ipdm_nc_supported(int H, int W);
+/* x: complex64 [B][H][W] with sens, else the coil images [n_coils][B][H][W]; y: complex64 [n_coils][B][M] */
+int64_t ipdm_ndft_workspace_bytes(int M, int H, int W);
+int ipdm_ndft_forward_c64(const float* x, const float* sens, const double* traj, float* y,
+                          float* work /* ipdm_ndft_workspace_bytes */, int B, int n_coils, int M, int H, int W, void* stream);
+/* x: with sens the combined image sum_c conj(S_c)(.) [B][H][W], else the coil images [n_coils][B][H][W] */
+int ipdm_ndft_adjoint_c64(const float* y, const float* sens, const double* traj, const float* weights, float* x,
+                          float* work /* ipdm_ndft_workspace_bytes */, int B, int n_coils, int M, int H, int W, void* stream);
+int64_t ipdm_toeplitz_psf_workspace_bytes(int M, int H, int W);
+int ipdm_toeplitz_psf_f32(const double* traj, const float* weights, float* psf,
+                          float* work /* ipdm_toeplitz_psf_workspace_bytes */, int M, int H, int W, void* stream);
+/* out = A^H W A v; v, out complex64 [B][H][W], out != v; sens NULL needs n_coils == 1 */
+int64_t ipdm_toeplitz_workspace_bytes(int B, int n_coils, int H, int W);
+int ipdm_toeplitz_normal_c64(const float* v, const float* sens, const float* psf, float* out,
+                             float* work /* ipdm_toeplitz_workspace_bytes */, int B, int n_coils, int H, int W, void* stream);
+/* ipdm_sense_cgprox_f32 and ipdm_pc_sense_cg_step_f32 (sched_stride 0: ipdm_ald_sense_cg_step_f32) for the operator
+ * above: (I + a A^H W A) x = z + a ahy with ahy = A^H W y REQUIRED (ipdm_ndft_adjoint_c64; the iterations never apply
+ * A).  Same solver kernels, stopping rule, per-sample freezing, iters_out, schedule records and fixed launch sequence
+ * (3 + 4 max_iter launches, + 1 with a Langevin update): one captured hipGraph serves every noise level. */
+int64_t ipdm_nc_sense_cg_workspace_bytes(int B, int n_coils, int H, int W);
+int ipdm_nc_sense_cgprox_f32(const float* z_re, const float* z_im, const float* sens, const float* psf, float a,
+                             const float* ahy, int max_iter, float tol, float* out_re, float* out_im, float* work,
+                             int32_t* iters_out, int B, int n_coils, int H, int W, void* stream);
+int ipdm_ald_nc_sense_cg_step_f32(float* x_re, float* x_im, const float* g_re, const float* g_im,
+                                  const float* noise_re, const float* noise_im,
+                                  float step, float noise_scale, uint64_t seed, int64_t sample_offset, int64_t step_id,
+                                  const ipdm_sched_t* dev_sched, int sched_stride, const float* sens, const float* psf,
+                                  float coef, float* work, const float* ahy, int max_iter, float tol, int32_t* iters_out,
+                                  int B, int n_coils, int H, int W, void* stream);
+
 /* Langevin update alone (ALD_optimizers.py:117): x += step*g + noise_scale*noise ; noise NULL -> Philox. */
 int ipdm_langevin_step_f32(float* x, const float* g, const float* noise, float step, float noise_scale,
                            uint64_t seed, int64_t sample_offset, int64_t step_id, const ipdm_sched_t* dev_sched,

@@ -107,6 +107,19 @@ SIGNATURES = {
                                   c_int, c_int, c_int, c_int, P],
     "ipdm_pc_singlecoil_step_f32": [P, P, P, P, P, P, c_float, c_float, c_uint64, c_int64, c_int64, P, c_int,
                                     P, P, c_int, c_float, c_int, P, c_int, c_int, c_int, P],
+    # non-Cartesian SENSE
+    "ipdm_nc_supported": [c_int, c_int],
+    "ipdm_ndft_workspace_bytes": [c_int, c_int, c_int],
+    "ipdm_ndft_forward_c64": [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P],
+    "ipdm_ndft_adjoint_c64": [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P],
+    "ipdm_toeplitz_psf_workspace_bytes": [c_int, c_int, c_int],
+    "ipdm_toeplitz_psf_f32": [P, P, P, P, c_int, c_int, c_int, P],
+    "ipdm_toeplitz_workspace_bytes": [c_int, c_int, c_int, c_int],
+    "ipdm_toeplitz_normal_c64": [P, P, P, P, P, c_int, c_int, c_int, c_int, P],
+    "ipdm_nc_sense_cg_workspace_bytes": [c_int, c_int, c_int, c_int],
+    "ipdm_nc_sense_cgprox_f32": [P, P, P, P, c_float, P, c_int, c_float, P, P, P, P, c_int, c_int, c_int, c_int, P],
+    "ipdm_ald_nc_sense_cg_step_f32": [P, P, P, P, P, P, c_float, c_float, c_uint64, c_int64, c_int64, P, c_int,
+                                      P, P, c_float, P, P, c_int, c_float, P, c_int, c_int, c_int, c_int, P],
     "ipdm_langevin_step_f32": [P, P, P, c_float, c_float, c_uint64, c_int64, c_int64, P, c_int64, c_int64, P],
     "ipdm_philox_normal_f32": [P, c_uint64, c_int64, c_int64, c_int, c_int64, c_int64, P],
     "ipdm_philox_block_host": [c_uint64, c_int64, c_int64, c_int, ctypes.c_uint32, P],
@@ -208,6 +221,8 @@ SIGNATURES = {
 }
 _RESTYPES = {"ipdm_build_arch": c_char_p, "ipdm_debug_lds_optin_count": c_int64, "ipdm_fft2c_workspace_bytes": c_int64, "ipdm_sense_workspace_bytes": c_int64, "ipdm_sense_cg_workspace_bytes": c_int64,
              "ipdm_pc_langevin_coef_workspace_bytes": c_int64,
+             "ipdm_ndft_workspace_bytes": c_int64, "ipdm_toeplitz_psf_workspace_bytes": c_int64,
+             "ipdm_toeplitz_workspace_bytes": c_int64, "ipdm_nc_sense_cg_workspace_bytes": c_int64,
              "ipdm_conv_bx3_weight_bytes": c_int64,
              "ipdm_conv_wino_bx3_weight_bytes": c_int64, "ipdm_conv_hx2_weight_bytes": c_int64,
              "ipdm_conv_wino_hx2_weight_bytes": c_int64, "ipdm_conv_wino1d_weight_bytes": c_int64, "ipdm_conv_wino1d_weight_bytes3d": c_int64,

@@ -273,7 +273,93 @@ static int cg_step_impl(float* x_re, float* x_im, const LangevinArgs& lg, const 
                   ipdm_stream(stream));
 }
 
+// ---- non-Cartesian SENSE: the same solver with the Toeplitz normal operator ----------------------------------
+// N = I + a A^H W A, A^H W A applied by ipdm_kspace_large::toeplitz_normal; A^H W y is always the caller's (the hot path never
+// applies A).  The strip form of cg_solve for every size: one plane per sample, the update kernels grid-stride.
+//     [Langevin]  ->  T x - A^H y  ->  init  ->  max_iter x ( T p  ->  update )
+struct NcCgWork {
+  float2 *ws, *nout, *r, *p;
+  CgState* state;
+};
+static inline NcCgWork nc_carve(float* work, int B, int n_coils, int H, int W) {
+  const size_t img = (size_t)B * H * W;
+  NcCgWork w;
+  w.ws = reinterpret_cast<float2*>(work);          // the Toeplitz chain's n_coils * B * H * 2W values
+  w.nout = w.ws + 2 * img * n_coils;
+  w.r = w.nout + img;
+  w.p = w.r + img;
+  w.state = reinterpret_cast<CgState*>(w.p + img);
+  return w;
+}
+
+static int nc_cg_solve(float* x_re, float* x_im, const LangevinArgs& lg, const ToepProblem& tp, float a, const float2* ahy,
+                       int max_iter, float tol, float* work, int32_t* iters_out, hipStream_t st) {
+  const int B = tp.B, H = tp.H, W = tp.W, HW = H * W;
+  const NcCgWork w = nc_carve(work, B, tp.n_coils, H, W);
+  int rc;
+  if (lg.g_re) {
+    rc = ipdm_kspace_large::langevin(x_re, x_im, lg, B, H, W, st);
+    if (rc) return rc;
+  }
+  rc = ipdm_kspace_large::toeplitz_normal(nullptr, x_re, x_im, tp, ahy, w.nout, w.ws, st);
+  if (rc) return rc;
+  hipLaunchKernelGGL(cg_init_kernel<false>, dim3(B), dim3(FFT_THREADS), 0, st, x_re, x_im, lg, a, tol, w.nout, 1, ahy, w.r, w.p,
+                     w.state, iters_out, HW);
+  rc = ipdm_launch_status();
+  if (rc) return rc;
+  for (int it = 0; it < max_iter; ++it) {
+    rc = ipdm_kspace_large::toeplitz_normal(w.p, nullptr, nullptr, tp, nullptr, w.nout, w.ws, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(cg_update_kernel<false>, dim3(B), dim3(FFT_THREADS), 0, st, x_re, x_im, lg.sched, lg.sched_stride, a, tol,
+                       w.nout, 1, w.r, w.p, w.state, iters_out, HW);
+    rc = ipdm_launch_status();
+    if (rc) return rc;
+  }
+  return IPDM_OK;
+}
+
+static inline bool nc_cg_dims_ok(int B, int n_coils, int H, int W) { return B >= 0 && n_coils > 0 && H > 0 && W > 0; }
+static inline bool nc_cg_served(int B, int n_coils, int H, int W) {
+  return ipdm_kspace_large::toeplitz_ok(H, W) && B <= 65535 && n_coils <= 65535;
+}
+
 }  // namespace
+
+extern "C" int64_t ipdm_nc_sense_cg_workspace_bytes(int B, int n_coils, int H, int W) {
+  if (B <= 0 || n_coils <= 0 || !ipdm_kspace_large::toeplitz_ok(H, W)) return 0;
+  return (2 * (int64_t)n_coils + 3) * B * H * W * (int64_t)sizeof(float2) + (int64_t)B * (int64_t)sizeof(CgState);
+}
+
+extern "C" int ipdm_nc_sense_cgprox_f32(const float* z_re, const float* z_im, const float* sens, const float* psf, float a,
+                                        const float* ahy, int max_iter, float tol, float* out_re, float* out_im, float* work,
+                                        int32_t* iters_out, int B, int n_coils, int H, int W, void* stream) {
+  IPDM_REQUIRE(nc_cg_dims_ok(B, n_coils, H, W) && cg_scalars_ok(max_iter, tol) && (sens || n_coils == 1));
+  if (B == 0) return IPDM_OK;
+  if (!nc_cg_served(B, n_coils, H, W)) return IPDM_EUNSUPPORTED;
+  IPDM_REQUIRE(z_re && z_im && psf && ahy && out_re && out_im && work);
+  hipStream_t st = ipdm_stream(stream);
+  const int rc = copy_planes(out_re, out_im, z_re, z_im, (size_t)B * H * W, st);
+  const ToepProblem tp{reinterpret_cast<const float2*>(sens), psf, B, n_coils, H, W};
+  return rc ? rc : nc_cg_solve(out_re, out_im, NO_LANGEVIN, tp, a, reinterpret_cast<const float2*>(ahy), max_iter, tol, work,
+                               iters_out, st);
+}
+
+extern "C" int ipdm_ald_nc_sense_cg_step_f32(float* x_re, float* x_im, const float* g_re, const float* g_im,
+                                             const float* noise_re, const float* noise_im, float step, float noise_scale,
+                                             uint64_t seed, int64_t sample_offset, int64_t step_id,
+                                             const ipdm_sched_t* dev_sched, int sched_stride, const float* sens,
+                                             const float* psf, float coef, float* work, const float* ahy, int max_iter, float tol,
+                                             int32_t* iters_out, int B, int n_coils, int H, int W, void* stream) {
+  IPDM_REQUIRE(nc_cg_dims_ok(B, n_coils, H, W) && cg_scalars_ok(max_iter, tol) && (sens || n_coils == 1) &&
+               sched_stride_ok(dev_sched, sched_stride));
+  if (B == 0) return IPDM_OK;
+  if (!nc_cg_served(B, n_coils, H, W)) return IPDM_EUNSUPPORTED;
+  IPDM_REQUIRE(x_re && x_im && g_re && g_im && (noise_re == nullptr) == (noise_im == nullptr) && psf && ahy && work);
+  const LangevinArgs lg{g_re, g_im, noise_re, noise_im, step, noise_scale, seed, sample_offset, step_id, dev_sched, sched_stride};
+  const ToepProblem tp{reinterpret_cast<const float2*>(sens), psf, B, n_coils, H, W};
+  return nc_cg_solve(x_re, x_im, lg, tp, coef, reinterpret_cast<const float2*>(ahy), max_iter, tol, work, iters_out,
+                     ipdm_stream(stream));
+}
 
 extern "C" int64_t ipdm_sense_cg_workspace_bytes(int B, int n_coils, int H, int W) {
   if (B <= 0 || n_coils <= 0 || H <= 0 || W <= 0) return 0;

@@ -420,6 +420,13 @@ static inline int copy_planes(float* out_re, float* out_im, const float* z_re, c
   return IPDM_OK;
 }
 
+// Non-Cartesian SENSE: A^H W A is the Toeplitz operator of the real spectrum psf on the 2H x 2W grid.
+struct ToepProblem {
+  const float2* sens;              // complex64 [n_coils][H][W]; NULL (n_coils == 1): S = 1
+  const float* psf;                // float32 [2H][2W]
+  int B, n_coils, H, W;
+};
+
 }  // namespace ipdm_kspace
 
 // row / column-pass operators for images of served sides beyond the LDS (kspace_large.hip)
@@ -445,4 +452,11 @@ int langevin(float* x_re, float* x_im, const ipdm_kspace::LangevinArgs& lg, int 
 template <typename SensT>
 int normal_op(const float2* xc, const float* x_re, const float* x_im, const ipdm_kspace::SenseProblem<SensT>& pb, float2* out,
               float2* ws, hipStream_t s);
+// Toeplitz normal operator of a non-Cartesian trajectory on the strip passes, every served size (toeplitz_ok: the padded
+// 2H x 2W grid is a size of ipdm_kspace_size_class):
+//   out[b] = sum_c conj(S_c) crop(F^-1(psf . F(pad(S_c v))))  [- sub[b] when sub is given]
+// v complex (vc) or planar (v_re, v_im; vc NULL); ws holds n_coils * B * H * 2W values and out must not overlap it.
+bool toeplitz_ok(int H, int W);
+int toeplitz_normal(const float2* vc, const float* v_re, const float* v_im, const ipdm_kspace::ToepProblem& tp, const float2* sub,
+                    float2* out, float2* ws, hipStream_t s);
 }  // namespace ipdm_kspace_large

@@ -473,4 +473,145 @@ int prox_step(float* x_re, float* x_im, const LangevinArgs& lg, const SenseProbl
 template int prox_step(float*, float*, const LangevinArgs&, const SenseProblem<float>&, float, int, float2*, hipStream_t);
 template int prox_step(float*, float*, const LangevinArgs&, const SenseProblem<float2>&, float, int, float2*, hipStream_t);
 
+// ---- Toeplitz normal operator of a non-Cartesian trajectory ---------------------------------------------
+// The H x W image sits at rows [H/2, H/2 + H), columns [W/2, W/2 + W) of a zero 2H x 2W grid that is never stored: the row
+// passes run over the H rows that hold data (length 2W), the two-way column pass over all 2W columns (length 2H) with zeros
+// loaded outside the H stored rows and only those rows stored.  ws[coil][b][H][2W].  Signs: the centring flips of the forward
+// transform's output and of the inverse transform's input cancel around the real factor psf, so the column pass applies
+// psf / (4HW) alone; the flips of the padded grid's index (r + H/2, c) remain at the two ends.
+struct ToepGeo {
+  int B, H, W;                     // image size
+  __device__ __forceinline__ size_t ws_at(int coil, int b, int r, int c) const {     // c on the 2W grid
+    return (((size_t)coil * B + b) * H + r) * (2 * (size_t)W) + c;
+  }
+};
+
+// rows of pad(sign * S_c * v) -> ws[coil][b]      (v complex64 or planar; sens NULL: S = 1)
+struct ToepRowsFwd {
+  ToepGeo g;
+  const float2* x;
+  const float *xr, *xi;
+  const float2* sens;
+  float2* dst;
+  __device__ __forceinline__ ToepRowsFwd for_image(int) const { return *this; }
+  __device__ __forceinline__ float2 load(int b, int coil, int r, int c) const {
+    const int c2 = c - g.W / 2;
+    if ((unsigned)c2 >= (unsigned)g.W) return make_float2(0.f, 0.f);
+    const size_t i = ((size_t)b * g.H + r) * g.W + c2;
+    const float2 v = x ? x[i] : make_float2(xr[i], xi[i]);
+    const float s = sign_rc(r + g.H / 2, c);
+    if (sens) return sens_mul(v, s, sens[((size_t)coil * g.H + r) * g.W + c2]);
+    return make_float2(v.x * s, v.y * s);
+  }
+  __device__ __forceinline__ void store(int b, int coil, int r, int c, float2 v) const { dst[g.ws_at(coil, b, r, c)] = v; }
+};
+
+// in-place columns on ws[coil][b], the 2H-long columns of the padded grid: forward, times psf / (4HW), inverse
+struct ToepCols {
+  ToepGeo g;
+  float2* ws;
+  const float* psf;                // [2H][2W]
+  float scale2;                    // 1 / (4HW): the orthonormal pair's two factors
+  __device__ __forceinline__ float2 load(int b, int coil, int r, int c) const {
+    const int r2 = r - g.H / 2;
+    return (unsigned)r2 < (unsigned)g.H ? ws[g.ws_at(coil, b, r2, c)] : make_float2(0.f, 0.f);
+  }
+  __device__ __forceinline__ void store(int b, int coil, int r, int c, float2 v) const {
+    const int r2 = r - g.H / 2;
+    if ((unsigned)r2 < (unsigned)g.H) ws[g.ws_at(coil, b, r2, c)] = v;
+  }
+  __device__ __forceinline__ bool skip(int, int, int) const { return false; }
+  __device__ __forceinline__ float2 mid(int, int, int r, int c, float2 v) const {
+    const float p = psf[(size_t)r * (2 * (size_t)g.W) + c] * scale2;
+    return make_float2(v.x * p, v.y * p);
+  }
+};
+
+// ws[coil][b] rows -> inverse row FFT (length 2W) -> crop -> acc += sign * conj(S_c) * v (registers, coil order) ->
+// out[b] = acc - sub[b]    (sub NULL: nothing subtracted)
+template <bool MIXED>
+__global__ __launch_bounds__(FFT_THREADS) void toep_rows_inv_accum_kernel(const float2* __restrict__ ws,
+                                                                          const float2* __restrict__ sens,
+                                                                          const float2* __restrict__ sub, float2* out, int B,
+                                                                          int n_coils, int H, int W) {
+  const int W2 = 2 * W;
+  STRIP_LDS_SETUP(W2)
+  const ToepGeo g{B, H, W};
+  const int RS = strip_lines<MIXED>(H, W2);
+  const int r0 = blockIdx.x * RS, b = blockIdx.y;
+  const int n = RS * W2;
+  float2 acc[EPT];
+#pragma unroll
+  for (int k = 0; k < EPT; ++k) acc[k] = make_float2(0.f, 0.f);
+  for (int coil = 0; coil < n_coils; ++coil) {
+    const float2* __restrict__ src = ws + g.ws_at(coil, b, r0, 0);       // the strip's rows are contiguous
+#pragma unroll
+    for (int k = 0; k < EPT; ++k) {
+      const int e = threadIdx.x + k * FFT_THREADS;
+      if (e < n) L.buf[e] = src[e];
+    }
+    __syncthreads();
+    fft_lines<MIXED>(L, W2, 1, W2, RS, false, true);
+#pragma unroll
+    for (int k = 0; k < EPT; ++k) {
+      const int e = threadIdx.x + k * FFT_THREADS;
+      if (e < n) {
+        const int lr = e / W2, c = e - lr * W2, c2 = c - W / 2;
+        if ((unsigned)c2 < (unsigned)W) {
+          const float2 v = L.buf[e];
+          const float sg = sign_rc(r0 + lr + H / 2, c);
+          const float2 t = sens ? sens_mul_conj(v, sg, sens[((size_t)coil * H + r0 + lr) * W + c2])
+                                : make_float2(v.x * sg, v.y * sg);
+          acc[k].x += t.x;
+          acc[k].y += t.y;
+        }
+      }
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int k = 0; k < EPT; ++k) {
+    const int e = threadIdx.x + k * FFT_THREADS;
+    if (e < n) {
+      const int lr = e / W2, c = e - lr * W2, c2 = c - W / 2;
+      if ((unsigned)c2 < (unsigned)W) {
+        const size_t gi = ((size_t)b * H + r0 + lr) * W + c2;
+        float2 o = acc[k];
+        if (sub) {
+          const float2 h = sub[gi];
+          o = make_float2(o.x - h.x, o.y - h.y);
+        }
+        out[gi] = o;
+      }
+    }
+  }
+}
+
+bool toeplitz_ok(int H, int W) {
+  if (H <= 0 || W <= 0 || H > FFT_MAX_SIDE / 2 || W > FFT_MAX_SIDE / 2) return false;
+  return lds_fft_ok(2 * H, 2 * W) || large_ok(2 * H, 2 * W);
+}
+
+int toeplitz_normal(const float2* vc, const float* v_re, const float* v_im, const ToepProblem& tp, const float2* sub, float2* out,
+                    float2* ws, hipStream_t s) {
+  const int B = tp.B, n = tp.n_coils, H = tp.H, W = tp.W;
+  const ToepGeo g{B, H, W};
+  ToepRowsFwd rf{g, vc, v_re, v_im, tp.sens, ws};
+  int rc = launch_rows(rf, B, n, H, 2 * W, 0, s);
+  if (rc) return rc;
+  ToepCols tc{g, ws, tp.psf, 0.25f / ((float)H * (float)W)};
+  rc = launch_cols<ToepCols, true>(tc, B, n, 2 * H, 2 * W, 0, s);
+  if (rc) return rc;
+  const size_t lds = strip_lds_bytes(2 * W);
+  const int RS = strip_lines(H, 2 * W);
+  return fft_dispatch(fft_mixed(H, 2 * W), [&](auto mixed) {
+    constexpr bool MIXED = decltype(mixed)::value;
+    rc = ipdm_lds_optin(toep_rows_inv_accum_kernel<MIXED>, lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL(toep_rows_inv_accum_kernel<MIXED>, dim3(H / RS, B), dim3(FFT_THREADS), lds, s, ws, tp.sens, sub, out, B, n,
+                       H, W);
+    return ipdm_launch_status();
+  });
+}
+
 }  // namespace ipdm_kspace_large

@@ -59,7 +59,7 @@ def build_scorenet(cfg, seed=0):
 def build_problem(device, n_samples, R=40, H=128, W=128, num_sens=4, seed=0, scorenet=None, cfg=None, lr_scaled=1.0,
                   sens_maps=None, proximal="L2Penalty", proximal_kwargs=None, mask=None, estimate_maps=False, measurement=None,
                   calib_max=12, kspace_scale=None, coil_compress=None, noise_cov=None, n_slices=None, maps_method="walsh",
-                  maps_kwargs=None, coil_compress_mode="pca", coil_compress_window=2):
+                  maps_kwargs=None, coil_compress_mode="pca", coil_compress_window=2, trajectory=None, traj_weights=None):
     """-> Namespace(sampler, scorenet, sigmas, op, image, measurement, call_kwargs); sens_maps: measured coil maps
     (num_sens, H, W), real or complex, instead of the synthetic "exp" maps (RSS-normalised where non-zero); proximal: a
     get_proximal name ("L2PenaltyCG": the exact proximal, proximal_kwargs = dict(max_iter=, tol=)); mask: the sampling mask
@@ -90,7 +90,21 @@ def build_problem(device, n_samples, R=40, H=128, W=128, num_sens=4, seed=0, sco
     same order.  The automatic kspace_scale is ONE number, 1 / the largest rss_max over the slices: the slices of a volume
     share a grey scale.  A simulated stack draws slice s from phantom seed `seed + s` and, with sens_maps=None, from "exp"
     maps of seed `seed + s * num_sens` (every coil anchor of the stack its own seed); the mask is the one of `seed`.  The
-    Namespace carries n_slices (1 without a stack); image is then (S, 1, H, W)."""
+    Namespace carries n_slices (1 without a stack); image is then (S, 1, H, W).
+    trajectory: (M, 2) k-space positions (k_y, k_x) in cycles per field of view -- non-Cartesian SENSE (NonCartesianSENSE;
+    traj_weights its optional likelihood weights).  Simulated: the phantom through the exact forward transform with the
+    synthetic complex maps (or sens_maps=).  Measured: measurement (n_coils, M) with sens_maps= required, scaled by
+    kspace_scale -- None: 1 / the peak magnitude of the density-compensated adjoint zero_filled(y).  The proximal is
+    L2PenaltyCG (the default name "L2Penalty" is replaced by it; any other is refused); mask, R, estimate_maps,
+    coil_compress and n_slices do not go with a trajectory and are refused before anything is allocated.  The Namespace
+    carries zero_filled, the density-compensated adjoint of the (scaled) measurement, (1, 1, H, W) on the device."""
+    if trajectory is not None:
+        return _build_noncartesian(device, n_samples, H, W, num_sens, seed, scorenet, cfg, lr_scaled, sens_maps, proximal,
+                                   proximal_kwargs, measurement, kspace_scale, trajectory, traj_weights,
+                                   dict(mask=mask is not None, estimate_maps=bool(estimate_maps), coil_compress=coil_compress is not None,
+                                        noise_cov=noise_cov is not None, n_slices=n_slices is not None))
+    if traj_weights is not None:
+        raise ValueError("build_problem: traj_weights= goes with trajectory=")
     prox_cls = get_proximal(proximal)                        # an unknown name fails here, before any GPU work
     kspace_scale = None if kspace_scale is None else float(kspace_scale)
     region = None
@@ -189,6 +203,59 @@ def build_problem(device, n_samples, R=40, H=128, W=128, num_sens=4, seed=0, sco
             op, eigval = _maps_from_simulated(meas1, op.random_under_fourier.mask, R, seed, calib_max, maps_method, maps_kwargs)
     return _assemble(device, n_samples, 1, H, W, scorenet, cfg, sigmas, op, img, meas1, prox_cls, proximal_kwargs, lr_scaled,
                      estimate_maps, kspace_scale, coil_matrix, eigval)
+
+
+def _build_noncartesian(device, n_samples, H, W, num_sens, seed, scorenet, cfg, lr_scaled, sens_maps, proximal, proximal_kwargs,
+                        measurement, kspace_scale, trajectory, traj_weights, refused):
+    """build_problem(trajectory=...), its docstring.  Every check runs on the host before the network is built."""
+    from .ncsn.linear_transforms.noncartesian import NonCartesianSENSE
+    from .synthetic import complex_coil_maps
+    for name, given in refused.items():
+        if given:
+            raise ValueError(f"build_problem: {name}= does not go with trajectory= (non-Cartesian SENSE takes given coil maps, "
+                             "one slice, and no sampling mask)")
+    if proximal not in ("L2Penalty", "L2PenaltyCG"):
+        get_proximal(proximal)
+        raise ValueError(f"build_problem: proximal={proximal!r} does not serve a trajectory; non-Cartesian SENSE takes L2PenaltyCG")
+    prox_cls = get_proximal("L2PenaltyCG")
+    if measurement is not None:
+        if sens_maps is None:
+            raise ValueError("build_problem(measurement=..., trajectory=...): pass sens_maps=, the coil maps (they cannot be "
+                             "estimated from non-Cartesian data here)")
+        measurement = torch.as_tensor(measurement)
+        M = torch.as_tensor(trajectory).shape[0] if torch.as_tensor(trajectory).dim() == 2 else -1
+        if measurement.dim() != 2 or not measurement.is_complex() or measurement.shape[1] != M:
+            raise ValueError(f"build_problem: measurement {tuple(measurement.shape)} {measurement.dtype}; complex (n_coils, M = {M}) "
+                             "expected with a trajectory")
+        num_sens = measurement.shape[0]
+    if sens_maps is None:
+        sens_maps = complex_coil_maps(num_sens, H, W, seed)
+    op = NonCartesianSENSE(trajectory, (1, H, W), sens_maps=sens_maps, weights=traj_weights)     # the remaining host checks
+    if op.num_sens != num_sens:
+        raise ValueError(f"build_problem: {num_sens} coil signals, {op.num_sens} coil maps")
+    cfg = acdc_config(device, H) if cfg is None else cfg
+    scorenet = build_scorenet(cfg, seed) if scorenet is None else scorenet
+    sigmas = get_sigmas(cfg, "recons")
+    if measurement is not None:
+        img = None
+        meas1 = measurement.to(torch.complex64).to(device).reshape(num_sens, 1, 1, -1).contiguous()
+        if kspace_scale is None:                             # the score prior expects magnitudes in [0, 1]
+            peak = float(op.zero_filled(meas1).abs().max())
+            if not peak > 0.0:
+                raise ValueError("build_problem: the measurement holds no signal")
+            kspace_scale = 1.0 / peak
+        meas1 = meas1 * float(kspace_scale)
+    else:
+        img = phantom_image(H, W, seed=seed).to(device)
+        meas1 = op(img)
+    meas = meas1.repeat(1, n_samples, 1, 1).contiguous()
+    params = dict(n_steps_each=cfg.sampling.n_steps_each, step_lr=cfg.sampling.step_lr, denoise=True, final_only=True)
+    sampler = ALDInvSegProximalRealImag(prox_cls(op, **(proximal_kwargs or {})), 1.0, "linear", (n_samples, 1, H, W), scorenet,
+                                        sigmas, params, cfg, meas, op, seg=None, device=device)
+    return Namespace(sampler=sampler, scorenet=scorenet, sigmas=sigmas, op=op, image=img, measurement=meas, cfg=cfg, params=params,
+                     call_kwargs=dict(label=None, lamda=0.1, save_dir=None, lr_scaled=lr_scaled, seg_mode="full"),
+                     estimated_maps=False, kspace_scale=kspace_scale, coil_matrix=None, n_slices=1, espirit_eigval=None,
+                     zero_filled=op.zero_filled(meas1))
 
 
 def build_pc_sampler(prob, sde, **kw):

@@ -225,13 +225,16 @@ def load_sens_maps(path):
     return maps.to(torch.complex128 if maps.is_complex() else torch.float64)
 
 
-def load_kspace(path, cine=False, slices=False):
+def load_kspace(path, cine=False, slices=False, noncartesian=False):
     """measured multi-coil k-space (n_coils, H, W) -- cine=True: 2D+time k-space (n_coils, T, H, W); slices=True: a stack
-    of slices (S, n_coils, H, W) -- from a ``.npy`` or ``.pt`` file -> host complex64 tensor, centred with orthonormal
+    of slices (S, n_coils, H, W); noncartesian=True: the samples of a trajectory (n_coils, M), in the order of
+    ``load_trajectory``'s positions -- from a ``.npy`` or ``.pt`` file -> host complex64 tensor, centred with orthonormal
     scale as ``SENSE.__call__`` produces it (``engine.build_problem(measurement=...)``, ``SENSE.from_cine_measurement``);
     any other rank or a real dtype is a ValueError"""
     if cine and slices:
         raise ValueError("load_kspace: cine=True or slices=True, not both (a cine volume is not served)")
+    if noncartesian and (cine or slices):
+        raise ValueError("load_kspace: noncartesian=True goes with neither cine=True nor slices=True")
     import numpy as np
     import torch
     ext = os.path.splitext(str(path))[1].lower()
@@ -243,12 +246,37 @@ def load_kspace(path, cine=False, slices=False):
             y = torch.from_numpy(y)
     else:
         raise ValueError(f"load_kspace: {path!r}: a .npy or .pt file")
-    if not isinstance(y, torch.Tensor) or y.dim() != (4 if cine or slices else 3):
+    if noncartesian:
+        if not isinstance(y, torch.Tensor) or y.dim() != 2:
+            raise ValueError(f"load_kspace: {path!r} must hold one array of shape (n_coils, M)")
+    elif not isinstance(y, torch.Tensor) or y.dim() != (4 if cine or slices else 3):
         raise ValueError(f"load_kspace: {path!r} must hold one array of shape "
                          f"{'(n_coils, T, H, W)' if cine else '(S, n_coils, H, W)' if slices else '(n_coils, H, W)'}")
     if not y.is_complex():
         raise ValueError(f"load_kspace: {path!r} holds {y.dtype}; complex k-space expected")
     return y.to(torch.complex64).contiguous()
+
+
+def load_trajectory(path):
+    """k-space trajectory (M, 2) = (k_y, k_x) in cycles per field of view, real, from a ``.npy`` or ``.pt`` file -> host
+    float64 tensor for ``NonCartesianSENSE`` / ``engine.build_problem(trajectory=...)``; that it is finite and inside
+    [-N/2, N/2] is checked where the image size is known"""
+    import numpy as np
+    import torch
+    ext = os.path.splitext(str(path))[1].lower()
+    if ext == ".npy":
+        k = torch.from_numpy(np.load(path, allow_pickle=False))
+    elif ext == ".pt":
+        k = torch.load(path, map_location="cpu")
+        if isinstance(k, np.ndarray):
+            k = torch.from_numpy(k)
+    else:
+        raise ValueError(f"load_trajectory: {path!r}: a .npy or .pt file")
+    if not isinstance(k, torch.Tensor) or k.dim() != 2 or k.shape[1] != 2 or k.shape[0] < 1:
+        raise ValueError(f"load_trajectory: {path!r} must hold one array of shape (M, 2) = (k_y, k_x) per sample")
+    if k.is_complex() or not k.is_floating_point():
+        raise TypeError(f"load_trajectory: {path!r} holds {k.dtype}; real floating positions expected")
+    return k.to(torch.float64).contiguous()
 
 
 def load_noise_cov(path):

@@ -32,6 +32,7 @@ import torch
 from ... import ops
 from .proximal_op import Proximal, L2Penalty, L2PenaltyCG, Constrained, SingleCoil  # noqa: F401
 from ..linear_transforms.undersampling_fourier import SENSE, RandomUndersamplingFourier
+from ..linear_transforms.noncartesian import NonCartesianSENSE, refuse_noncartesian
 from ...helpers.utils import data_transform, reshape_temporal_dim
 from ..linear_transforms.finite_diff import FiniteDiff
 
@@ -171,6 +172,12 @@ class ALDInvSegProximalRealImag(ALDOptimizer):
             ops.axpy_sched(grad, gseg, dev_sched=st["sched_dev"])
         if st.get("cg") is not None:         # multi-coil SENSE + L2PenaltyCG: exact proximal, coef = alpha / lamda
             cg = st["cg"]
+            if cg.get("psf") is not None:    # non-Cartesian SENSE: the same tail with the Toeplitz normal operator
+                ops.ald_nc_sense_cg_step(st["x"][:B], st["x"][B:], grad[:B], grad[B:], cg["ahy"], st["sens"], cg["psf"],
+                                         st["work"], noise_re=st["noise_re"], noise_im=st["noise_im"], seed=st["seed"],
+                                         sample_offset=st["sample_offset"], dev_sched=st["sched_dev"],
+                                         max_iter=cg["max_iter"], tol=cg["tol"], iters_out=cg["iters"])
+                return
             ops.ald_sense_cg_step(st["x"][:B], st["x"][B:], grad[:B], grad[B:], st["y"], st["sens"], st["mask"], st["work"],
                                   noise_re=st["noise_re"], noise_im=st["noise_im"], seed=st["seed"],
                                   sample_offset=st["sample_offset"], dev_sched=st["sched_dev"], ahy=cg["ahy"],
@@ -191,6 +198,11 @@ class ALDInvSegProximalRealImag(ALDOptimizer):
             raise NotImplementedError("segmentation-likelihood guidance needs a network with the fused forward + input-gradient "
                                       f"chain (ncsn.models.seg_unet.UNet.loglh_grad); got {type(self.seg).__name__}: there is "
                                       "no autograd on the HIP path")
+        if isinstance(self.linear_tfm, NonCartesianSENSE):
+            if isinstance(self.proximal, L2PenaltyCG):
+                return None
+            raise NotImplementedError(f"no fused iteration for {type(self.proximal).__name__} + NonCartesianSENSE: the "
+                                      "non-Cartesian operator takes L2PenaltyCG, the exact proximal")
         if isinstance(self.linear_tfm, SENSE):
             if isinstance(self.proximal, (L2Penalty, L2PenaltyCG)):
                 return None
@@ -208,10 +220,14 @@ class ALDInvSegProximalRealImag(ALDOptimizer):
     def _cg_state(self, B, n_coils, H, W, dev, ahy):
         """-> (st["cg"], workspace) of the SENSE iteration tail: None and the one-step tail's scratch, or the CG tail's
         settings with A^H y (constant over the run), the per-sample iteration counts and its larger scratch"""
-        if not (isinstance(self.proximal, L2PenaltyCG) and isinstance(self.linear_tfm, SENSE)):
+        nc = isinstance(self.linear_tfm, NonCartesianSENSE)
+        if not (isinstance(self.proximal, L2PenaltyCG) and (nc or isinstance(self.linear_tfm, SENSE))):
             return None, ops.sense_workspace(B, n_coils, H, W, dev)
         iters = torch.zeros(B, dtype=torch.int32, device=dev)
         self.proximal.last_iters = iters
+        if nc:                               # ahy = A^H W y; the spectrum of the Toeplitz kernel is formed here, once
+            return (dict(ahy=ahy.to(torch.complex64).contiguous(), max_iter=self.proximal.max_iter, tol=self.proximal.tol,
+                         iters=iters, psf=self.linear_tfm.psf_dev(dev)), ops.nc_sense_cg_workspace(B, n_coils, H, W, dev))
         return (dict(ahy=ahy.to(torch.complex64).contiguous(), max_iter=self.proximal.max_iter, tol=self.proximal.tol,
                      iters=iters), ops.sense_cg_workspace(B, n_coils, H, W, dev))
 
@@ -238,8 +254,13 @@ class ALDInvSegProximalRealImag(ALDOptimizer):
         lin = self.linear_tfm
 
         x0 = kwargs.get("x_init")
-        ahy = lin.conj_op(meas) if x0 is None or isinstance(self.proximal, L2PenaltyCG) else None
-        x0 = ahy if x0 is None else x0.to(dev)                                # zero-filled SENSE recon, = A^H y
+        nc = isinstance(lin, NonCartesianSENSE)
+        if nc:                                                                # A^H W y for the solver; the start is zero_filled(y)
+            ahy = lin.adjoint_weighted(meas)
+            x0 = lin.zero_filled(meas) if x0 is None else x0.to(dev)
+        else:
+            ahy = lin.conj_op(meas) if x0 is None or isinstance(self.proximal, L2PenaltyCG) else None
+            x0 = ahy if x0 is None else x0.to(dev)                            # zero-filled SENSE recon, = A^H y
         B, H, W = x0.shape[0], x0.shape[-2], x0.shape[-1]
         x = torch.cat([x0.real, x0.imag], dim=0).contiguous().float()        # (2B, 1, H, W)
         steps, noise_scales = step_schedule(sigmas, step_lr)
@@ -250,7 +271,7 @@ class ALDInvSegProximalRealImag(ALDOptimizer):
 
         cg, work = self._cg_state(B, lin.sens_maps.shape[-3] if sc_mode is None else 1, H, W, dev, ahy)
         st = dict(x=x, B=B, y=meas, sc_mode=sc_mode, sens=lin.sens_dev(dev) if sc_mode is None else None,
-                  mask=lin.mask_u8(dev), work=work, cg=cg,
+                  mask=None if nc else lin.mask_u8(dev), work=work, cg=cg,
                   labels=torch.zeros(2 * B, dtype=torch.long, device=dev),
                   noise_re=None, noise_im=None, seed=kwargs.get("seed", 0),
                   sample_offset=kwargs.get("sample_offset", 0),
@@ -396,6 +417,7 @@ class ALD2DTime(ALDOptimizer):
 
     def __init__(self, proximal: Proximal, scorenet_T, sigmas_T, *args, **kwargs):
         super(ALD2DTime, self).__init__(*args, **kwargs)
+        refuse_noncartesian(self.linear_tfm, "ALD2DTime")
         if getattr(self.linear_tfm, "n_map_sets", 1) > 1:
             # the batch here is (B, T) flattened: row % S would pick a map set by frame.  Volume cine is not built.
             raise ValueError(f"ALD2DTime: the operator holds {self.linear_tfm.n_map_sets} coil-map sets (one per slice); the "

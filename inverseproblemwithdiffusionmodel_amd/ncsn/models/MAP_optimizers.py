@@ -15,6 +15,7 @@ every n_iters // 50 iterations as the reference); ``UndersamplingFourier`` (magn
 import torch
 
 from ... import ops
+from ..linear_transforms.noncartesian import refuse_noncartesian
 
 
 class TotalVariation:
@@ -38,6 +39,7 @@ class MAPModel:
     ipdm_adam_ascent_f32 on the planar (real, imaginary) state -- torch's Adam treats a complex parameter the same way)."""
 
     def __init__(self, S, lin_tfm, reg, reg_weight, device=None):
+        refuse_noncartesian(lin_tfm, "MAPModel")
         self.device = torch.device("cuda") if device is None else device
         self.S = S.to(self.device).to(torch.complex64).contiguous()
         self.lin_tfm = lin_tfm
@@ -84,6 +86,7 @@ class MAPOptimizer(object):
                  opt_params=None):
         if opt_class is not None and opt_class is not torch.optim.Adam:
             raise NotImplementedError("only torch.optim.Adam semantics are built (ipdm_adam_ascent_f32)")
+        refuse_noncartesian(linear_tfm, type(self).__name__)
         self.x_init = x_init
         self.measurement = measurement
         self.scorenet = scorenet
@@ -166,6 +169,7 @@ class MAPOptimizer2DTime(object):
         self.scorenet_S, self.scorenet_T = scorenet_S, scorenet_T
         self.win_size = int(np.sqrt(self.scorenet_T.config.data.channels))
         self.linear_tfm = linear_tfm
+        refuse_noncartesian(linear_tfm, "MAPOptimizer2DTime")
         if getattr(linear_tfm, "n_map_sets", 1) > 1:
             # the batch here is (B, T) flattened: row % S would pick a map set by frame.  Volume cine is not built.
             raise ValueError(f"MAPOptimizer2DTime: the operator holds {linear_tfm.n_map_sets} coil-map sets (one per slice); "

@@ -13,9 +13,17 @@ import torch
 
 from ..linear_transforms import LinearTransform
 from ..linear_transforms.undersampling_fourier import RandomUndersamplingFourier, SENSE
+from ..linear_transforms.noncartesian import NonCartesianSENSE
 from ... import ops
 
 SGD_LR = 5e-2
+
+
+def _refuse_noncartesian(lin_tfm, name):
+    """the one-SGD-step rule divides by K = num_sens * W, a count of grid lines: it has no meaning off the grid"""
+    if isinstance(lin_tfm, NonCartesianSENSE):
+        raise NotImplementedError(f"{name}: no rule for a non-Cartesian operator (NonCartesianSENSE); use L2PenaltyCG, the "
+                                  "exact proximal")
 
 
 def _singlecoil(lin_tfm, z, y, coef, mode):
@@ -35,6 +43,10 @@ class Proximal(object):
 
 
 class L2Penalty(Proximal):
+    def __init__(self, lin_tfm: LinearTransform):
+        _refuse_noncartesian(lin_tfm, "L2Penalty")
+        super(L2Penalty, self).__init__(lin_tfm)
+
     def coef(self, alpha, lamda, z_shape):
         if isinstance(self.lin_tfm, SENSE):
             K = self.lin_tfm.sens_maps.shape[-3] * z_shape[-1]
@@ -111,6 +123,7 @@ class Constrained(Proximal):
 
 class SingleCoil(Proximal):
     def __init__(self, lin_tfm: RandomUndersamplingFourier):
+        _refuse_noncartesian(lin_tfm, "SingleCoil")
         super(SingleCoil, self).__init__(lin_tfm)
         assert isinstance(self.lin_tfm, RandomUndersamplingFourier), "only supporting RandomUnversamplingFourier"
 
@@ -162,6 +175,14 @@ class L2PenaltyCG(Proximal):
             o_re, o_im, self.last_iters = ops.sense_cgprox(
                 zr[..., 0].contiguous(), zr[..., 1].contiguous(), y, self.lin_tfm.sens_dev(z.device),
                 self.lin_tfm.mask_u8(z.device), a, max_iter=self.max_iter, tol=self.tol)
+            return torch.complex(o_re, o_im)
+        if isinstance(self.lin_tfm, NonCartesianSENSE):
+            # y: the samples (n, B, 1, M); A^H W y by the direct transform, then the Toeplitz CG
+            lin = self.lin_tfm
+            zr = torch.view_as_real(z)
+            o_re, o_im, self.last_iters = ops.nc_sense_cgprox(
+                zr[..., 0].contiguous(), zr[..., 1].contiguous(), lin.adjoint_weighted(y).contiguous(),
+                lin.sens_dev(z.device), lin.psf_dev(z.device), a, max_iter=self.max_iter, tol=self.tol)
             return torch.complex(o_re, o_im)
         if isinstance(self.lin_tfm, RandomUndersamplingFourier):
             self.last_iters = None

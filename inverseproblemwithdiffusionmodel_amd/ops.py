@@ -1161,6 +1161,213 @@ def pc_singlecoil_step(x_re, x_im, g_re, g_im, y, mask_u8, mode, step=0.0, noise
     _written(x_re, x_im)
 
 
+# ---- non-Cartesian SENSE (csrc/kspace_nc.hip, the Toeplitz chain of kspace_large.hip) ---------------------
+NC_SIZE_RULE = "the padded grid 2H x 2W must be a served k-space size: " + KSPACE_SIZE_RULE + ", for 2H and 2W"
+
+
+def nc_supported(H, W):
+    """whether the non-Cartesian operators serve an H x W image (NC_SIZE_RULE: kspace_size_class(2H, 2W) != 0).  Needs no
+    GPU."""
+    return bool(_lib.lib.ipdm_nc_supported(int(H), int(W)))
+
+
+def _nc_unsupported(H, W, what):
+    if not nc_supported(H, W):
+        raise _lib.IpdmUnsupported(f"{what}: no non-Cartesian kernel for {H}x{W}: {NC_SIZE_RULE}")
+
+
+def _nc_operand(t, dtype, name, what):
+    """operand read through a raw pointer: a contiguous GPU tensor of exactly this dtype, never converted"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"ipdm {what}: {name} must be a GPU tensor (the HIP path has no CPU fallback)")
+    if t.dtype != dtype:
+        raise TypeError(f"ipdm {what}: {name} must be {dtype}, got {t.dtype}")
+    if not t.is_contiguous():
+        raise TypeError(f"ipdm {what}: {name} must be contiguous (call .contiguous() and keep the result)")
+    return t
+
+
+def _nc_traj(traj, weights, what):
+    """-> M of a device trajectory float64 [M, 2] (and weights float32 [M], optional)"""
+    _nc_operand(traj, torch.float64, "trajectory", what)
+    if traj.dim() != 2 or traj.shape[1] != 2 or traj.shape[0] < 1:
+        raise ValueError(f"ipdm {what}: trajectory {tuple(traj.shape)} is not (M, 2)")
+    M = traj.shape[0]
+    if weights is not None:
+        _nc_operand(weights, torch.float32, "weights", what)
+        if tuple(weights.shape) != (M,):
+            raise ValueError(f"ipdm {what}: weights {tuple(weights.shape)} do not match the {M} samples")
+    return M
+
+
+def _nc_sens(sens, H, W, what):
+    """-> n_coils of complex64 maps [n, H, W] (None: 1, S = 1)"""
+    if sens is None:
+        return 1
+    _nc_operand(sens, torch.complex64, "coil maps", what)
+    if sens.dim() != 3 or tuple(sens.shape[-2:]) != (H, W) or sens.shape[0] < 1:
+        raise ValueError(f"ipdm {what}: coil maps {tuple(sens.shape)} do not match [n_coils, {H}, {W}]")
+    return sens.shape[0]
+
+
+def _nc_table_work(nbytes, device):
+    return torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=device)
+
+
+def ndft_forward(x, traj, sens=None):
+    """exact non-uniform DFT of images at the trajectory's samples (ipdm.h, ipdm_ndft_forward_c64).
+    sens [n, H, W]: x [B, H, W] (or [B, 1, H, W]) -> y [n, B, M] = A x;  sens None: x [n, B, H, W] coil images -> [n, B, M]"""
+    what = "ndft_forward"
+    _nc_operand(x, torch.complex64, "x", what)
+    M = _nc_traj(traj, None, what)
+    H, W = x.shape[-2:]
+    n = _nc_sens(sens, H, W, what)
+    if sens is None:
+        if x.dim() < 3:
+            raise ValueError(f"ipdm {what}: without coil maps x is [n_coils, B, H, W], got {tuple(x.shape)}")
+        n = x.shape[0]
+        B = x.numel() // (n * H * W)
+    else:
+        B = x.numel() // (H * W)
+    _nc_unsupported(H, W, what)
+    y = torch.empty((n, B, M), dtype=torch.complex64, device=x.device)
+    work = _nc_table_work(_lib.lib.ipdm_ndft_workspace_bytes(M, H, W), x.device)
+    call("ipdm_ndft_forward_c64", _ptr(x), _ptr(sens), _ptr(traj), _ptr(y), _ptr(work), B, n, M, H, W, _stream())
+    return y
+
+
+def ndft_adjoint(y, traj, H, W, sens=None, weights=None):
+    """adjoint of ndft_forward, the samples weighted first.  y [n, B, M] -> sens [n, H, W]: A^H W y [B, H, W]; sens None: the
+    coil images [n, B, H, W]"""
+    what = "ndft_adjoint"
+    _nc_operand(y, torch.complex64, "y", what)
+    M = _nc_traj(traj, weights, what)
+    if y.dim() != 3 or y.shape[-1] != M:
+        raise ValueError(f"ipdm {what}: y {tuple(y.shape)} is not [n_coils, B, {M}]")
+    n, B = y.shape[0], y.shape[1]
+    if sens is not None and _nc_sens(sens, H, W, what) != n:
+        raise ValueError(f"ipdm {what}: {n} coil signals, {sens.shape[0]} coil maps")
+    _nc_unsupported(H, W, what)
+    x = torch.empty((B, H, W) if sens is not None else (n, B, H, W), dtype=torch.complex64, device=y.device)
+    work = _nc_table_work(_lib.lib.ipdm_ndft_workspace_bytes(M, H, W), y.device)
+    call("ipdm_ndft_adjoint_c64", _ptr(y), _ptr(sens), _ptr(traj), _ptr(weights), _ptr(x), _ptr(work), B, n, M, H, W, _stream())
+    return x
+
+
+def toeplitz_psf(traj, H, W, weights=None):
+    """the real spectrum P [2H, 2W] (float32) of the trajectory's Toeplitz kernel: A^H W A = crop F^-1 P F pad"""
+    what = "toeplitz_psf"
+    M = _nc_traj(traj, weights, what)
+    _nc_unsupported(H, W, what)
+    psf = torch.empty((2 * H, 2 * W), dtype=torch.float32, device=traj.device)
+    work = _nc_table_work(_lib.lib.ipdm_toeplitz_psf_workspace_bytes(M, H, W), traj.device)
+    call("ipdm_toeplitz_psf_f32", _ptr(traj), _ptr(weights), _ptr(psf), _ptr(work), M, H, W, _stream())
+    return psf
+
+
+def _nc_psf(psf, H, W, what):
+    _nc_operand(psf, torch.float32, "psf", what)
+    if tuple(psf.shape) != (2 * H, 2 * W):
+        raise ValueError(f"ipdm {what}: psf {tuple(psf.shape)} is not [{2 * H}, {2 * W}]")
+
+
+def toeplitz_normal(v, psf, sens=None):
+    """A^H W A v by the Toeplitz chain.  v complex64 [B, H, W] (or [B, 1, H, W]) -> the same shape"""
+    what = "toeplitz_normal"
+    _nc_operand(v, torch.complex64, "v", what)
+    H, W = v.shape[-2:]
+    B = v.numel() // (H * W) if H * W else 0
+    n = _nc_sens(sens, H, W, what)
+    _nc_psf(psf, H, W, what)
+    _nc_unsupported(H, W, what)
+    out = torch.empty_like(v)
+    work = torch.empty(_lib.lib.ipdm_toeplitz_workspace_bytes(B, n, H, W) // 4, dtype=torch.float32, device=v.device)
+    call("ipdm_toeplitz_normal_c64", _ptr(v), _ptr(sens), _ptr(psf), _ptr(out), _ptr(work), B, n, H, W, _stream())
+    return out
+
+
+def nc_sense_cg_workspace(B, n_coils, H, W, device):
+    """scratch tensor of the non-Cartesian conjugate-gradient proximal (the Toeplitz chain's rows, T v, r, p, state)"""
+    nbytes = _lib.lib.ipdm_nc_sense_cg_workspace_bytes(B, n_coils, H, W)
+    return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=device) if nbytes else None
+
+
+def _nc_cg_args(work, ahy, iters_out, B, n_coils, H, W, device, what):
+    need = _lib.lib.ipdm_nc_sense_cg_workspace_bytes(B, n_coils, H, W)
+    if work is None:
+        work = nc_sense_cg_workspace(B, n_coils, H, W, device)
+    elif (not isinstance(work, torch.Tensor) or not work.is_cuda or work.dtype != torch.float32 or not work.is_contiguous()
+            or work.numel() * 4 < need):
+        raise ValueError(f"{what}: `work` must be a contiguous float32 GPU tensor of >= {need} bytes "
+                         f"(ops.nc_sense_cg_workspace({B}, {n_coils}, {H}, {W}, device))")
+    if ahy is None:
+        raise ValueError(f"{what}: ahy = A^H W y is required (ops.ndft_adjoint): the iterations never apply A")
+    _inplace_operand(ahy, torch.complex64, "ahy")
+    if ahy.numel() != B * H * W:
+        raise ValueError(f"{what}: ahy {tuple(ahy.shape)} does not match the image batch [{B}, {H}, {W}]")
+    if iters_out is None:
+        iters_out = torch.zeros(B, dtype=torch.int32, device=device)
+    else:
+        _inplace_operand(iters_out, torch.int32, "iters_out")
+        if iters_out.numel() < B:
+            raise ValueError(f"{what}: iters_out holds {iters_out.numel()} < {B} entries")
+    return work, iters_out
+
+
+def nc_sense_cgprox(z_re, z_im, ahy, sens, psf, a, max_iter=10, tol=1e-5, out_re=None, out_im=None, work=None, iters_out=None):
+    """exact non-Cartesian SENSE proximal (I + a A^H W A) x = z + a ahy by conjugate gradients (sense_cgprox with the
+    Toeplitz operator; ahy = ndft_adjoint(y, ...), psf = toeplitz_psf(...)) -> (out_re, out_im, iters)"""
+    what = "nc_sense_cgprox"
+    max_iter, tol = _check_cg_scalars(max_iter, tol, what)
+    z_re, z_im = _nc_operand(z_re, torch.float32, "z_re", what), _nc_operand(z_im, torch.float32, "z_im", what)
+    H, W = z_re.shape[-2:]
+    B = z_re.numel() // (H * W) if H * W else 0
+    if z_im.shape != z_re.shape:
+        raise ValueError(f"{what}: z_re {tuple(z_re.shape)} and z_im {tuple(z_im.shape)} differ")
+    n = _nc_sens(sens, H, W, what)
+    _nc_psf(psf, H, W, what)
+    _nc_unsupported(H, W, what)
+    work, iters_out = _nc_cg_args(work, ahy, iters_out, B, n, H, W, z_re.device, what)
+    out_re = torch.empty_like(z_re) if out_re is None else _inplace_operand(out_re, torch.float32, "out_re")
+    out_im = torch.empty_like(z_im) if out_im is None else _inplace_operand(out_im, torch.float32, "out_im")
+    call("ipdm_nc_sense_cgprox_f32", _ptr(z_re), _ptr(z_im), _ptr(sens), _ptr(psf), float(a), _ptr(ahy), max_iter, tol,
+         _ptr(out_re), _ptr(out_im), _ptr(work), _ptr(iters_out), B, n, H, W, _stream())
+    _written(out_re, out_im, iters_out)
+    return out_re, out_im, iters_out
+
+
+def ald_nc_sense_cg_step(x_re, x_im, g_re, g_im, ahy, sens, psf, work, step=0.0, noise_scale=0.0, coef=0.0, noise_re=None,
+                         noise_im=None, seed=0, sample_offset=0, step_id=0, dev_sched=None, sample_sched=None, max_iter=10,
+                         tol=1e-5, iters_out=None):
+    """ald_sense_cg_step for the non-Cartesian operator: Langevin update, then nc_sense_cgprox, in place on x_re / x_im.
+    sample_sched: a schedule record per sample (pc_sense_step).  -> iters (device int32 [B])"""
+    what = "ald_nc_sense_cg_step"
+    max_iter, tol = _check_cg_scalars(max_iter, tol, what)
+    for t, nm in ((x_re, "x_re"), (x_im, "x_im"), (g_re, "g_re"), (g_im, "g_im")):
+        _inplace_operand(t, torch.float32, nm)
+    for t, nm in ((noise_re, "noise_re"), (noise_im, "noise_im")):
+        if t is not None:
+            _inplace_operand(t, torch.float32, nm)
+    if (noise_re is None) != (noise_im is None):
+        raise ValueError(f"{what}: pass both noise planes or neither")
+    H, W = x_re.shape[-2:]
+    B = x_re.numel() // (H * W) if H * W else 0
+    if any(t.numel() != x_re.numel() for t in (x_im, g_re, g_im)) or any(
+            t is not None and t.numel() != x_re.numel() for t in (noise_re, noise_im)):
+        raise ValueError(f"{what}: operand sizes do not match the state")
+    n = _nc_sens(sens, H, W, what)
+    _nc_psf(psf, H, W, what)
+    _nc_unsupported(H, W, what)
+    head = (_ptr(x_re), _ptr(x_im), _ptr(g_re), _ptr(g_im), _ptr(noise_re), _ptr(noise_im), float(step), float(noise_scale),
+            int(seed), int(sample_offset), int(step_id), _ptr(dev_sched))
+    head = _pc_head(what, head, B, dev_sched, sample_sched)
+    work, iters_out = _nc_cg_args(work, ahy, iters_out, B, n, H, W, x_re.device, what)
+    call("ipdm_ald_nc_sense_cg_step_f32", *head, _ptr(sens), _ptr(psf), float(coef), _ptr(work), _ptr(ahy), max_iter, tol,
+         _ptr(iters_out), B, n, H, W, _stream())
+    _written(x_re, x_im, iters_out)
+    return iters_out
+
+
 # ---- segmentation-likelihood guidance glue ----------------------------------------------------------
 def zero_insert2(x):
     """(..., H, W) -> (..., 2H, 2W): x at the even positions, zeros elsewhere"""

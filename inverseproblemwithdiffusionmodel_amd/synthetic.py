@@ -122,3 +122,32 @@ def vd_mask_2d(H, W, R, center_frac=0.04, seed=0, partial_fourier=None):
     if partial_fourier is not None:
         mask[int(round(partial_fourier * H)):] = False
     return torch.from_numpy(mask)[None, None]
+
+
+def radial_trajectory(n_spokes, n_readout, H, W, golden_angle=True):
+    """float64 (n_spokes * n_readout, 2) radial k-space trajectory, (k_y, k_x) in cycles per field of view: spokes through
+    the centre, readout position t = (j - n_readout/2) / n_readout in [-1/2, 1/2), spoke i at angle i * pi (sqrt(5) - 1) / 2
+    (golden angle) or i * pi / n_spokes (uniform); k_y = t sin(angle) H, k_x = t cos(angle) W, inside [-N/2, N/2]."""
+    import numpy as np
+    if any(isinstance(v, bool) or int(v) != v or v < 1 for v in (n_spokes, n_readout, H, W)):
+        raise ValueError(f"radial_trajectory: positive integers expected, got {(n_spokes, n_readout, H, W)}")
+    t = (np.arange(int(n_readout), dtype=np.float64) - n_readout / 2.0) / n_readout
+    i = np.arange(int(n_spokes), dtype=np.float64)
+    ang = i * (np.pi * (np.sqrt(5.0) - 1.0) / 2.0) if golden_angle else i * (np.pi / n_spokes)
+    ky = t[None, :] * np.sin(ang)[:, None] * H
+    kx = t[None, :] * np.cos(ang)[:, None] * W
+    return torch.from_numpy(np.stack([ky.reshape(-1), kx.reshape(-1)], axis=1))
+
+
+def radial_density(trajectory, H, W):
+    """float64 (M,) ramp density compensation of a radial trajectory: w proportional to the normalised radius
+    sqrt((k_y/H)^2 + (k_x/W)^2), the centre samples at half the smallest non-zero radius, normalised to sum w = H W.  For
+    the zero-filled image only; the likelihood's weights stay 1."""
+    k = torch.as_tensor(trajectory, dtype=torch.float64)
+    if k.dim() != 2 or k.shape[1] != 2 or k.shape[0] < 1:
+        raise ValueError(f"radial_density: trajectory {tuple(k.shape)} is not (M, 2)")
+    r = torch.sqrt((k[:, 0] / H) ** 2 + (k[:, 1] / W) ** 2)
+    pos = r[r > 0]
+    floor = 0.5 * float(pos.min()) if pos.numel() else 1.0
+    r = torch.where(r > 0, r, torch.full_like(r, floor))
+    return r * (float(H * W) / float(r.sum()))

@@ -10,7 +10,11 @@ Samples are sharded over the launched ranks (torchrun) and rank 0 writes the pos
 A stack of slices in ONE batch: --n_slices S simulates S slices (phantom seeds seed .. seed + S - 1, coil maps per slice),
 --kspace PATH --slices reads a measured stack (S, n_coils, H, W).  --num_samples then counts samples PER SLICE: the batch
 axis of reconstructions.pt has num_samples * S rows in the order sample * S + slice, sens_maps.pt is (S, n, H, W), and
-posterior_slices.pt holds the per-slice mean / std over the rows b % S == s.  One process only (no sharded volumes)."""
+posterior_slices.pt holds the per-slice mean / std over the rows b % S == s.  One process only (no sharded volumes).
+Non-Cartesian sampling: --trajectory radial --spokes N [--readout M] simulates a golden-angle radial acquisition of the
+phantom, --trajectory PATH one on the (M, 2) positions of a file, --kspace PATH --trajectory PATH --sens_maps PATH
+reconstructs measured samples (n_coils, M).  The proximal is then L2PenaltyCG; trajectory.pt is written instead of
+mask.pt and ZF.pt is the density-compensated adjoint."""
 import argparse
 import os
 import pickle
@@ -35,8 +39,9 @@ if __name__ == '__main__':
     parser.add_argument("--step_lr", type=float, default=0.0000009)
     parser.add_argument("--num_steps_each", type=int, default=3)
     parser.add_argument("--lr_scaled", type=float, default=1.)
-    parser.add_argument("--proximal_type", default="L2Penalty", choices=PROXIMAL_NAMES,
-                        help="data-consistency operator; L2PenaltyCG: the exact multi-coil proximal by conjugate gradients")
+    parser.add_argument("--proximal_type", default=None, choices=PROXIMAL_NAMES,
+                        help="data-consistency operator (default L2Penalty; with --trajectory: L2PenaltyCG, the only one); "
+                             "L2PenaltyCG: the exact multi-coil proximal by conjugate gradients")
     parser.add_argument("--cg_iters", type=int, default=10, help="L2PenaltyCG: CG iterations at most")
     parser.add_argument("--cg_tol", type=float, default=1e-5, help="L2PenaltyCG: stop at |r| <= cg_tol |b|")
     parser.add_argument("--num_samples", type=int, default=1)
@@ -87,6 +92,12 @@ if __name__ == '__main__':
                         help="--kspace: factor on the measurement; auto: 1 / the peak of its calibration image")
     from inverseproblemwithdiffusionmodel_amd.helpers.load_data import add_maps_method_args, driver_maps_method
     add_maps_method_args(parser)
+    parser.add_argument("--trajectory", default=None, metavar="radial|PATH",
+                        help="non-Cartesian sampling: 'radial' (golden-angle spokes, --spokes / --readout) or a .npy / .pt file "
+                             "with (M, 2) positions (k_y, k_x) in cycles per field of view; implies --proximal_type L2PenaltyCG")
+    parser.add_argument("--spokes", type=int, default=None, metavar="N", help="--trajectory radial: number of spokes")
+    parser.add_argument("--readout", type=int, default=None, metavar="M",
+                        help="--trajectory radial: samples per spoke (default: 2 x the larger image side)")
     parser.add_argument("--seg_synthetic", action="store_true",
                         help="run the guidance with seeded random UNet weights (exercises the path; not meaningful imaging)")
     args_dict = vars(parser.parse_args())
@@ -109,7 +120,50 @@ if __name__ == '__main__':
     H = args_dict["image_size"]
     W = args_dict["image_width"] if args_dict["image_width"] is not None else H
     kspace = None
-    if args_dict["kspace"]:
+    trajectory = None
+    if args_dict["trajectory"]:                                           # every refusal before the network is built
+        if args_dict["proximal_type"] not in (None, "L2PenaltyCG"):
+            sys.exit(f"--trajectory: non-Cartesian SENSE takes --proximal_type L2PenaltyCG, not {args_dict['proximal_type']}")
+        args_dict["proximal_type"] = "L2PenaltyCG"
+        for flag in ("mask", "mask_2d", "estimate_maps", "coil_compress", "noise_cov", "slices", "n_slices"):
+            if args_dict[flag] not in (None, False):
+                sys.exit(f"--trajectory does not go with --{flag}: non-Cartesian SENSE takes given coil maps, one slice and no "
+                         "sampling mask")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            sys.exit("--trajectory: one process (sharded non-Cartesian runs are not built)")
+        from inverseproblemwithdiffusionmodel_amd import ops
+        from inverseproblemwithdiffusionmodel_amd.helpers.load_data import load_kspace, load_trajectory
+        from inverseproblemwithdiffusionmodel_amd.ncsn.linear_transforms.noncartesian import check_trajectory
+        from inverseproblemwithdiffusionmodel_amd.synthetic import radial_trajectory
+        if not ops.nc_supported(H, W):
+            sys.exit(f"--image_size {H} --image_width {W}: no non-Cartesian kernel for {H}x{W}; {ops.NC_SIZE_RULE}")
+        try:
+            if args_dict["trajectory"] == "radial":
+                if args_dict["spokes"] is None or args_dict["spokes"] < 1:
+                    sys.exit("--trajectory radial needs --spokes N (>= 1)")
+                if args_dict["kspace"]:
+                    sys.exit("--kspace PATH needs --trajectory PATH, the positions of its samples")
+                readout = args_dict["readout"] if args_dict["readout"] is not None else 2 * max(H, W)
+                trajectory = radial_trajectory(args_dict["spokes"], readout, H, W)
+            else:
+                if args_dict["spokes"] is not None or args_dict["readout"] is not None:
+                    sys.exit("--spokes / --readout go with --trajectory radial")
+                trajectory = load_trajectory(args_dict["trajectory"])
+            trajectory = check_trajectory(trajectory, H, W, "--trajectory")
+            if args_dict["kspace"]:
+                if not args_dict["sens_maps"] or args_dict["sens_phase"]:
+                    sys.exit("--kspace PATH --trajectory PATH needs --sens_maps PATH (maps are not estimated from non-Cartesian data)")
+                kspace = load_kspace(args_dict["kspace"], noncartesian=True)
+                if kspace.shape[1] != trajectory.shape[0]:
+                    sys.exit(f"--kspace holds {tuple(kspace.shape)}; (n_coils, {trajectory.shape[0]}) expected for this trajectory")
+                args_dict["num_sens"] = int(kspace.shape[0])
+        except (ValueError, TypeError) as e:
+            sys.exit(str(e))
+    elif args_dict["spokes"] is not None or args_dict["readout"] is not None:
+        sys.exit("--spokes / --readout go with --trajectory radial")
+    if args_dict["proximal_type"] is None:
+        args_dict["proximal_type"] = "L2Penalty"
+    if args_dict["kspace"] and trajectory is None:
         if not args_dict["mask"]:
             sys.exit("--kspace PATH needs --mask PATH, the sampling mask of the acquisition")
         if bool(args_dict["sens_maps"]) == args_dict["estimate_maps"] or args_dict["sens_phase"]:
@@ -133,11 +187,12 @@ if __name__ == '__main__':
                      f"{H}, {W}), shared by its slices")
     kspace_scale = None if args_dict["kspace_scale"] == "auto" else float(args_dict["kspace_scale"])
     from inverseproblemwithdiffusionmodel_amd import ops
-    if ops.kspace_size_class(H, W) == ops.KSPACE_NONE:                    # before any allocation
+    if trajectory is None and ops.kspace_size_class(H, W) == ops.KSPACE_NONE:     # before any allocation
         sys.exit(f"--image_size {H} --image_width {W}: no k-space kernel for {H}x{W}; {ops.KSPACE_SIZE_RULE}")
     # the mask, and the calibration region the run depends on, before the score network is built or a GPU is touched
     from inverseproblemwithdiffusionmodel_amd.helpers.load_data import driver_mask
-    mask = driver_mask(args_dict["mask"], args_dict["mask_2d"], H, W, args_dict["R"], args_dict["seed"])
+    mask = None if trajectory is not None else driver_mask(args_dict["mask"], args_dict["mask_2d"], H, W, args_dict["R"],
+                                                           args_dict["seed"])
     noise_cov = region = None
     if args_dict["noise_cov"] and args_dict["coil_compress"] is None:
         sys.exit("--noise_cov PATH goes with --coil_compress N (whitening is part of the compression)")
@@ -149,7 +204,8 @@ if __name__ == '__main__':
                 noise_cov = ops.check_noise_cov(load_noise_cov(args_dict["noise_cov"]), args_dict["num_sens"], "--noise_cov")
         except (ValueError, TypeError, NotImplementedError) as e:
             sys.exit(str(e))
-    if args_dict["estimate_maps"] or args_dict["coil_compress"] is not None or (kspace is not None and kspace_scale is None):
+    if trajectory is None and (args_dict["estimate_maps"] or args_dict["coil_compress"] is not None
+                               or (kspace is not None and kspace_scale is None)):
         from inverseproblemwithdiffusionmodel_amd.ncsn.linear_transforms import undersampling_fourier as uf
         try:
             region = uf.calibration_region(mask if mask is not None else
@@ -202,7 +258,8 @@ if __name__ == '__main__':
                                 maps_method=maps_method, maps_kwargs=maps_kwargs,
                                 proximal=args_dict["proximal_type"],
                                 proximal_kwargs=(dict(max_iter=args_dict["cg_iters"], tol=args_dict["cg_tol"])
-                                                 if args_dict["proximal_type"] == "L2PenaltyCG" else None))
+                                                 if args_dict["proximal_type"] == "L2PenaltyCG" else None),
+                                trajectory=trajectory)
     label = None
     if args_dict["seg_start_time"] < 1.:
         from inverseproblemwithdiffusionmodel_amd.helpers.load_model import reload_model
@@ -221,7 +278,8 @@ if __name__ == '__main__':
     if rank == 0:
         os.makedirs(save_dir, exist_ok=True)
     S = prob.n_slices if stack else 1                                 # rows of one sample: its slices, in order
-    direct_recons = prob.op.conj_op(prob.measurement[:, :S])
+    # non-Cartesian: the density-compensated adjoint (the plain adjoint of radial data is a blur)
+    direct_recons = prob.zero_filled if trajectory is not None else prob.op.conj_op(prob.measurement[:, :S])
 
     t0 = time.time()
     kw = dict(prob.call_kwargs, label=label, lamda=args_dict["lamda"], save_dir=save_dir, seg_mode=args_dict["seg_mode"],
@@ -254,7 +312,10 @@ if __name__ == '__main__':
         torch.save(prob.measurement[:, :S].cpu(), os.path.join(save_dir, "measurement.pt"))
         torch.save(img_out.cpu(), os.path.join(save_dir, "reconstructions.pt"))
         torch.save(direct_recons.cpu(), os.path.join(save_dir, "ZF.pt"))
-        torch.save(prob.op.random_under_fourier.mask, os.path.join(save_dir, "mask.pt"))
+        if trajectory is not None:
+            torch.save(prob.op.trajectory, os.path.join(save_dir, "trajectory.pt"))
+        else:
+            torch.save(prob.op.random_under_fourier.mask, os.path.join(save_dir, "mask.pt"))
         if sens_maps is not None or prob.estimated_maps or prob.coil_matrix is not None or stack:
             torch.save(prob.op.sens_maps, os.path.join(save_dir, "sens_maps.pt"))
         if prob.coil_matrix is not None:
