@@ -531,6 +531,36 @@ int ipdm_ald_nc_sense_cg_step_f32(float* x_re, float* x_im, const float* g_re, c
                                   const ipdm_sched_t* dev_sched, int sched_stride, const float* sens, const float* psf,
                                   float coef, float* work, const float* ahy, int max_iter, float tol, int32_t* iters_out,
                                   int B, int n_coils, int H, int W, void* stream);
+/* Frame sets (radial cine): one trajectory per frame, the ipdm_*_sets_* rule a third time.
+ *   traj      device float64 [T][M][2], T = traj_sets >= 1 frames of M samples each (frames of unequal length: pad to one M
+ *             and give the padding weight 0)
+ *   weights   device float32 [T][M] or NULL
+ *   psf       float32 [T][2H][2W], set t from trajectory t (and weights t); T = psf_sets
+ * Image row b of every operand ([B][H][W], [n_coils][B][M], ahy, iters_out, the schedule records) reads set b % T, so a
+ * (posterior sample, frame) batch flattened frame-fastest is served as it lies in memory.  B % T != 0, T < 1: IPDM_EINVAL.
+ * T * M beyond INT32_MAX: IPDM_EUNSUPPORTED.  The two transforms need ipdm_ndft_workspace_bytes(T * M, H, W) -- the phasor
+ * tables cover all T * M samples --, the psf call ipdm_toeplitz_psf_workspace_bytes(M, H, W) (the sets are formed one
+ * after another through it), the others the workspace of their one-set form.  Every sum of row b runs in the order the
+ * one-set entry point has for trajectory b % T: its rows equal, bit for bit, the rows of that call on the same batch.
+ * The iteration path gains no launch: the column pass offsets its psf read by (b % T) * 4HW, a workgroup-uniform value.
+ * The entry points above are these with T = 1. */
+int ipdm_ndft_forward_sets_c64(const float* x, const float* sens, const double* traj, int traj_sets, float* y, float* work,
+                               int B, int n_coils, int M, int H, int W, void* stream);
+int ipdm_ndft_adjoint_sets_c64(const float* y, const float* sens, const double* traj, int traj_sets, const float* weights,
+                               float* x, float* work, int B, int n_coils, int M, int H, int W, void* stream);
+int ipdm_toeplitz_psf_sets_f32(const double* traj, int traj_sets, const float* weights, float* psf, float* work, int M, int H,
+                               int W, void* stream);
+int ipdm_toeplitz_normal_sets_c64(const float* v, const float* sens, const float* psf, int psf_sets, float* out, float* work,
+                                  int B, int n_coils, int H, int W, void* stream);
+int ipdm_nc_sense_cgprox_sets_f32(const float* z_re, const float* z_im, const float* sens, const float* psf, int psf_sets,
+                                  float a, const float* ahy, int max_iter, float tol, float* out_re, float* out_im,
+                                  float* work, int32_t* iters_out, int B, int n_coils, int H, int W, void* stream);
+int ipdm_ald_nc_sense_cg_step_sets_f32(float* x_re, float* x_im, const float* g_re, const float* g_im,
+                                       const float* noise_re, const float* noise_im,
+                                       float step, float noise_scale, uint64_t seed, int64_t sample_offset, int64_t step_id,
+                                       const ipdm_sched_t* dev_sched, int sched_stride, const float* sens, const float* psf,
+                                       int psf_sets, float coef, float* work, const float* ahy, int max_iter, float tol,
+                                       int32_t* iters_out, int B, int n_coils, int H, int W, void* stream);
 
 /* Langevin update alone (ALD_optimizers.py:117): x += step*g + noise_scale*noise ; noise NULL -> Philox. */
 int ipdm_langevin_step_f32(float* x, const float* g, const float* noise, float step, float noise_scale,

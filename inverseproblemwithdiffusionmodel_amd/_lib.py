@@ -120,6 +120,14 @@ SIGNATURES = {
     "ipdm_nc_sense_cgprox_f32": [P, P, P, P, c_float, P, c_int, c_float, P, P, P, P, c_int, c_int, c_int, c_int, P],
     "ipdm_ald_nc_sense_cg_step_f32": [P, P, P, P, P, P, c_float, c_float, c_uint64, c_int64, c_int64, P, c_int,
                                       P, P, c_float, P, P, c_int, c_float, P, c_int, c_int, c_int, c_int, P],
+    # ... with one trajectory / psf per frame: the set count follows the trajectory / psf pointer
+    "ipdm_ndft_forward_sets_c64": [P, P, P, c_int, P, P, c_int, c_int, c_int, c_int, c_int, P],
+    "ipdm_ndft_adjoint_sets_c64": [P, P, P, c_int, P, P, P, c_int, c_int, c_int, c_int, c_int, P],
+    "ipdm_toeplitz_psf_sets_f32": [P, c_int, P, P, P, c_int, c_int, c_int, P],
+    "ipdm_toeplitz_normal_sets_c64": [P, P, P, c_int, P, P, c_int, c_int, c_int, c_int, P],
+    "ipdm_nc_sense_cgprox_sets_f32": [P, P, P, P, c_int, c_float, P, c_int, c_float, P, P, P, P, c_int, c_int, c_int, c_int, P],
+    "ipdm_ald_nc_sense_cg_step_sets_f32": [P, P, P, P, P, P, c_float, c_float, c_uint64, c_int64, c_int64, P, c_int,
+                                           P, P, c_int, c_float, P, P, c_int, c_float, P, c_int, c_int, c_int, c_int, P],
     "ipdm_langevin_step_f32": [P, P, P, c_float, c_float, c_uint64, c_int64, c_int64, P, c_int64, c_int64, P],
     "ipdm_philox_normal_f32": [P, c_uint64, c_int64, c_int64, c_int, c_int64, c_int64, P],
     "ipdm_philox_block_host": [c_uint64, c_int64, c_int64, c_int, ctypes.c_uint32, P],

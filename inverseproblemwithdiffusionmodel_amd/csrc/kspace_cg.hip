@@ -330,18 +330,46 @@ extern "C" int64_t ipdm_nc_sense_cg_workspace_bytes(int B, int n_coils, int H, i
   return (2 * (int64_t)n_coils + 3) * B * H * W * (int64_t)sizeof(float2) + (int64_t)B * (int64_t)sizeof(CgState);
 }
 
-extern "C" int ipdm_nc_sense_cgprox_f32(const float* z_re, const float* z_im, const float* sens, const float* psf, float a,
-                                        const float* ahy, int max_iter, float tol, float* out_re, float* out_im, float* work,
-                                        int32_t* iters_out, int B, int n_coils, int H, int W, void* stream) {
-  IPDM_REQUIRE(nc_cg_dims_ok(B, n_coils, H, W) && cg_scalars_ok(max_iter, tol) && (sens || n_coils == 1));
+// psf [psf_sets][2H][2W]: image row b solves with set b % psf_sets (frames); the launch sequence is the same
+extern "C" int ipdm_nc_sense_cgprox_sets_f32(const float* z_re, const float* z_im, const float* sens, const float* psf,
+                                             int psf_sets, float a, const float* ahy, int max_iter, float tol, float* out_re,
+                                             float* out_im, float* work, int32_t* iters_out, int B, int n_coils, int H, int W,
+                                             void* stream) {
+  IPDM_REQUIRE(nc_cg_dims_ok(B, n_coils, H, W) && cg_scalars_ok(max_iter, tol) && (sens || n_coils == 1) && psf_sets >= 1 &&
+               B % psf_sets == 0);
   if (B == 0) return IPDM_OK;
   if (!nc_cg_served(B, n_coils, H, W)) return IPDM_EUNSUPPORTED;
   IPDM_REQUIRE(z_re && z_im && psf && ahy && out_re && out_im && work);
   hipStream_t st = ipdm_stream(stream);
   const int rc = copy_planes(out_re, out_im, z_re, z_im, (size_t)B * H * W, st);
-  const ToepProblem tp{reinterpret_cast<const float2*>(sens), psf, B, n_coils, H, W};
+  const ToepProblem tp{reinterpret_cast<const float2*>(sens), psf, B, n_coils, H, W, psf_sets};
   return rc ? rc : nc_cg_solve(out_re, out_im, NO_LANGEVIN, tp, a, reinterpret_cast<const float2*>(ahy), max_iter, tol, work,
                                iters_out, st);
+}
+
+extern "C" int ipdm_nc_sense_cgprox_f32(const float* z_re, const float* z_im, const float* sens, const float* psf, float a,
+                                        const float* ahy, int max_iter, float tol, float* out_re, float* out_im, float* work,
+                                        int32_t* iters_out, int B, int n_coils, int H, int W, void* stream) {
+  return ipdm_nc_sense_cgprox_sets_f32(z_re, z_im, sens, psf, 1, a, ahy, max_iter, tol, out_re, out_im, work, iters_out, B,
+                                       n_coils, H, W, stream);
+}
+
+extern "C" int ipdm_ald_nc_sense_cg_step_sets_f32(float* x_re, float* x_im, const float* g_re, const float* g_im,
+                                                  const float* noise_re, const float* noise_im, float step, float noise_scale,
+                                                  uint64_t seed, int64_t sample_offset, int64_t step_id,
+                                                  const ipdm_sched_t* dev_sched, int sched_stride, const float* sens,
+                                                  const float* psf, int psf_sets, float coef, float* work, const float* ahy,
+                                                  int max_iter, float tol, int32_t* iters_out, int B, int n_coils, int H, int W,
+                                                  void* stream) {
+  IPDM_REQUIRE(nc_cg_dims_ok(B, n_coils, H, W) && cg_scalars_ok(max_iter, tol) && (sens || n_coils == 1) &&
+               sched_stride_ok(dev_sched, sched_stride) && psf_sets >= 1 && B % psf_sets == 0);
+  if (B == 0) return IPDM_OK;
+  if (!nc_cg_served(B, n_coils, H, W)) return IPDM_EUNSUPPORTED;
+  IPDM_REQUIRE(x_re && x_im && g_re && g_im && (noise_re == nullptr) == (noise_im == nullptr) && psf && ahy && work);
+  const LangevinArgs lg{g_re, g_im, noise_re, noise_im, step, noise_scale, seed, sample_offset, step_id, dev_sched, sched_stride};
+  const ToepProblem tp{reinterpret_cast<const float2*>(sens), psf, B, n_coils, H, W, psf_sets};
+  return nc_cg_solve(x_re, x_im, lg, tp, coef, reinterpret_cast<const float2*>(ahy), max_iter, tol, work, iters_out,
+                     ipdm_stream(stream));
 }
 
 extern "C" int ipdm_ald_nc_sense_cg_step_f32(float* x_re, float* x_im, const float* g_re, const float* g_im,
@@ -350,15 +378,9 @@ extern "C" int ipdm_ald_nc_sense_cg_step_f32(float* x_re, float* x_im, const flo
                                              const ipdm_sched_t* dev_sched, int sched_stride, const float* sens,
                                              const float* psf, float coef, float* work, const float* ahy, int max_iter, float tol,
                                              int32_t* iters_out, int B, int n_coils, int H, int W, void* stream) {
-  IPDM_REQUIRE(nc_cg_dims_ok(B, n_coils, H, W) && cg_scalars_ok(max_iter, tol) && (sens || n_coils == 1) &&
-               sched_stride_ok(dev_sched, sched_stride));
-  if (B == 0) return IPDM_OK;
-  if (!nc_cg_served(B, n_coils, H, W)) return IPDM_EUNSUPPORTED;
-  IPDM_REQUIRE(x_re && x_im && g_re && g_im && (noise_re == nullptr) == (noise_im == nullptr) && psf && ahy && work);
-  const LangevinArgs lg{g_re, g_im, noise_re, noise_im, step, noise_scale, seed, sample_offset, step_id, dev_sched, sched_stride};
-  const ToepProblem tp{reinterpret_cast<const float2*>(sens), psf, B, n_coils, H, W};
-  return nc_cg_solve(x_re, x_im, lg, tp, coef, reinterpret_cast<const float2*>(ahy), max_iter, tol, work, iters_out,
-                     ipdm_stream(stream));
+  return ipdm_ald_nc_sense_cg_step_sets_f32(x_re, x_im, g_re, g_im, noise_re, noise_im, step, noise_scale, seed, sample_offset,
+                                            step_id, dev_sched, sched_stride, sens, psf, 1, coef, work, ahy, max_iter, tol,
+                                            iters_out, B, n_coils, H, W, stream);
 }
 
 extern "C" int64_t ipdm_sense_cg_workspace_bytes(int B, int n_coils, int H, int W) {

@@ -423,8 +423,9 @@ static inline int copy_planes(float* out_re, float* out_im, const float* z_re, c
 // Non-Cartesian SENSE: A^H W A is the Toeplitz operator of the real spectrum psf on the 2H x 2W grid.
 struct ToepProblem {
   const float2* sens;              // complex64 [n_coils][H][W]; NULL (n_coils == 1): S = 1
-  const float* psf;                // float32 [2H][2W]
+  const float* psf;                // float32 [psf_sets][2H][2W]
   int B, n_coils, H, W;
+  int psf_sets = 1;                // frames: image row b reads set b % psf_sets
 };
 
 }  // namespace ipdm_kspace

@@ -510,8 +510,9 @@ struct ToepRowsFwd {
 struct ToepCols {
   ToepGeo g;
   float2* ws;
-  const float* psf;                // [2H][2W]
+  const float* psf;                // [psf_sets][2H][2W]
   float scale2;                    // 1 / (4HW): the orthonormal pair's two factors
+  int psf_sets;                    // image row b reads set b % psf_sets (b is the workgroup's: a scalar offset)
   __device__ __forceinline__ float2 load(int b, int coil, int r, int c) const {
     const int r2 = r - g.H / 2;
     return (unsigned)r2 < (unsigned)g.H ? ws[g.ws_at(coil, b, r2, c)] : make_float2(0.f, 0.f);
@@ -521,8 +522,9 @@ struct ToepCols {
     if ((unsigned)r2 < (unsigned)g.H) ws[g.ws_at(coil, b, r2, c)] = v;
   }
   __device__ __forceinline__ bool skip(int, int, int) const { return false; }
-  __device__ __forceinline__ float2 mid(int, int, int r, int c, float2 v) const {
-    const float p = psf[(size_t)r * (2 * (size_t)g.W) + c] * scale2;
+  __device__ __forceinline__ float2 mid(int b, int, int r, int c, float2 v) const {
+    const float* __restrict__ ps = psf + (size_t)(b % psf_sets) * (4 * (size_t)g.H * g.W);
+    const float p = ps[(size_t)r * (2 * (size_t)g.W) + c] * scale2;
     return make_float2(v.x * p, v.y * p);
   }
 };
@@ -599,7 +601,7 @@ int toeplitz_normal(const float2* vc, const float* v_re, const float* v_im, cons
   ToepRowsFwd rf{g, vc, v_re, v_im, tp.sens, ws};
   int rc = launch_rows(rf, B, n, H, 2 * W, 0, s);
   if (rc) return rc;
-  ToepCols tc{g, ws, tp.psf, 0.25f / ((float)H * (float)W)};
+  ToepCols tc{g, ws, tp.psf, 0.25f / ((float)H * (float)W), tp.psf_sets};
   rc = launch_cols<ToepCols, true>(tc, B, n, 2 * H, 2 * W, 0, s);
   if (rc) return rc;
   const size_t lds = strip_lds_bytes(2 * W);

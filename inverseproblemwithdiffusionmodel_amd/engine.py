@@ -218,6 +218,9 @@ def _build_noncartesian(device, n_samples, H, W, num_sens, seed, scorenet, cfg, 
         get_proximal(proximal)
         raise ValueError(f"build_problem: proximal={proximal!r} does not serve a trajectory; non-Cartesian SENSE takes L2PenaltyCG")
     prox_cls = get_proximal("L2PenaltyCG")
+    if torch.as_tensor(trajectory).dim() > 2:
+        raise ValueError(f"build_problem: trajectory {tuple(torch.as_tensor(trajectory).shape)}: a 2-D problem takes (M, 2); one "
+                         "trajectory per frame (T, M, 2) is the 2D+time sampler's (ALD2DTime, scripts/cine_SENSE_real_img_2d_time.py)")
     if measurement is not None:
         if sens_maps is None:
             raise ValueError("build_problem(measurement=..., trajectory=...): pass sens_maps=, the coil maps (they cannot be "

@@ -228,13 +228,15 @@ def load_sens_maps(path):
 def load_kspace(path, cine=False, slices=False, noncartesian=False):
     """measured multi-coil k-space (n_coils, H, W) -- cine=True: 2D+time k-space (n_coils, T, H, W); slices=True: a stack
     of slices (S, n_coils, H, W); noncartesian=True: the samples of a trajectory (n_coils, M), in the order of
-    ``load_trajectory``'s positions -- from a ``.npy`` or ``.pt`` file -> host complex64 tensor, centred with orthonormal
+    ``load_trajectory``'s positions; noncartesian=True with cine=True: the samples of a framed trajectory (n_coils, T, M)
+    -- from a ``.npy`` or ``.pt`` file -> host complex64 tensor, centred with orthonormal
     scale as ``SENSE.__call__`` produces it (``engine.build_problem(measurement=...)``, ``SENSE.from_cine_measurement``);
     any other rank or a real dtype is a ValueError"""
     if cine and slices:
         raise ValueError("load_kspace: cine=True or slices=True, not both (a cine volume is not served)")
-    if noncartesian and (cine or slices):
-        raise ValueError("load_kspace: noncartesian=True goes with neither cine=True nor slices=True")
+    if noncartesian and slices:
+        raise ValueError("load_kspace: noncartesian=True takes cine=True (n_coils, T, M) or neither cine=True nor slices=True "
+                         "(n_coils, M); a stack of slices is not served")
     import numpy as np
     import torch
     ext = os.path.splitext(str(path))[1].lower()
@@ -247,8 +249,8 @@ def load_kspace(path, cine=False, slices=False, noncartesian=False):
     else:
         raise ValueError(f"load_kspace: {path!r}: a .npy or .pt file")
     if noncartesian:
-        if not isinstance(y, torch.Tensor) or y.dim() != 2:
-            raise ValueError(f"load_kspace: {path!r} must hold one array of shape (n_coils, M)")
+        if not isinstance(y, torch.Tensor) or y.dim() != (3 if cine else 2):
+            raise ValueError(f"load_kspace: {path!r} must hold one array of shape {'(n_coils, T, M)' if cine else '(n_coils, M)'}")
     elif not isinstance(y, torch.Tensor) or y.dim() != (4 if cine or slices else 3):
         raise ValueError(f"load_kspace: {path!r} must hold one array of shape "
                          f"{'(n_coils, T, H, W)' if cine else '(S, n_coils, H, W)' if slices else '(n_coils, H, W)'}")
@@ -257,10 +259,11 @@ def load_kspace(path, cine=False, slices=False, noncartesian=False):
     return y.to(torch.complex64).contiguous()
 
 
-def load_trajectory(path):
-    """k-space trajectory (M, 2) = (k_y, k_x) in cycles per field of view, real, from a ``.npy`` or ``.pt`` file -> host
-    float64 tensor for ``NonCartesianSENSE`` / ``engine.build_problem(trajectory=...)``; that it is finite and inside
-    [-N/2, N/2] is checked where the image size is known"""
+def load_trajectory(path, cine=False):
+    """k-space trajectory (M, 2) = (k_y, k_x) in cycles per field of view -- cine=True: (T, M, 2), one trajectory per frame
+    --, real, from a ``.npy`` or ``.pt`` file -> host float64 tensor for ``NonCartesianSENSE`` /
+    ``engine.build_problem(trajectory=...)``; that it is finite and inside [-N/2, N/2] is checked where the image size is
+    known"""
     import numpy as np
     import torch
     ext = os.path.splitext(str(path))[1].lower()
@@ -272,7 +275,10 @@ def load_trajectory(path):
             k = torch.from_numpy(k)
     else:
         raise ValueError(f"load_trajectory: {path!r}: a .npy or .pt file")
-    if not isinstance(k, torch.Tensor) or k.dim() != 2 or k.shape[1] != 2 or k.shape[0] < 1:
+    if cine:
+        if not isinstance(k, torch.Tensor) or k.dim() != 3 or k.shape[2] != 2 or k.shape[0] < 1 or k.shape[1] < 1:
+            raise ValueError(f"load_trajectory: {path!r} must hold one array of shape (T, M, 2) = (k_y, k_x) per frame and sample")
+    elif not isinstance(k, torch.Tensor) or k.dim() != 2 or k.shape[1] != 2 or k.shape[0] < 1:
         raise ValueError(f"load_trajectory: {path!r} must hold one array of shape (M, 2) = (k_y, k_x) per sample")
     if k.is_complex() or not k.is_floating_point():
         raise TypeError(f"load_trajectory: {path!r} holds {k.dtype}; real floating positions expected")

@@ -410,6 +410,8 @@ class ALD2DTime(ALDOptimizer):
     TV), and the SENSE L2Penalty proximal on every frame.
 
     x_mod_shape: (B, T, C, H, W); measurement: (num_sens, B, T, C, H, W).
+    With a framed ``NonCartesianSENSE`` (T trajectories, radial cine) the measurement is (num_sens, B, T, 1, M), the proximal
+    is ``L2PenaltyCG``, the start is the density-compensated ``zero_filled`` image and A^H W y is formed once per call.
     Extra optional call kwargs: noise_fn(like) (injected noise; default Philox), seed, sample_offset (first global sample
     id of this process' block: sharded runs), verbose, n_levels/start_level.  `if_random_shift` draws ONE host-side
     np.random shift per step for the whole batch (:472): ranks of a sharded run seed numpy identically and stay in step.
@@ -417,7 +419,17 @@ class ALD2DTime(ALDOptimizer):
 
     def __init__(self, proximal: Proximal, scorenet_T, sigmas_T, *args, **kwargs):
         super(ALD2DTime, self).__init__(*args, **kwargs)
-        refuse_noncartesian(self.linear_tfm, "ALD2DTime")
+        refuse_noncartesian(self.linear_tfm, "ALD2DTime", framed_ok=True)
+        self._nc = isinstance(self.linear_tfm, NonCartesianSENSE)
+        if self._nc:
+            # radial cine: one trajectory per frame; the flattened row b * T + t reads frame t = row % T
+            if self.linear_tfm.n_frames != self.x_mod_shape[1]:
+                raise ValueError(f"ALD2DTime: the operator holds {self.linear_tfm.n_frames} frames, x_mod_shape "
+                                 f"{tuple(self.x_mod_shape)} has T = {self.x_mod_shape[1]}")
+            if not isinstance(proximal, L2PenaltyCG):
+                raise NotImplementedError(f"ALD2DTime: no proximal {type(proximal).__name__} for NonCartesianSENSE: the "
+                                          "non-Cartesian operator takes L2PenaltyCG, the exact proximal")
+        self._ahy = None
         if getattr(self.linear_tfm, "n_map_sets", 1) > 1:
             # the batch here is (B, T) flattened: row % S would pick a map set by frame.  Volume cine is not built.
             raise ValueError(f"ALD2DTime: the operator holds {self.linear_tfm.n_map_sets} coil-map sets (one per slice); the "
@@ -460,6 +472,11 @@ class ALD2DTime(ALDOptimizer):
             if_skip_spatial = True
         self.preprocessing_steps(**kwargs)
         x_mod = self.init_x_mod()
+        self._ahy = None
+        if self._nc:                                     # constant over the run: the loop never repeats the direct transform
+            num_sens = self.measurement.shape[0]
+            meas = self.measurement.to(self.device).reshape(num_sens, -1, *self.measurement.shape[3:])
+            self._ahy = self.linear_tfm.adjoint_weighted(meas.contiguous()).contiguous()
         L = self.sigmas.shape[0]
         lv0 = kwargs.get("start_level", 0)
         lv1 = L if kwargs.get("n_levels") is None else min(L, lv0 + kwargs["n_levels"])
@@ -478,6 +495,10 @@ class ALD2DTime(ALDOptimizer):
         return [x_mod.to("cpu")]
 
     def init_x_mod(self):
+        if self._nc:                                     # (num_sens, B, T, 1, M): the zero-filled image, as the 2-D sampler
+            num_sens, B, T = self.measurement.shape[:3]
+            measurement = self.measurement.to(self.device).reshape(num_sens, B * T, *self.measurement.shape[3:])
+            return self.linear_tfm.zero_filled(measurement.contiguous()).reshape(B, T, *self.linear_tfm.in_shape)
         num_sens, B, T, C, H, W = self.measurement.shape
         measurement = self.measurement.to(self.device).reshape(num_sens, -1, C, H, W)
         return self.linear_tfm.conj_op(measurement).reshape(B, T, C, H, W)
@@ -534,7 +555,13 @@ class ALD2DTime(ALDOptimizer):
         B, T, C, H, W = x_mod.shape
         num_sens = self.measurement.shape[0]
         measurement = self.measurement.to(x_mod.device).reshape(num_sens, -1, *self.measurement.shape[3:])
-        x = self.proximal(x_mod.reshape(-1, C, H, W).contiguous(), measurement.contiguous(), alpha * lr_scaled, 1.)
+        if self._nc:
+            if self._ahy is None:                        # proximal_step called on its own
+                self._ahy = self.linear_tfm.adjoint_weighted(measurement.contiguous()).contiguous()
+            x = self.proximal(x_mod.reshape(-1, C, H, W).contiguous(), measurement.contiguous(), alpha * lr_scaled, 1.,
+                              ahy=self._ahy)
+        else:
+            x = self.proximal(x_mod.reshape(-1, C, H, W).contiguous(), measurement.contiguous(), alpha * lr_scaled, 1.)
         return x.reshape(B, T, C, H, W)
 
     def _screenshot(self, x_mod, print_args: dict):

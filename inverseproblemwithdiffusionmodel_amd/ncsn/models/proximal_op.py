@@ -165,7 +165,9 @@ class L2PenaltyCG(Proximal):
     def coef(self, alpha, lamda, z_shape=None):
         return alpha / lamda
 
-    def __call__(self, z, y, alpha, lamda):
+    def __call__(self, z, y, alpha, lamda, ahy=None):
+        """ahy (non-Cartesian operator only): A^H W y = ``lin_tfm.adjoint_weighted(y)``, (B, 1, H, W) complex64, formed once
+        by a caller that applies the proximal in a loop; None: formed here, by the direct transform, in every call"""
         if not z.is_cuda:
             raise RuntimeError("L2PenaltyCG: expected GPU tensors (no CPU fallback in this build)")
         a = self.coef(float(alpha), float(lamda), z.shape)
@@ -177,11 +179,14 @@ class L2PenaltyCG(Proximal):
                 self.lin_tfm.mask_u8(z.device), a, max_iter=self.max_iter, tol=self.tol)
             return torch.complex(o_re, o_im)
         if isinstance(self.lin_tfm, NonCartesianSENSE):
-            # y: the samples (n, B, 1, M); A^H W y by the direct transform, then the Toeplitz CG
+            # y: the samples (n, B, 1, M); A^H W y by the direct transform (unless the caller holds it), then the Toeplitz CG
+            # (a framed operator: row b with the spectrum of frame b % T, 4.4m)
             lin = self.lin_tfm
             zr = torch.view_as_real(z)
+            if ahy is None:
+                ahy = lin.adjoint_weighted(y)
             o_re, o_im, self.last_iters = ops.nc_sense_cgprox(
-                zr[..., 0].contiguous(), zr[..., 1].contiguous(), lin.adjoint_weighted(y).contiguous(),
+                zr[..., 0].contiguous(), zr[..., 1].contiguous(), ahy.to(torch.complex64).contiguous(),
                 lin.sens_dev(z.device), lin.psf_dev(z.device), a, max_iter=self.max_iter, tol=self.tol)
             return torch.complex(o_re, o_im)
         if isinstance(self.lin_tfm, RandomUndersamplingFourier):

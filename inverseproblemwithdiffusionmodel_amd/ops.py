@@ -1188,16 +1188,42 @@ def _nc_operand(t, dtype, name, what):
 
 
 def _nc_traj(traj, weights, what):
-    """-> M of a device trajectory float64 [M, 2] (and weights float32 [M], optional)"""
+    """-> (M, T) of a device trajectory float64 [M, 2] (T None; weights float32 [M], optional) or of one trajectory per
+    frame [T, M, 2] (weights [T, M]): image row b reads frame b % T"""
     _nc_operand(traj, torch.float64, "trajectory", what)
-    if traj.dim() != 2 or traj.shape[1] != 2 or traj.shape[0] < 1:
-        raise ValueError(f"ipdm {what}: trajectory {tuple(traj.shape)} is not (M, 2)")
-    M = traj.shape[0]
+    if traj.dim() == 3 and traj.shape[2] == 2 and traj.shape[0] >= 1 and traj.shape[1] >= 1:
+        T, M = traj.shape[0], traj.shape[1]
+    elif traj.dim() != 2 or traj.shape[1] != 2 or traj.shape[0] < 1:
+        raise ValueError(f"ipdm {what}: trajectory {tuple(traj.shape)} is not (M, 2)" + (" or (T, M, 2)" if traj.dim() > 2 else ""))
+    else:
+        T, M = None, traj.shape[0]
     if weights is not None:
         _nc_operand(weights, torch.float32, "weights", what)
-        if tuple(weights.shape) != (M,):
+        if T is not None and tuple(weights.shape) != (T, M):
+            raise ValueError(f"ipdm {what}: weights {tuple(weights.shape)} do not match the {T} frames of {M} samples")
+        if T is None and tuple(weights.shape) != (M,):
             raise ValueError(f"ipdm {what}: weights {tuple(weights.shape)} do not match the {M} samples")
-    return M
+    return M, T
+
+
+def _nc_frames(B, T, what):
+    """a batch of B rows over T frame sets (row b reads set b % T): refused on the host unless T divides B"""
+    if T is not None and B % T != 0:
+        raise ValueError(f"ipdm {what}: B = {B} image rows are not a multiple of the T = {T} frames (row b reads frame b % T)")
+
+
+def _nc_traj_frames(traj, B, what):
+    """the B % T refusal of a framed trajectory [T, M, 2], from the shapes alone: before any operand is looked at"""
+    if isinstance(traj, torch.Tensor) and traj.dim() == 3 and traj.shape[2] == 2 and traj.shape[0] >= 1:
+        _nc_frames(B, traj.shape[0], what)
+
+
+def _nc_rows(t):
+    """-> (B, H, W) of an image batch [..., H, W] (None where it is no tensor of two or more dimensions)"""
+    if not isinstance(t, torch.Tensor) or t.dim() < 2:
+        return None
+    H, W = t.shape[-2:]
+    return (t.numel() // (H * W) if H * W else 0), H, W
 
 
 def _nc_sens(sens, H, W, what):
@@ -1216,10 +1242,13 @@ def _nc_table_work(nbytes, device):
 
 def ndft_forward(x, traj, sens=None):
     """exact non-uniform DFT of images at the trajectory's samples (ipdm.h, ipdm_ndft_forward_c64).
-    sens [n, H, W]: x [B, H, W] (or [B, 1, H, W]) -> y [n, B, M] = A x;  sens None: x [n, B, H, W] coil images -> [n, B, M]"""
+    sens [n, H, W]: x [B, H, W] (or [B, 1, H, W]) -> y [n, B, M] = A x;  sens None: x [n, B, H, W] coil images -> [n, B, M].
+    traj [M, 2], or [T, M, 2]: row b at the samples of frame b % T (ipdm_ndft_forward_sets_c64)"""
     what = "ndft_forward"
+    if _nc_rows(x) is not None and (sens is not None or x.dim() >= 3):
+        _nc_traj_frames(traj, _nc_rows(x)[0] // (1 if sens is not None else max(x.shape[0], 1)), what)
     _nc_operand(x, torch.complex64, "x", what)
-    M = _nc_traj(traj, None, what)
+    M, T = _nc_traj(traj, None, what)
     H, W = x.shape[-2:]
     n = _nc_sens(sens, H, W, what)
     if sens is None:
@@ -1229,60 +1258,93 @@ def ndft_forward(x, traj, sens=None):
         B = x.numel() // (n * H * W)
     else:
         B = x.numel() // (H * W)
+    _nc_frames(B, T, what)
     _nc_unsupported(H, W, what)
     y = torch.empty((n, B, M), dtype=torch.complex64, device=x.device)
-    work = _nc_table_work(_lib.lib.ipdm_ndft_workspace_bytes(M, H, W), x.device)
-    call("ipdm_ndft_forward_c64", _ptr(x), _ptr(sens), _ptr(traj), _ptr(y), _ptr(work), B, n, M, H, W, _stream())
+    work = _nc_table_work(_lib.lib.ipdm_ndft_workspace_bytes((T or 1) * M, H, W), x.device)
+    if T is None:
+        call("ipdm_ndft_forward_c64", _ptr(x), _ptr(sens), _ptr(traj), _ptr(y), _ptr(work), B, n, M, H, W, _stream())
+    else:
+        call("ipdm_ndft_forward_sets_c64", _ptr(x), _ptr(sens), _ptr(traj), T, _ptr(y), _ptr(work), B, n, M, H, W, _stream())
     return y
 
 
 def ndft_adjoint(y, traj, H, W, sens=None, weights=None):
     """adjoint of ndft_forward, the samples weighted first.  y [n, B, M] -> sens [n, H, W]: A^H W y [B, H, W]; sens None: the
-    coil images [n, B, H, W]"""
+    coil images [n, B, H, W].  traj [T, M, 2] (weights [T, M]): row b from the samples of frame b % T"""
     what = "ndft_adjoint"
+    if isinstance(y, torch.Tensor) and y.dim() == 3:
+        _nc_traj_frames(traj, y.shape[1], what)
     _nc_operand(y, torch.complex64, "y", what)
-    M = _nc_traj(traj, weights, what)
+    M, T = _nc_traj(traj, weights, what)
     if y.dim() != 3 or y.shape[-1] != M:
         raise ValueError(f"ipdm {what}: y {tuple(y.shape)} is not [n_coils, B, {M}]")
     n, B = y.shape[0], y.shape[1]
+    _nc_frames(B, T, what)
     if sens is not None and _nc_sens(sens, H, W, what) != n:
         raise ValueError(f"ipdm {what}: {n} coil signals, {sens.shape[0]} coil maps")
     _nc_unsupported(H, W, what)
     x = torch.empty((B, H, W) if sens is not None else (n, B, H, W), dtype=torch.complex64, device=y.device)
-    work = _nc_table_work(_lib.lib.ipdm_ndft_workspace_bytes(M, H, W), y.device)
-    call("ipdm_ndft_adjoint_c64", _ptr(y), _ptr(sens), _ptr(traj), _ptr(weights), _ptr(x), _ptr(work), B, n, M, H, W, _stream())
+    work = _nc_table_work(_lib.lib.ipdm_ndft_workspace_bytes((T or 1) * M, H, W), y.device)
+    if T is None:
+        call("ipdm_ndft_adjoint_c64", _ptr(y), _ptr(sens), _ptr(traj), _ptr(weights), _ptr(x), _ptr(work), B, n, M, H, W, _stream())
+    else:
+        call("ipdm_ndft_adjoint_sets_c64", _ptr(y), _ptr(sens), _ptr(traj), T, _ptr(weights), _ptr(x), _ptr(work), B, n, M, H, W,
+             _stream())
     return x
 
 
 def toeplitz_psf(traj, H, W, weights=None):
-    """the real spectrum P [2H, 2W] (float32) of the trajectory's Toeplitz kernel: A^H W A = crop F^-1 P F pad"""
+    """the real spectrum P [2H, 2W] (float32) of the trajectory's Toeplitz kernel: A^H W A = crop F^-1 P F pad.
+    traj [T, M, 2] (weights [T, M]) -> [T, 2H, 2W], one spectrum per frame"""
     what = "toeplitz_psf"
-    M = _nc_traj(traj, weights, what)
+    M, T = _nc_traj(traj, weights, what)
     _nc_unsupported(H, W, what)
-    psf = torch.empty((2 * H, 2 * W), dtype=torch.float32, device=traj.device)
+    psf = torch.empty((2 * H, 2 * W) if T is None else (T, 2 * H, 2 * W), dtype=torch.float32, device=traj.device)
     work = _nc_table_work(_lib.lib.ipdm_toeplitz_psf_workspace_bytes(M, H, W), traj.device)
-    call("ipdm_toeplitz_psf_f32", _ptr(traj), _ptr(weights), _ptr(psf), _ptr(work), M, H, W, _stream())
+    if T is None:
+        call("ipdm_toeplitz_psf_f32", _ptr(traj), _ptr(weights), _ptr(psf), _ptr(work), M, H, W, _stream())
+    else:
+        call("ipdm_toeplitz_psf_sets_f32", _ptr(traj), T, _ptr(weights), _ptr(psf), _ptr(work), M, H, W, _stream())
     return psf
 
 
-def _nc_psf(psf, H, W, what):
+def _nc_psf_frames(psf, x, what):
+    """-> T of a psf [T, 2H, 2W] for the image batch x (row b reads set b % T), None of the one-set form [2H, 2W].  Shapes
+    alone: a psf of neither form and B % T != 0 are refused here, before any operand is looked at"""
+    rows = _nc_rows(x)
+    if rows is None or not isinstance(psf, torch.Tensor) or psf.dim() < 3:
+        return None
+    B, H, W = rows
+    if psf.dim() != 3 or tuple(psf.shape[1:]) != (2 * H, 2 * W) or psf.shape[0] < 1:
+        raise ValueError(f"ipdm {what}: psf {tuple(psf.shape)} is neither [{2 * H}, {2 * W}] nor [T, {2 * H}, {2 * W}]")
+    _nc_frames(B, psf.shape[0], what)
+    return psf.shape[0]
+
+
+def _nc_psf(psf, H, W, T, what):
     _nc_operand(psf, torch.float32, "psf", what)
-    if tuple(psf.shape) != (2 * H, 2 * W):
+    if T is None and tuple(psf.shape) != (2 * H, 2 * W):
         raise ValueError(f"ipdm {what}: psf {tuple(psf.shape)} is not [{2 * H}, {2 * W}]")
 
 
 def toeplitz_normal(v, psf, sens=None):
-    """A^H W A v by the Toeplitz chain.  v complex64 [B, H, W] (or [B, 1, H, W]) -> the same shape"""
+    """A^H W A v by the Toeplitz chain.  v complex64 [B, H, W] (or [B, 1, H, W]) -> the same shape.  psf [2H, 2W], or
+    [T, 2H, 2W]: row b with the spectrum of frame b % T"""
     what = "toeplitz_normal"
+    T = _nc_psf_frames(psf, v, what)
     _nc_operand(v, torch.complex64, "v", what)
     H, W = v.shape[-2:]
     B = v.numel() // (H * W) if H * W else 0
     n = _nc_sens(sens, H, W, what)
-    _nc_psf(psf, H, W, what)
+    _nc_psf(psf, H, W, T, what)
     _nc_unsupported(H, W, what)
     out = torch.empty_like(v)
     work = torch.empty(_lib.lib.ipdm_toeplitz_workspace_bytes(B, n, H, W) // 4, dtype=torch.float32, device=v.device)
-    call("ipdm_toeplitz_normal_c64", _ptr(v), _ptr(sens), _ptr(psf), _ptr(out), _ptr(work), B, n, H, W, _stream())
+    if T is None:
+        call("ipdm_toeplitz_normal_c64", _ptr(v), _ptr(sens), _ptr(psf), _ptr(out), _ptr(work), B, n, H, W, _stream())
+    else:
+        call("ipdm_toeplitz_normal_sets_c64", _ptr(v), _ptr(sens), _ptr(psf), T, _ptr(out), _ptr(work), B, n, H, W, _stream())
     return out
 
 
@@ -1316,22 +1378,28 @@ def _nc_cg_args(work, ahy, iters_out, B, n_coils, H, W, device, what):
 
 def nc_sense_cgprox(z_re, z_im, ahy, sens, psf, a, max_iter=10, tol=1e-5, out_re=None, out_im=None, work=None, iters_out=None):
     """exact non-Cartesian SENSE proximal (I + a A^H W A) x = z + a ahy by conjugate gradients (sense_cgprox with the
-    Toeplitz operator; ahy = ndft_adjoint(y, ...), psf = toeplitz_psf(...)) -> (out_re, out_im, iters)"""
+    Toeplitz operator; ahy = ndft_adjoint(y, ...), psf = toeplitz_psf(...)) -> (out_re, out_im, iters).  psf [T, 2H, 2W]: row
+    b solves with the spectrum of frame b % T"""
     what = "nc_sense_cgprox"
     max_iter, tol = _check_cg_scalars(max_iter, tol, what)
+    T = _nc_psf_frames(psf, z_re, what)
     z_re, z_im = _nc_operand(z_re, torch.float32, "z_re", what), _nc_operand(z_im, torch.float32, "z_im", what)
     H, W = z_re.shape[-2:]
     B = z_re.numel() // (H * W) if H * W else 0
     if z_im.shape != z_re.shape:
         raise ValueError(f"{what}: z_re {tuple(z_re.shape)} and z_im {tuple(z_im.shape)} differ")
     n = _nc_sens(sens, H, W, what)
-    _nc_psf(psf, H, W, what)
+    _nc_psf(psf, H, W, T, what)
     _nc_unsupported(H, W, what)
     work, iters_out = _nc_cg_args(work, ahy, iters_out, B, n, H, W, z_re.device, what)
     out_re = torch.empty_like(z_re) if out_re is None else _inplace_operand(out_re, torch.float32, "out_re")
     out_im = torch.empty_like(z_im) if out_im is None else _inplace_operand(out_im, torch.float32, "out_im")
-    call("ipdm_nc_sense_cgprox_f32", _ptr(z_re), _ptr(z_im), _ptr(sens), _ptr(psf), float(a), _ptr(ahy), max_iter, tol,
-         _ptr(out_re), _ptr(out_im), _ptr(work), _ptr(iters_out), B, n, H, W, _stream())
+    if T is None:
+        call("ipdm_nc_sense_cgprox_f32", _ptr(z_re), _ptr(z_im), _ptr(sens), _ptr(psf), float(a), _ptr(ahy), max_iter, tol,
+             _ptr(out_re), _ptr(out_im), _ptr(work), _ptr(iters_out), B, n, H, W, _stream())
+    else:
+        call("ipdm_nc_sense_cgprox_sets_f32", _ptr(z_re), _ptr(z_im), _ptr(sens), _ptr(psf), T, float(a), _ptr(ahy), max_iter,
+             tol, _ptr(out_re), _ptr(out_im), _ptr(work), _ptr(iters_out), B, n, H, W, _stream())
     _written(out_re, out_im, iters_out)
     return out_re, out_im, iters_out
 
@@ -1340,9 +1408,11 @@ def ald_nc_sense_cg_step(x_re, x_im, g_re, g_im, ahy, sens, psf, work, step=0.0,
                          noise_im=None, seed=0, sample_offset=0, step_id=0, dev_sched=None, sample_sched=None, max_iter=10,
                          tol=1e-5, iters_out=None):
     """ald_sense_cg_step for the non-Cartesian operator: Langevin update, then nc_sense_cgprox, in place on x_re / x_im.
-    sample_sched: a schedule record per sample (pc_sense_step).  -> iters (device int32 [B])"""
+    sample_sched: a schedule record per sample (pc_sense_step).  psf [T, 2H, 2W]: row b with the spectrum of frame b % T.
+    -> iters (device int32 [B])"""
     what = "ald_nc_sense_cg_step"
     max_iter, tol = _check_cg_scalars(max_iter, tol, what)
+    T = _nc_psf_frames(psf, x_re, what)
     for t, nm in ((x_re, "x_re"), (x_im, "x_im"), (g_re, "g_re"), (g_im, "g_im")):
         _inplace_operand(t, torch.float32, nm)
     for t, nm in ((noise_re, "noise_re"), (noise_im, "noise_im")):
@@ -1356,14 +1426,18 @@ def ald_nc_sense_cg_step(x_re, x_im, g_re, g_im, ahy, sens, psf, work, step=0.0,
             t is not None and t.numel() != x_re.numel() for t in (noise_re, noise_im)):
         raise ValueError(f"{what}: operand sizes do not match the state")
     n = _nc_sens(sens, H, W, what)
-    _nc_psf(psf, H, W, what)
+    _nc_psf(psf, H, W, T, what)
     _nc_unsupported(H, W, what)
     head = (_ptr(x_re), _ptr(x_im), _ptr(g_re), _ptr(g_im), _ptr(noise_re), _ptr(noise_im), float(step), float(noise_scale),
             int(seed), int(sample_offset), int(step_id), _ptr(dev_sched))
     head = _pc_head(what, head, B, dev_sched, sample_sched)
     work, iters_out = _nc_cg_args(work, ahy, iters_out, B, n, H, W, x_re.device, what)
-    call("ipdm_ald_nc_sense_cg_step_f32", *head, _ptr(sens), _ptr(psf), float(coef), _ptr(work), _ptr(ahy), max_iter, tol,
-         _ptr(iters_out), B, n, H, W, _stream())
+    if T is None:
+        call("ipdm_ald_nc_sense_cg_step_f32", *head, _ptr(sens), _ptr(psf), float(coef), _ptr(work), _ptr(ahy), max_iter, tol,
+             _ptr(iters_out), B, n, H, W, _stream())
+    else:
+        call("ipdm_ald_nc_sense_cg_step_sets_f32", *head, _ptr(sens), _ptr(psf), T, float(coef), _ptr(work), _ptr(ahy), max_iter,
+             tol, _ptr(iters_out), B, n, H, W, _stream())
     _written(x_re, x_im, iters_out)
     return iters_out
 

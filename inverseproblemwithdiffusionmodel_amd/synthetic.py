@@ -139,11 +139,24 @@ def radial_trajectory(n_spokes, n_readout, H, W, golden_angle=True):
     return torch.from_numpy(np.stack([ky.reshape(-1), kx.reshape(-1)], axis=1))
 
 
+def radial_cine_trajectory(n_frames, spokes_per_frame, n_readout, H, W):
+    """float64 (n_frames, spokes_per_frame * n_readout, 2): golden-angle radial cine.  The spoke index runs on across the
+    frames -- frame t holds spokes t * spokes_per_frame ... (t + 1) * spokes_per_frame - 1 of
+    ``radial_trajectory(n_frames * spokes_per_frame, ...)`` --, so every frame has a trajectory of its own."""
+    if isinstance(n_frames, bool) or int(n_frames) != n_frames or n_frames < 1:
+        raise ValueError(f"radial_cine_trajectory: n_frames must be a positive integer, got {n_frames}")
+    k = radial_trajectory(int(n_frames) * spokes_per_frame, n_readout, H, W)
+    return k.reshape(int(n_frames), int(spokes_per_frame) * int(n_readout), 2).contiguous()
+
+
 def radial_density(trajectory, H, W):
     """float64 (M,) ramp density compensation of a radial trajectory: w proportional to the normalised radius
     sqrt((k_y/H)^2 + (k_x/W)^2), the centre samples at half the smallest non-zero radius, normalised to sum w = H W.  For
-    the zero-filled image only; the likelihood's weights stay 1."""
+    the zero-filled image only; the likelihood's weights stay 1.  A framed trajectory (T, M, 2) gives (T, M), every frame
+    normalised on its own."""
     k = torch.as_tensor(trajectory, dtype=torch.float64)
+    if k.dim() == 3 and k.shape[2] == 2 and k.shape[0] >= 1 and k.shape[1] >= 1:
+        return torch.stack([radial_density(k[t], H, W) for t in range(k.shape[0])])
     if k.dim() != 2 or k.shape[1] != 2 or k.shape[0] < 1:
         raise ValueError(f"radial_density: trajectory {tuple(k.shape)} is not (M, 2)")
     r = torch.sqrt((k[:, 0] / H) ** 2 + (k[:, 1] / W) ** 2)
