@@ -562,6 +562,19 @@ int ipdm_ald_nc_sense_cg_step_sets_f32(float* x_re, float* x_im, const float* g_
                                        int psf_sets, float coef, float* work, const float* ahy, int max_iter, float tol,
                                        int32_t* iters_out, int B, int n_coils, int H, int W, void* stream);
 
+/* Non-Cartesian self-calibration (csrc/nc_calib.hip): the weighted Gram matrix of the samples themselves, for coil
+ * compression before calibration images exist.  y [n_coils][B][M] complex64 (the layout of the ndft_* operands), weights
+ * [M] float32 >= 0 (NULL: 1; the calibration window of the trajectory), gram [B][n_coils][n_coils] complex64:
+ *   G_b[i][j] = sum_m w_m y[i][b][m] conj(y[j][b][m])
+ * Double products and sums over chunks of a fixed length, the chunks added in order, one rounding to float32, no atomics:
+ * G is exactly Hermitian with a real diagonal, independent of the batch, and reproducible bit for bit.  y is read only
+ * where w_m > 0, so a NaN at a zero-weight sample does not reach G.  work: ipdm_nc_coil_gram_workspace_bytes (the double
+ * partial sums; 16-byte aligned; 0 for a shape the call refuses).  n_coils 1..64 and B <= 65535, otherwise
+ * IPDM_EUNSUPPORTED; M < 1, n_coils < 1 or NULL tensors: IPDM_EINVAL; B == 0 returns IPDM_OK.  The result feeds
+ * ipdm_coilcomp_matrix_c64 / ipdm_coil_apply_c64 as ipdm_coil_gram_c64's does. */
+size_t ipdm_nc_coil_gram_workspace_bytes(int B, int n_coils, int M);
+int ipdm_nc_coil_gram_c64(const float* y, const float* weights, float* gram, float* work, int B, int n_coils, int M, void* stream);
+
 /* Langevin update alone (ALD_optimizers.py:117): x += step*g + noise_scale*noise ; noise NULL -> Philox. */
 int ipdm_langevin_step_f32(float* x, const float* g, const float* noise, float step, float noise_scale,
                            uint64_t seed, int64_t sample_offset, int64_t step_id, const ipdm_sched_t* dev_sched,

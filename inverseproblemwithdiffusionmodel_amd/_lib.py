@@ -128,6 +128,9 @@ SIGNATURES = {
     "ipdm_nc_sense_cgprox_sets_f32": [P, P, P, P, c_int, c_float, P, c_int, c_float, P, P, P, P, c_int, c_int, c_int, c_int, P],
     "ipdm_ald_nc_sense_cg_step_sets_f32": [P, P, P, P, P, P, c_float, c_float, c_uint64, c_int64, c_int64, P, c_int,
                                            P, P, c_int, c_float, P, P, c_int, c_float, P, c_int, c_int, c_int, c_int, P],
+    # non-Cartesian self-calibration: the weighted Gram matrix of the samples
+    "ipdm_nc_coil_gram_workspace_bytes": [c_int, c_int, c_int],
+    "ipdm_nc_coil_gram_c64": [P, P, P, P, c_int, c_int, c_int, P],
     "ipdm_langevin_step_f32": [P, P, P, c_float, c_float, c_uint64, c_int64, c_int64, P, c_int64, c_int64, P],
     "ipdm_philox_normal_f32": [P, c_uint64, c_int64, c_int64, c_int, c_int64, c_int64, P],
     "ipdm_philox_block_host": [c_uint64, c_int64, c_int64, c_int, ctypes.c_uint32, P],
@@ -236,7 +239,7 @@ _RESTYPES = {"ipdm_build_arch": c_char_p, "ipdm_debug_lds_optin_count": c_int64,
              "ipdm_conv_wino_hx2_weight_bytes": c_int64, "ipdm_conv_wino1d_weight_bytes": c_int64, "ipdm_conv_wino1d_weight_bytes3d": c_int64,
              "ipdm_conv1d_hx2_weight_bytes": c_int64, "ipdm_csm_workspace_bytes": ctypes.c_size_t,
              "ipdm_coilcomp_workspace_bytes": ctypes.c_size_t, "ipdm_gcc_workspace_bytes": ctypes.c_size_t,
-             "ipdm_espirit_workspace_bytes": ctypes.c_size_t}
+             "ipdm_espirit_workspace_bytes": ctypes.c_size_t, "ipdm_nc_coil_gram_workspace_bytes": ctypes.c_size_t}
 
 IPDM_EINVAL = -1
 IPDM_EUNSUPPORTED = -2

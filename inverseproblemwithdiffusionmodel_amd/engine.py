@@ -59,7 +59,8 @@ def build_scorenet(cfg, seed=0):
 def build_problem(device, n_samples, R=40, H=128, W=128, num_sens=4, seed=0, scorenet=None, cfg=None, lr_scaled=1.0,
                   sens_maps=None, proximal="L2Penalty", proximal_kwargs=None, mask=None, estimate_maps=False, measurement=None,
                   calib_max=12, kspace_scale=None, coil_compress=None, noise_cov=None, n_slices=None, maps_method="walsh",
-                  maps_kwargs=None, coil_compress_mode="pca", coil_compress_window=2, trajectory=None, traj_weights=None):
+                  maps_kwargs=None, coil_compress_mode="pca", coil_compress_window=2, trajectory=None, traj_weights=None,
+                  self_calibrate=False, virtual_coils=None):
     """-> Namespace(sampler, scorenet, sigmas, op, image, measurement, call_kwargs); sens_maps: measured coil maps
     (num_sens, H, W), real or complex, instead of the synthetic "exp" maps (RSS-normalised where non-zero); proximal: a
     get_proximal name ("L2PenaltyCG": the exact proximal, proximal_kwargs = dict(max_iter=, tol=)); mask: the sampling mask
@@ -97,14 +98,25 @@ def build_problem(device, n_samples, R=40, H=128, W=128, num_sens=4, seed=0, sco
     kspace_scale -- None: 1 / the peak magnitude of the density-compensated adjoint zero_filled(y).  The proximal is
     L2PenaltyCG (the default name "L2Penalty" is replaced by it; any other is refused); mask, R, estimate_maps,
     coil_compress and n_slices do not go with a trajectory and are refused before anything is allocated.  The Namespace
-    carries zero_filled, the density-compensated adjoint of the (scaled) measurement, (1, 1, H, W) on the device."""
+    carries zero_filled, the density-compensated adjoint of the (scaled) measurement, (1, 1, H, W) on the device.
+    self_calibrate=True (with trajectory=): the coil maps come from the non-Cartesian samples themselves
+    (NonCartesianSENSE.from_measurement: calib_max, maps_method, maps_kwargs as above; virtual_coils=N whitens with noise_cov
+    and compresses up to 64 coils to N first).  Measured: measurement (n_coils, M) and no sens_maps=; the automatic
+    kspace_scale is taken after the calibration.  Simulated: measured through the true synthetic maps, reconstructed with
+    the estimated ones.  sens_maps= with self_calibrate is a ValueError.  The Namespace carries sens_maps (host), coil_matrix
+    ((N, n) on the host, None without compression), calib_region (ah, aw) and calib_kspace ((n', H, W) on the device)."""
     if trajectory is not None:
         return _build_noncartesian(device, n_samples, H, W, num_sens, seed, scorenet, cfg, lr_scaled, sens_maps, proximal,
                                    proximal_kwargs, measurement, kspace_scale, trajectory, traj_weights,
                                    dict(mask=mask is not None, estimate_maps=bool(estimate_maps), coil_compress=coil_compress is not None,
-                                        noise_cov=noise_cov is not None, n_slices=n_slices is not None))
+                                        noise_cov=noise_cov is not None and not self_calibrate, n_slices=n_slices is not None),
+                                   dict(virtual_coils=virtual_coils, noise_cov=noise_cov, calib_max=calib_max, method=maps_method,
+                                        kw=dict(maps_kwargs or {})) if self_calibrate else None, virtual_coils)
     if traj_weights is not None:
         raise ValueError("build_problem: traj_weights= goes with trajectory=")
+    if self_calibrate or virtual_coils is not None:
+        raise ValueError("build_problem: self_calibrate= and virtual_coils= go with trajectory= (Cartesian data: estimate_maps=, "
+                         "coil_compress=)")
     prox_cls = get_proximal(proximal)                        # an unknown name fails here, before any GPU work
     kspace_scale = None if kspace_scale is None else float(kspace_scale)
     region = None
@@ -206,9 +218,10 @@ def build_problem(device, n_samples, R=40, H=128, W=128, num_sens=4, seed=0, sco
 
 
 def _build_noncartesian(device, n_samples, H, W, num_sens, seed, scorenet, cfg, lr_scaled, sens_maps, proximal, proximal_kwargs,
-                        measurement, kspace_scale, trajectory, traj_weights, refused):
-    """build_problem(trajectory=...), its docstring.  Every check runs on the host before the network is built."""
-    from .ncsn.linear_transforms.noncartesian import NonCartesianSENSE
+                        measurement, kspace_scale, trajectory, traj_weights, refused, calib=None, virtual_coils=None):
+    """build_problem(trajectory=...), its docstring.  Every check runs on the host before the network is built.  calib: the
+    self-calibration request (virtual_coils, noise_cov, calib_max, method, kw), None without self_calibrate"""
+    from .ncsn.linear_transforms.noncartesian import NonCartesianSENSE, calibration_window
     from .synthetic import complex_coil_maps
     for name, given in refused.items():
         if given:
@@ -221,24 +234,46 @@ def _build_noncartesian(device, n_samples, H, W, num_sens, seed, scorenet, cfg, 
     if torch.as_tensor(trajectory).dim() > 2:
         raise ValueError(f"build_problem: trajectory {tuple(torch.as_tensor(trajectory).shape)}: a 2-D problem takes (M, 2); one "
                          "trajectory per frame (T, M, 2) is the 2D+time sampler's (ALD2DTime, scripts/cine_SENSE_real_img_2d_time.py)")
+    if calib is None and virtual_coils is not None:
+        raise ValueError("build_problem: virtual_coils= goes with self_calibrate=True")
+    if calib is not None and sens_maps is not None:
+        raise ValueError("build_problem: self_calibrate=True estimates the coil maps; it does not go with sens_maps=")
     if measurement is not None:
-        if sens_maps is None:
-            raise ValueError("build_problem(measurement=..., trajectory=...): pass sens_maps=, the coil maps (they cannot be "
-                             "estimated from non-Cartesian data here)")
+        if sens_maps is None and calib is None:
+            raise ValueError("build_problem(measurement=..., trajectory=...): pass sens_maps=, the coil maps, or "
+                             "self_calibrate=True to estimate them from the samples")
         measurement = torch.as_tensor(measurement)
         M = torch.as_tensor(trajectory).shape[0] if torch.as_tensor(trajectory).dim() == 2 else -1
         if measurement.dim() != 2 or not measurement.is_complex() or measurement.shape[1] != M:
             raise ValueError(f"build_problem: measurement {tuple(measurement.shape)} {measurement.dtype}; complex (n_coils, M = {M}) "
                              "expected with a trajectory")
         num_sens = measurement.shape[0]
-    if sens_maps is None:
+    measured_calib = calib is not None and measurement is not None    # no maps yet: the operator comes from the calibration
+    if sens_maps is None and not measured_calib:
         sens_maps = complex_coil_maps(num_sens, H, W, seed)
-    op = NonCartesianSENSE(trajectory, (1, H, W), sens_maps=sens_maps, weights=traj_weights)     # the remaining host checks
-    if op.num_sens != num_sens:
+    # the remaining host checks (measured self-calibration: trajectory, weights and size alone, on the one-coil operator)
+    op = NonCartesianSENSE(trajectory, (1, H, W), sens_maps=sens_maps, weights=traj_weights)
+    if not measured_calib and op.num_sens != num_sens:
         raise ValueError(f"build_problem: {num_sens} coil signals, {op.num_sens} coil maps")
+    if calib is not None:                                    # the window and the estimator's limits, on the host as well
+        ah, aw, _ = calibration_window(op.trajectory, H, W, calib["calib_max"])
+        NonCartesianSENSE._check_calib(num_sens, calib["virtual_coils"], calib["noise_cov"], H, W, ah, aw, calib["method"],
+                                       dict(calib["kw"]), "build_problem(self_calibrate=True)")
     cfg = acdc_config(device, H) if cfg is None else cfg
     scorenet = build_scorenet(cfg, seed) if scorenet is None else scorenet
     sigmas = get_sigmas(cfg, "recons")
+    cal = None
+    if calib is not None:                                    # simulated with the true maps, reconstructed with the estimated ones
+        img = None if measurement is not None else phantom_image(H, W, seed=seed).to(device)
+        y = measurement.to(torch.complex64).to(device) if measurement is not None else op(img).reshape(num_sens, -1)
+        kw = dict(calib["kw"])
+        kw.pop("return_eig", None)
+        cal = NonCartesianSENSE.from_measurement(y, op.trajectory, (1, H, W), weights=traj_weights, n_virtual=calib["virtual_coils"],
+                                                 noise_cov=calib["noise_cov"], method=calib["method"], calib_max=calib["calib_max"],
+                                                 **kw)
+        op, num_sens = cal.op, cal.op.num_sens
+        measurement = cal.measurement if measurement is not None else None
+        meas1 = cal.measurement.reshape(num_sens, 1, 1, -1).contiguous()
     if measurement is not None:
         img = None
         meas1 = measurement.to(torch.complex64).to(device).reshape(num_sens, 1, 1, -1).contiguous()
@@ -248,7 +283,7 @@ def _build_noncartesian(device, n_samples, H, W, num_sens, seed, scorenet, cfg, 
                 raise ValueError("build_problem: the measurement holds no signal")
             kspace_scale = 1.0 / peak
         meas1 = meas1 * float(kspace_scale)
-    else:
+    elif cal is None:
         img = phantom_image(H, W, seed=seed).to(device)
         meas1 = op(img)
     meas = meas1.repeat(1, n_samples, 1, 1).contiguous()
@@ -257,8 +292,10 @@ def _build_noncartesian(device, n_samples, H, W, num_sens, seed, scorenet, cfg, 
                                         sigmas, params, cfg, meas, op, seg=None, device=device)
     return Namespace(sampler=sampler, scorenet=scorenet, sigmas=sigmas, op=op, image=img, measurement=meas, cfg=cfg, params=params,
                      call_kwargs=dict(label=None, lamda=0.1, save_dir=None, lr_scaled=lr_scaled, seg_mode="full"),
-                     estimated_maps=False, kspace_scale=kspace_scale, coil_matrix=None, n_slices=1, espirit_eigval=None,
-                     zero_filled=op.zero_filled(meas1))
+                     estimated_maps=cal is not None, kspace_scale=kspace_scale,
+                     coil_matrix=None if cal is None else cal.coil_matrix, n_slices=1,
+                     espirit_eigval=None if cal is None else cal.eigval, zero_filled=op.zero_filled(meas1), sens_maps=op.sens_maps,
+                     calib_region=None if cal is None else cal.region, calib_kspace=None if cal is None else cal.calib_kspace)
 
 
 def build_pc_sampler(prob, sde, **kw):

@@ -404,6 +404,52 @@ def driver_maps_method(a, estimate_maps, n_coils, H, W, region):
     return "espirit", dict(ksize=k, sv_thresh=t, crop=c)
 
 
+def add_self_calibrate_args(parser):
+    """the drivers' non-Cartesian self-calibration flags (with --trajectory; --noise_cov, --calib_max and --maps_method are
+    the flags the Cartesian calibration already has)"""
+    parser.add_argument("--self_calibrate", action="store_true",
+                        help="--trajectory: estimate the coil maps from the non-Cartesian samples themselves (the window of "
+                             "samples about the k-space centre); --kspace PATH then needs no --sens_maps")
+    parser.add_argument("--virtual_coils", type=int, default=None, metavar="N",
+                        help="--self_calibrate: whiten (--noise_cov PATH) and compress the samples (up to 64 coils) to N <= 32 "
+                             "virtual coils first; the maps are those of the virtual coils")
+
+
+def driver_self_calibrate(a, trajectory, H, W, num_sens):
+    """host-side check of --self_calibrate and its companions, before a score network is built or a GPU touched; every
+    failure is a ``sys.exit``.  a: the parsed flags (Namespace or dict); trajectory: the checked trajectory, (M, 2) or
+    (T, M, 2), None without --trajectory.  -> None without --self_calibrate, else Namespace(virtual_coils, noise_cov,
+    calib_max, maps_method, maps_kwargs, region)"""
+    import sys
+    from argparse import Namespace
+    from ..ncsn.linear_transforms.noncartesian import NonCartesianSENSE, calibration_window
+    get = a.get if isinstance(a, dict) else lambda k: getattr(a, k)
+    if not get("self_calibrate"):
+        if get("virtual_coils") is not None:
+            sys.exit("--virtual_coils N goes with --self_calibrate")
+        return None
+    if trajectory is None:
+        sys.exit("--self_calibrate goes with --trajectory (Cartesian data: --estimate_maps, --coil_compress)")
+    if get("sens_maps") or get("sens_phase"):
+        sys.exit("--self_calibrate estimates the coil maps; it does not go with --sens_maps / --sens_phase")
+    if get("noise_cov") and get("virtual_coils") is None:
+        sys.exit("--noise_cov PATH goes with --virtual_coils N (whitening is part of the compression)")
+    try:
+        noise_cov = load_noise_cov(get("noise_cov")) if get("noise_cov") else None
+        ah, aw, _ = calibration_window(trajectory, H, W, get("calib_max"))
+    except (ValueError, TypeError) as e:
+        sys.exit(f"--self_calibrate: {e}")
+    n_est = num_sens if get("virtual_coils") is None else get("virtual_coils")
+    maps_method, maps_kwargs = driver_maps_method(a, True, n_est, H, W, (ah, aw))
+    try:
+        _, noise_cov, _ = NonCartesianSENSE._check_calib(num_sens, get("virtual_coils"), noise_cov, H, W, ah, aw, maps_method,
+                                                         dict(maps_kwargs), "--self_calibrate")
+    except (ValueError, TypeError, NotImplementedError) as e:
+        sys.exit(str(e))
+    return Namespace(virtual_coils=get("virtual_coils"), noise_cov=noise_cov, calib_max=get("calib_max"), maps_method=maps_method,
+                     maps_kwargs=maps_kwargs, region=(ah, aw))
+
+
 def add_cine_measurement_args(parser):
     """the cine drivers' measured-data flags, with the meanings scripts/acdc_SENSE_real_img.py gives them"""
     parser.add_argument("--kspace", default=None,

@@ -10,15 +10,20 @@ Radial cine: a trajectory (T, M, 2) holds one trajectory per fr
 every image batch belongs to frame b % T, the rule of the Cartesian coil-map sets, so the (posterior sample, frame) batch
 of ``ALD2DTime``, flattened frame-fastest, is served as it lies in memory.
 
-The reference has no non-Cartesian code.  Out of scope: coil-map estimation or compression from non-Cartesian data, map
-sets, view sharing, frames of unequal length other than by zero weights, gridding approximations, off-resonance,
-trajectories beyond Nyquist.
+Self-calibration: ``calibration_window`` finds the box of grid cells the samples cover about the centre
+and a window on the samples; ``NonCartesianSENSE.estimate_sens_maps`` / ``compress_measurement`` / ``from_measurement``
+take coil maps and a compression matrix from the samples themselves (a regularised per-coil inverse of the windowed
+samples gives Cartesian calibration k-space for the Walsh and ESPIRiT estimators; cine frames are pooled).
+
+The reference has no non-Cartesian code.  Out of scope: map sets and stacks, geometric compression, a second ESPIRiT map
+set, view-shared composites, a noise covariance estimated from a noise scan, frames of unequal length other than by zero
+weights, gridding approximations, off-resonance, trajectories beyond Nyquist.
 """
 import numpy as np
 import torch
 
 from . import LinearTransform
-from .undersampling_fourier import SENSE, _check_gpu
+from .undersampling_fourier import SENSE, _check_gpu, _largest_box
 from ... import ops
 
 
@@ -68,6 +73,53 @@ def check_weights(weights, M, what="NonCartesianSENSE", frames=None):
     if not bool(torch.isfinite(w).all()) or float(w.min()) < 0:
         raise ValueError(f"{what}: weights must be finite and not negative")
     return w.contiguous()
+
+
+def _in_shape_hw(in_shape, what):
+    if len(in_shape) not in (2, 3) or (len(in_shape) == 3 and in_shape[0] != 1):
+        raise ValueError(f"{what}: in_shape {tuple(in_shape)} is not (1, H, W)")
+    return int(in_shape[-2]), int(in_shape[-1])
+
+
+def calibration_window(trajectory, H, W, calib_max=12, taper=2.0):
+    """-> (ah, aw, weights (M,) float64): the calibration box of a non-Cartesian acquisition and the window on its samples
+    (DESIGN.md 4.4n).  Grid cell (p, q) counts as sampled when some sample rounds to it (k_y + H//2, k_x + W//2); that
+    occupancy goes through the largest-box rule of ``calibration_region`` (symmetric about DC, half-widths at most
+    calib_max, the same tie-breaks).  weights: 1 where max(|k_y| - ah, |k_x| - aw) <= 0.5, a raised cosine down to 0 over
+    the next `taper` cycles, 0 beyond.  A framed trajectory (T, M, 2) is pooled over its frames -- the non-Cartesian
+    time average -- and the weights are (T * M,), frame by frame.  ValueError, naming the box found, when ah < 2 or
+    aw < 2.  Host only."""
+    if isinstance(calib_max, bool) or int(calib_max) != calib_max or calib_max < 0:
+        raise ValueError(f"calibration_window: calib_max must be an integer >= 0, got {calib_max}")
+    taper = float(taper)
+    if not (taper >= 0.0 and taper < float("inf")):
+        raise ValueError(f"calibration_window: taper must be finite and not negative, got {taper}")
+    k = check_trajectory(trajectory, H, W, "calibration_window").reshape(-1, 2).numpy()
+    p = np.floor(k[:, 0] + 0.5).astype(np.int64) + H // 2
+    q = np.floor(k[:, 1] + 0.5).astype(np.int64) + W // 2
+    inside = (p >= 0) & (p < H) & (q >= 0) & (q < W)                        # k = +N/2 rounds to the cell past the grid
+    occupied = np.zeros((H, W), dtype=bool)
+    occupied[p[inside], q[inside]] = True
+    best = _largest_box(occupied, H, W, calib_max)
+    if best is None:
+        raise ValueError(f"calibration window: no sample of the trajectory rounds to the k-space centre of the {H}x{W} grid; "
+                         "coil maps cannot be estimated from this acquisition: pass measured maps (sens_maps=)")
+    ah, aw = best
+    if ah < 2 or aw < 2:
+        raise ValueError(f"calibration window: the samples cover every grid cell of a {2 * ah + 1} x {2 * aw + 1} box about the "
+                         f"centre of the {H}x{W} grid and no larger one (half-widths ah = {ah}, aw = {aw}); the coil-map "
+                         "estimator needs at least 5 x 5 (ah >= 2 and aw >= 2): acquire more spokes, or pass measured maps "
+                         "(sens_maps=)")
+    d = np.maximum(np.abs(k[:, 0]) - ah, np.abs(k[:, 1]) - aw) - 0.5
+    w = np.zeros(len(k), dtype=np.float64)
+    w[d <= 0] = 1.0
+    if taper > 0:
+        ramp = (d > 0) & (d < taper)
+        w[ramp] = 0.5 * (1.0 + np.cos(np.pi * d[ramp] / taper))
+    return ah, aw, torch.from_numpy(w)
+
+
+CALIB_DEFAULTS = dict(lam=1e-2, max_iter=40, tol=1e-4)                      # DESIGN.md 4.4n, the lam / iteration table
 
 
 class NonCartesianSENSE(LinearTransform):
@@ -181,6 +233,145 @@ class NonCartesianSENSE(LinearTransform):
 
     def projection(self, X: torch.Tensor, S: torch.Tensor, lamda: float) -> torch.Tensor:
         raise NotImplementedError("NonCartesianSENSE: the k-space projection has no meaning off the grid; use L2PenaltyCG")
+
+    # ---- self-calibration: maps and compression from the samples themselves ----
+    @staticmethod
+    def _calib_operands(y, trajectory, in_shape, what):
+        """host-side normalisation -> (y complex tensor (n, M) or (n, T, M), trajectory float64 (M, 2) or (T, M, 2), H, W):
+        singleton batch / channel dims of a saved (n, 1, 1, M) measurement are dropped.  TypeError / ValueError."""
+        H, W = _in_shape_hw(in_shape, what)
+        k = check_trajectory(trajectory, H, W, what)
+        if not isinstance(y, (torch.Tensor, np.ndarray)):
+            raise TypeError(f"{what}: y must be a torch tensor or numpy array, got {type(y).__name__}")
+        y = torch.as_tensor(y).detach()
+        if not y.is_complex():
+            raise TypeError(f"{what}: y must be complex samples, got {y.dtype}")
+        if y.dim() > k.dim() and all(s == 1 for s in y.shape[1:y.dim() - (k.dim() - 1)]):
+            y = y.reshape((y.shape[0],) + tuple(y.shape[y.dim() - (k.dim() - 1):]))
+        want = tuple(k.shape[:-1])
+        if y.dim() != k.dim() or tuple(y.shape[1:]) != want or y.shape[0] < 1:
+            raise ValueError(f"{what}: y {tuple(y.shape)}; (n_coils,) + {want} expected for a trajectory {tuple(k.shape)}")
+        return y, k, H, W
+
+    @staticmethod
+    def _check_calib(n, n_virtual, noise_cov, H, W, ah, aw, method, kw, what):
+        """every host-side refusal of the calibration chain, before any GPU work -> (n_virtual, noise_cov, return_eig)"""
+        if n_virtual is not None:
+            n_virtual = ops._coilcomp_counts(n, n_virtual, what)
+            if noise_cov is not None:
+                noise_cov = ops.check_noise_cov(noise_cov, n, f"{what}: noise_cov")
+        elif noise_cov is not None:
+            raise ValueError(f"{what}: noise_cov= goes with n_virtual= (whitening is part of the compression)")
+        if ops.kspace_size_class(H, W) == ops.KSPACE_NONE or not ops.nc_supported(H, W):
+            raise ops._lib.IpdmUnsupported(f"{what}: no calibration kernels for {H}x{W}: {ops.KSPACE_SIZE_RULE}, and "
+                                           f"{ops.NC_SIZE_RULE}")
+        n_est = n if n_virtual is None else n_virtual
+        return_eig = SENSE._check_maps_method(method, n_est, H, W, ah, aw, kw, what)
+        if method == "walsh" and not ops.csm_supported(n_est, kw.get("radius", 2), H, W):
+            raise ops._lib.IpdmUnsupported(f"{what}: the map estimator serves 1..32 coils and radius 1..4, got {n_est} coils, "
+                                           f"radius {kw.get('radius', 2)}: compress the measurement first (n_virtual=)")
+        return n_virtual, noise_cov, return_eig
+
+    @staticmethod
+    def _calib_dev(y, k, w):
+        """-> (samples (n, 1, Mt) complex64, pooled trajectory (Mt, 2) float64, window (Mt,) float32) on the GPU"""
+        dev = y.device if y.is_cuda else "cuda"
+        yd = y.to(torch.complex64).to(dev).reshape(y.shape[0], 1, -1).contiguous()
+        return yd, k.reshape(-1, 2).to(dev).contiguous(), w.to(torch.float32).to(dev).contiguous()
+
+    @staticmethod
+    def _maps_dev(yd, kd, wd, H, W, ah, aw, method, kw, solver, what):
+        """calibration k-space and maps of the pooled samples yd (n, 1, Mt) -> (maps (n, H, W) on the GPU, eigval (H, W) or
+        None, rss_max, calibration k-space (n, H, W), CG iterations (n,))"""
+        ks, iters = ops.nc_calib_kspace(yd, kd, H, W, wd, return_iters=True, **solver)
+        if method == "espirit":                                             # rss_max: the peak of the Walsh calibration image
+            _, _, rss_max = ops.estimate_sens_maps(ks, ah, aw, return_rss=True)
+            maps, eigval = SENSE._espirit_maps(ks, ah, aw, what, **kw)
+            eigval = eigval[0]
+        else:
+            maps, _, rss_max = ops.estimate_sens_maps(ks, ah, aw, return_rss=True, **kw)
+            eigval = None
+        return maps[:, 0], eigval, float(rss_max[0]), ks[:, 0], iters[:, 0]
+
+    @staticmethod
+    def _solver_kw(lam, max_iter, tol):
+        d = dict(CALIB_DEFAULTS)
+        d.update({k: v for k, v in (("lam", lam), ("max_iter", max_iter), ("tol", tol)) if v is not None})
+        return d
+
+    @staticmethod
+    def estimate_sens_maps(y, trajectory, in_shape, calib_max=12, method="walsh", lam=None, max_iter=None, tol=None, **kw):
+        """coil maps from non-Cartesian samples themselves: y (n, M) at trajectory (M, 2), or (n, T, M) at (T, M, 2) -- the
+        frames are pooled.  The samples inside ``calibration_window(trajectory, H, W, calib_max)`` are gridded by a
+        regularised per-coil inverse (``ops.nc_calib_kspace``: lam, max_iter, tol; defaults CALIB_DEFAULTS) and the
+        Cartesian estimators run on that k-space with the window's box: ``ops.estimate_sens_maps`` (method="walsh"; kw:
+        radius, power_iters, thresh) or ``ops.espirit_maps`` (method="espirit"; kw: ksize, sv_thresh, crop, power_iters;
+        return_eig=True: -> (maps, eigval (H, W) float32 on the host)).  -> host complex128 (n, H, W), unit RSS inside
+        the support and zero outside: ready for ``sens_maps=``.  Every argument is checked on the host first."""
+        what = "NonCartesianSENSE.estimate_sens_maps"
+        y, k, H, W = NonCartesianSENSE._calib_operands(y, trajectory, in_shape, what)
+        ah, aw, w = calibration_window(k, H, W, calib_max)
+        _, _, return_eig = NonCartesianSENSE._check_calib(y.shape[0], None, None, H, W, ah, aw, method, kw, what)
+        yd, kd, wd = NonCartesianSENSE._calib_dev(y, k, w)
+        maps, eigval, _, _, _ = NonCartesianSENSE._maps_dev(yd, kd, wd, H, W, ah, aw, method, kw,
+                                                            NonCartesianSENSE._solver_kw(lam, max_iter, tol), what)
+        maps = maps.cpu().to(torch.complex128)
+        return (maps, eigval.cpu()) if return_eig else maps
+
+    @staticmethod
+    def compress_measurement(y, trajectory, in_shape, n_virtual, noise_cov=None, calib_max=12):
+        """whitening and coil compression of non-Cartesian samples: y (n, M) or (n, T, M) as for estimate_sens_maps (up to 64
+        coils) to n_virtual 1..min(n, 32) virtual coils.  The Gram matrix is ``ops.nc_coil_gram`` of the pooled samples
+        under the calibration window's weights, the matrix ``ops.coilcomp_matrix`` (noise_cov: the (n, n) coil noise
+        covariance, optional), applied to the samples of every frame by ``ops.coil_apply``.  -> (y' of y's shape with
+        n_virtual coils, complex64 on the GPU; A (n_virtual, n) complex64 on the host)."""
+        what = "NonCartesianSENSE.compress_measurement"
+        y, k, H, W = NonCartesianSENSE._calib_operands(y, trajectory, in_shape, what)
+        n_virtual = ops._coilcomp_counts(y.shape[0], n_virtual, what)
+        if noise_cov is not None:
+            noise_cov = ops.check_noise_cov(noise_cov, y.shape[0], f"{what}: noise_cov")
+        _, _, w = calibration_window(k, H, W, calib_max)
+        yd, _, wd = NonCartesianSENSE._calib_dev(y, k, w)
+        out, A = NonCartesianSENSE._compress_dev(yd, wd, n_virtual, noise_cov, what)
+        return out.reshape((n_virtual,) + tuple(y.shape[1:])), A.cpu()
+
+    @staticmethod
+    def _compress_dev(yd, wd, n_virtual, noise_cov, what):
+        A, _, status = ops.coilcomp_matrix(ops.nc_coil_gram(yd, wd), n_virtual, noise_cov, return_eig=True)
+        if int(status[0]) != 0:
+            raise RuntimeError(f"{what}: the noise covariance has a non-positive Cholesky pivot in fp32")
+        return ops.coil_apply(yd, A[0].contiguous()), A[0]
+
+    @classmethod
+    def from_measurement(cls, y, trajectory, in_shape, weights=None, n_virtual=None, noise_cov=None, method="walsh",
+                         calib_max=12, lam=None, max_iter=None, tol=None, **kw):
+        """the operator of a non-Cartesian acquisition, calibrated from its own samples: y (n, M) at trajectory (M, 2), or cine
+        data (n, T, M) at (T, M, 2) -- the operator is then framed and the maps come from the pool of the frames.  With
+        n_virtual the samples are whitened (noise_cov) and compressed first (compress_measurement; up to 64 physical
+        coils) and the maps are those of the virtual coils; weights: the likelihood's, handed to the operator.  method, kw,
+        lam, max_iter, tol: estimate_sens_maps'.  -> Namespace(op, measurement (n', M) / (n', T, M) complex64 on the GPU,
+        sens_maps (n', H, W) complex128 on the host, coil_matrix (n', n) complex64 on the host or None, region (ah, aw),
+        rss_max (the peak of the calibration image), calib_kspace (n', H, W) complex64 on the GPU, cg_iters (n',) int32 on
+        the host, eigval (the ESPIRiT eigenvalue map on the host, None for Walsh)).  Every argument is checked on the host
+        before any GPU work."""
+        from argparse import Namespace
+        what = "NonCartesianSENSE.from_measurement"
+        y, k, H, W = cls._calib_operands(y, trajectory, in_shape, what)
+        if weights is not None:
+            check_weights(weights, k.shape[-2], what, frames=k.shape[0] if k.dim() == 3 else None)
+        ah, aw, w = calibration_window(k, H, W, calib_max)
+        n_virtual, noise_cov, _ = cls._check_calib(y.shape[0], n_virtual, noise_cov, H, W, ah, aw, method, kw, what)
+        yd, kd, wd = cls._calib_dev(y, k, w)
+        A = None
+        if n_virtual is not None:
+            yd, A = cls._compress_dev(yd, wd, n_virtual, noise_cov, what)
+        maps, eigval, rss_max, ks, iters = cls._maps_dev(yd, kd, wd, H, W, ah, aw, method, kw,
+                                                         cls._solver_kw(lam, max_iter, tol), what)
+        maps = maps.cpu().to(torch.complex128)
+        op = cls(k, (1, H, W), sens_maps=maps, weights=weights, normalize=False)
+        return Namespace(op=op, measurement=yd.reshape((yd.shape[0],) + tuple(y.shape[1:])), sens_maps=op.sens_maps,
+                         coil_matrix=None if A is None else A.cpu(), region=(ah, aw), rss_max=rss_max, calib_kspace=ks,
+                         cg_iters=iters.cpu(), eigval=None if eigval is None else eigval.cpu())
 
 
 def refuse_noncartesian(lin_tfm, who, framed_ok=False):

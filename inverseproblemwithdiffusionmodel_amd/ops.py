@@ -1442,6 +1442,102 @@ def ald_nc_sense_cg_step(x_re, x_im, g_re, g_im, ahy, sens, psf, work, step=0.0,
     return iters_out
 
 
+# ---- non-Cartesian self-calibration (csrc/nc_calib.hip) ----------------------------------------------------
+NC_GRAM_CHUNK = 1024                             # samples per partial sum of nc_coil_gram (csrc/nc_calib.hip, NCG_CHUNK)
+
+
+def nc_coil_gram_workspace(B, n_coils, M, device):
+    """scratch tensor of nc_coil_gram (the double partial sums per chunk of NC_GRAM_CHUNK samples); None for a shape without
+    a kernel"""
+    nbytes = _lib.lib.ipdm_nc_coil_gram_workspace_bytes(int(B), int(n_coils), int(M))
+    return torch.empty(nbytes // 8, dtype=torch.float64, device=device) if nbytes else None
+
+
+def _nc_samples(y, what):
+    """-> (n, B, M) of non-Cartesian samples y [n, B, M] complex64"""
+    _nc_operand(y, torch.complex64, "y", what)
+    if y.dim() != 3 or min(y.shape[0], y.shape[2]) < 1:
+        raise ValueError(f"ipdm {what}: y {tuple(y.shape)} is not [n_coils, B, M]")
+    return tuple(y.shape)
+
+
+def _nc_window(weights, M, what):
+    if weights is not None:
+        _nc_operand(weights, torch.float32, "weights", what)
+        if tuple(weights.shape) != (M,):
+            raise ValueError(f"ipdm {what}: weights {tuple(weights.shape)} do not match the {M} samples")
+
+
+def nc_coil_gram(y, weights=None, *, out=None, work=None):
+    """weighted Gram matrices of non-Cartesian samples y [n, B, M] complex64 (1..64 coils): G_b[i][j] = sum_m w_m y_i conj(y_j)
+    with weights [M] float32 >= 0 (None: 1; ``calibration_window``'s) -> (B, n, n) complex64, exactly Hermitian; y is read
+    only where w_m > 0 (ipdm.h, ipdm_nc_coil_gram_c64).  The result goes to ``coilcomp_matrix`` as ``coil_gram``'s does."""
+    what = "nc_coil_gram"
+    n, B, M = _nc_samples(y, what)
+    _nc_window(weights, M, what)
+    if n > 64:
+        raise _lib.IpdmUnsupported(f"ipdm {what}: {n} coils; the kernel serves 1..64")
+    if out is None:
+        out = torch.empty((B, n, n), dtype=torch.complex64, device=y.device)
+    else:
+        _inplace_operand(out, torch.complex64, "out")
+        if tuple(out.shape) != (B, n, n):
+            raise ValueError(f"ipdm {what}: out {tuple(out.shape)}, expected {(B, n, n)}")
+    need = _lib.lib.ipdm_nc_coil_gram_workspace_bytes(B, n, M)
+    if work is None:
+        work = nc_coil_gram_workspace(B, n, M, y.device)
+    elif (not isinstance(work, torch.Tensor) or not work.is_cuda or work.dtype != torch.float64 or not work.is_contiguous()
+            or work.numel() * 8 < need):
+        raise ValueError(f"ipdm {what}: `work` must be a contiguous float64 GPU tensor of >= {need} bytes "
+                         f"(ops.nc_coil_gram_workspace({B}, {n}, {M}, device))")
+    call("ipdm_nc_coil_gram_c64", _ptr(y), _ptr(weights), _ptr(out), _ptr(work), B, n, M, _stream())
+    _written(out)
+    return out
+
+
+def nc_calib_images(y, traj, H, W, weights, lam=1e-2, max_iter=40, tol=1e-4, return_iters=False):
+    """low-resolution calibration images of non-Cartesian samples: y [n, B, M] complex64 at traj [M, 2] float64, weights [M]
+    float32 the calibration window (``calibration_window``) -> x [n, B, H, W] complex64, per coil the regularised inverse
+        (A^H W A + lam t0 I) x_c = A^H W y_c,   t0 = sum(w) / (H W)
+    of the windowed samples: no density compensation, any trajectory the operator accepts.  One ``toeplitz_psf``, one
+    ``ndft_adjoint`` and one ``nc_sense_cgprox`` call with the n B coil images as batch rows, one unit map, z = 0 and
+    a = 1 / (lam t0).  tol = 0 runs max_iter iterations.  return_iters: -> (x, iters int32 [n, B]).  sum(w) is read back
+    once (the solver's `a` is a host scalar)."""
+    what = "nc_calib_images"
+    n, B, M = _nc_samples(y, what)
+    _nc_operand(traj, torch.float64, "trajectory", what)
+    if tuple(traj.shape) != (M, 2):
+        raise ValueError(f"ipdm {what}: trajectory {tuple(traj.shape)} is not ({M}, 2), one position per sample")
+    if weights is None:
+        raise ValueError(f"ipdm {what}: weights, the calibration window of the trajectory, are required")
+    _nc_window(weights, M, what)
+    lam = float(lam)
+    if not (lam > 0.0 and lam < float("inf")):
+        raise ValueError(f"ipdm {what}: lam must be positive and finite, got {lam}")
+    max_iter, tol = _check_cg_scalars(max_iter, tol, what)
+    H, W = int(H), int(W)
+    _nc_unsupported(H, W, what)
+    t0 = float(weights.sum(dtype=torch.float64)) / (H * W)
+    if not t0 > 0.0:
+        raise ValueError(f"ipdm {what}: the weights are all zero")
+    psf = toeplitz_psf(traj, H, W, weights)
+    ahy = ndft_adjoint(y, traj, H, W, None, weights).reshape(n * B, H, W)
+    z = torch.zeros((n * B, H, W), dtype=torch.float32, device=y.device)
+    x_re, x_im, iters = nc_sense_cgprox(z, z, ahy, None, psf, 1.0 / (lam * t0), max_iter=max_iter, tol=tol)
+    x = torch.complex(x_re, x_im).reshape(n, B, H, W)
+    return (x, iters.reshape(n, B)) if return_iters else x
+
+
+def nc_calib_kspace(y, traj, H, W, weights, lam=1e-2, max_iter=40, tol=1e-4, return_iters=False):
+    """Cartesian calibration k-space of non-Cartesian samples: ``fft2c`` of ``nc_calib_images`` -> [n, B, H, W] complex64, which
+    ``estimate_sens_maps`` and ``espirit_maps`` take as it is, with the box of ``calibration_window``"""
+    if kspace_size_class(H, W) == KSPACE_NONE:
+        raise _lib.IpdmUnsupported(f"ipdm nc_calib_kspace: no k-space kernel for {H}x{W}; {KSPACE_SIZE_RULE}")
+    x, iters = nc_calib_images(y, traj, H, W, weights, lam, max_iter, tol, return_iters=True)
+    k = fft2c(x)
+    return (k, iters) if return_iters else k
+
+
 # ---- segmentation-likelihood guidance glue ----------------------------------------------------------
 def zero_insert2(x):
     """(..., H, W) -> (..., 2H, 2W): x at the even positions, zeros elsewhere"""

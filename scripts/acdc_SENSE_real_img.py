@@ -14,7 +14,10 @@ posterior_slices.pt holds the per-slice mean / std over the rows b % S == s.  On
 Non-Cartesian sampling: --trajectory radial --spokes N [--readout M] simulates a golden-angle radial acquisition of the
 phantom, --trajectory PATH one on the (M, 2) positions of a file, --kspace PATH --trajectory PATH --sens_maps PATH
 reconstructs measured samples (n_coils, M).  The proximal is then L2PenaltyCG; trajectory.pt is written instead of
-mask.pt and ZF.pt is the density-compensated adjoint."""
+mask.pt and ZF.pt is the density-compensated adjoint.  --self_calibrate takes the coil maps from the non-Cartesian samples
+themselves ([--virtual_coils N] [--noise_cov PATH] [--calib_max N] [--maps_method walsh|espirit]), so that
+--kspace PATH --trajectory PATH --self_calibrate needs no --sens_maps; sens_maps.pt, calib_kspace.pt and (with
+--virtual_coils) coil_matrix.pt are written."""
 import argparse
 import os
 import pickle
@@ -90,8 +93,10 @@ if __name__ == '__main__':
                         help="--coil_compress: .npy / .pt file with the (n_coils, n_coils) coil noise covariance of the prescan")
     parser.add_argument("--kspace_scale", default="auto",
                         help="--kspace: factor on the measurement; auto: 1 / the peak of its calibration image")
-    from inverseproblemwithdiffusionmodel_amd.helpers.load_data import add_maps_method_args, driver_maps_method
+    from inverseproblemwithdiffusionmodel_amd.helpers.load_data import (add_maps_method_args, add_self_calibrate_args,
+                                                                         driver_maps_method, driver_self_calibrate)
     add_maps_method_args(parser)
+    add_self_calibrate_args(parser)
     parser.add_argument("--trajectory", default=None, metavar="radial|PATH",
                         help="non-Cartesian sampling: 'radial' (golden-angle spokes, --spokes / --readout) or a .npy / .pt file "
                              "with (M, 2) positions (k_y, k_x) in cycles per field of view; implies --proximal_type L2PenaltyCG")
@@ -121,12 +126,15 @@ if __name__ == '__main__':
     W = args_dict["image_width"] if args_dict["image_width"] is not None else H
     kspace = None
     trajectory = None
+    self_cal = None
+    if not args_dict["trajectory"]:
+        driver_self_calibrate(args_dict, None, H, W, args_dict["num_sens"])       # the flags alone: they go with --trajectory
     if args_dict["trajectory"]:                                           # every refusal before the network is built
         if args_dict["proximal_type"] not in (None, "L2PenaltyCG"):
             sys.exit(f"--trajectory: non-Cartesian SENSE takes --proximal_type L2PenaltyCG, not {args_dict['proximal_type']}")
         args_dict["proximal_type"] = "L2PenaltyCG"
         for flag in ("mask", "mask_2d", "estimate_maps", "coil_compress", "noise_cov", "slices", "n_slices"):
-            if args_dict[flag] not in (None, False):
+            if args_dict[flag] not in (None, False) and not (flag == "noise_cov" and args_dict["self_calibrate"]):
                 sys.exit(f"--trajectory does not go with --{flag}: non-Cartesian SENSE takes given coil maps, one slice and no "
                          "sampling mask")
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -151,14 +159,16 @@ if __name__ == '__main__':
                 trajectory = load_trajectory(args_dict["trajectory"])
             trajectory = check_trajectory(trajectory, H, W, "--trajectory")
             if args_dict["kspace"]:
-                if not args_dict["sens_maps"] or args_dict["sens_phase"]:
-                    sys.exit("--kspace PATH --trajectory PATH needs --sens_maps PATH (maps are not estimated from non-Cartesian data)")
+                if not args_dict["self_calibrate"] and (not args_dict["sens_maps"] or args_dict["sens_phase"]):
+                    sys.exit("--kspace PATH --trajectory PATH needs --sens_maps PATH, or --self_calibrate to estimate the maps "
+                             "from the samples")
                 kspace = load_kspace(args_dict["kspace"], noncartesian=True)
                 if kspace.shape[1] != trajectory.shape[0]:
                     sys.exit(f"--kspace holds {tuple(kspace.shape)}; (n_coils, {trajectory.shape[0]}) expected for this trajectory")
                 args_dict["num_sens"] = int(kspace.shape[0])
         except (ValueError, TypeError) as e:
             sys.exit(str(e))
+        self_cal = driver_self_calibrate(args_dict, trajectory, H, W, args_dict["num_sens"])     # the window, before the network
     elif args_dict["spokes"] is not None or args_dict["readout"] is not None:
         sys.exit("--spokes / --readout go with --trajectory radial")
     if args_dict["proximal_type"] is None:
@@ -194,7 +204,7 @@ if __name__ == '__main__':
     mask = None if trajectory is not None else driver_mask(args_dict["mask"], args_dict["mask_2d"], H, W, args_dict["R"],
                                                            args_dict["seed"])
     noise_cov = region = None
-    if args_dict["noise_cov"] and args_dict["coil_compress"] is None:
+    if args_dict["noise_cov"] and args_dict["coil_compress"] is None and self_cal is None:
         sys.exit("--noise_cov PATH goes with --coil_compress N (whitening is part of the compression)")
     if args_dict["coil_compress"] is not None:                            # a bad N or a bad covariance fails here
         from inverseproblemwithdiffusionmodel_amd.helpers.load_data import load_noise_cov
@@ -224,9 +234,12 @@ if __name__ == '__main__':
                                            args_dict["coil_compress_window"], "--coil_compress_mode geometric")
         except (ValueError, NotImplementedError) as e:
             sys.exit(str(e))
-    maps_method, maps_kwargs = driver_maps_method(
-        args_dict, args_dict["estimate_maps"],
-        args_dict["num_sens"] if args_dict["coil_compress"] is None else args_dict["coil_compress"], H, W, region)
+    if self_cal is not None:
+        maps_method, maps_kwargs, noise_cov = self_cal.maps_method, self_cal.maps_kwargs, self_cal.noise_cov
+    else:
+        maps_method, maps_kwargs = driver_maps_method(
+            args_dict, args_dict["estimate_maps"],
+            args_dict["num_sens"] if args_dict["coil_compress"] is None else args_dict["coil_compress"], H, W, region)
     from inverseproblemwithdiffusionmodel_amd import engine, sharding
     world, rank, device = sharding.init_distributed()
     from inverseproblemwithdiffusionmodel_amd.helpers.load_model import load_scorenet_weights
@@ -259,7 +272,8 @@ if __name__ == '__main__':
                                 proximal=args_dict["proximal_type"],
                                 proximal_kwargs=(dict(max_iter=args_dict["cg_iters"], tol=args_dict["cg_tol"])
                                                  if args_dict["proximal_type"] == "L2PenaltyCG" else None),
-                                trajectory=trajectory)
+                                trajectory=trajectory, self_calibrate=self_cal is not None,
+                                virtual_coils=args_dict["virtual_coils"])
     label = None
     if args_dict["seg_start_time"] < 1.:
         from inverseproblemwithdiffusionmodel_amd.helpers.load_model import reload_model
@@ -320,6 +334,8 @@ if __name__ == '__main__':
             torch.save(prob.op.sens_maps, os.path.join(save_dir, "sens_maps.pt"))
         if prob.coil_matrix is not None:
             torch.save(prob.coil_matrix, os.path.join(save_dir, "coil_matrix.pt"))
+        if self_cal is not None:
+            torch.save(prob.calib_kspace.cpu(), os.path.join(save_dir, "calib_kspace.pt"))
         if prob.espirit_eigval is not None:
             torch.save(prob.espirit_eigval, os.path.join(save_dir, "espirit_eigval.pt"))
         if post is not None:

@@ -9,7 +9,10 @@ T), against the one-set tail on the same operands: each arm captured as a hipGra
 --rounds rounds, median and range per arm.  --frames 1 is the one-set spectrum in the sets form, [1, 2H, 2W].
 
     python scripts/bench_nc_sense.py [--size 128] [--batch 14] [--spokes 32] [--readout 256] [--cg_iters 10] [--tiny]
-    python scripts/bench_nc_sense.py --frames 24 --batch 24"""
+    python scripts/bench_nc_sense.py --frames 24 --batch 24
+--calibrate: the stages of the self-calibration, each timed once -- a report, not a gate.
+
+    python scripts/bench_nc_sense.py --calibrate [--coils 8]"""
 import argparse
 import json
 import os
@@ -150,8 +153,47 @@ def bench_frames(size, B, coils, spokes, readout, cg_iters, T, rounds):
     return out
 
 
+def bench_calibrate(size, coils, spokes, readout):
+    """self-calibration, each stage timed once after one untimed warm-up pass (wall clock around a device
+    synchronisation): the window on the host, the sample Gram matrix, the Toeplitz spectrum, the adjoint, the conjugate
+    gradients of the calibration images (the default lam, cap and tolerance), the FFT and the Walsh estimator.  A report."""
+    from inverseproblemwithdiffusionmodel_amd import ops
+    from inverseproblemwithdiffusionmodel_amd.ncsn.linear_transforms.noncartesian import (CALIB_DEFAULTS, NonCartesianSENSE,
+                                                                                          calibration_window)
+    from inverseproblemwithdiffusionmodel_amd.synthetic import complex_coil_maps, phantom_image, radial_trajectory
+    dev = torch.device("cuda")
+    k = radial_trajectory(spokes, readout, size, size)
+    t0 = time.perf_counter()
+    ah, aw, w = calibration_window(k, size, size)
+    ms_window = (time.perf_counter() - t0) * 1e3
+    with torch.no_grad():
+        op = NonCartesianSENSE(k, (1, size, size), sens_maps=complex_coil_maps(coils, size, size, 0))
+        y = op(phantom_image(size, size, seed=0).to(dev)).reshape(coils, 1, -1).contiguous()
+        kd, wd = k.to(dev).contiguous(), w.to(torch.float32).to(dev).contiguous()
+        t0v = float(wd.sum(dtype=torch.float64)) / (size * size)
+        z = torch.zeros(coils, size, size, device=dev)
+        t, iters = {}, None
+        for _ in range(2):                                           # the first pass warms up; the second one's times are kept
+            t["ms_gram"] = wall_ms(lambda: ops.nc_coil_gram(y, wd))
+            psf, ahy = [None], [None]
+            t["ms_psf"] = wall_ms(lambda: psf.__setitem__(0, ops.toeplitz_psf(kd, size, size, wd)))
+            t["ms_adjoint"] = wall_ms(lambda: ahy.__setitem__(0, ops.ndft_adjoint(y, kd, size, size, None, wd).reshape(coils, size, size)))
+            x = [None]
+            t["ms_cg"] = wall_ms(lambda: x.__setitem__(0, ops.nc_sense_cgprox(
+                z, z, ahy[0], None, psf[0], 1.0 / (CALIB_DEFAULTS["lam"] * t0v), max_iter=CALIB_DEFAULTS["max_iter"],
+                tol=CALIB_DEFAULTS["tol"])))
+            ks = ops.fft2c(torch.complex(x[0][0], x[0][1]).reshape(coils, 1, size, size))
+            t["ms_estimator_walsh"] = wall_ms(lambda: ops.estimate_sens_maps(ks, ah, aw))
+            iters = x[0][2].cpu().tolist()
+    return dict(bench="nc_sense_calibrate", size=size, coils=coils, spokes=spokes, readout=readout, box=[ah, aw],
+                window_samples=int((w > 0).sum()), cg_iters=iters, ms_window_host=round(ms_window, 2),
+                **{k_: round(v, 3) for k_, v in t.items()})
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
+    ap.add_argument("--calibrate", action="store_true",
+                    help="time the self-calibration stages once (window, Gram, psf, adjoint, CG, estimator): a report")
     ap.add_argument("--size", type=int, default=128)
     ap.add_argument("--batch", type=int, default=14)
     ap.add_argument("--coils", type=int, default=4)
@@ -164,6 +206,9 @@ if __name__ == "__main__":
                     help="time the tail with T psf sets (radial cine) against the one-set tail; --batch a multiple of T")
     ap.add_argument("--rounds", type=int, default=7, help="--frames: alternating rounds of 20 replays per arm")
     a = ap.parse_args()
+    if a.calibrate:
+        print(json.dumps(bench_calibrate(a.size, a.coils, a.spokes, a.readout)), flush=True)
+        sys.exit(0)
     if a.frames is not None:
         if a.frames < 1:
             sys.exit("--frames T: T >= 1")

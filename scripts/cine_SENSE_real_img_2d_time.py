@@ -9,7 +9,9 @@ measurement.  Radial cine: --trajectory radial --spokes N [--readout M] simulate
 phantom with N spokes per frame (the spoke index runs on across the --T frames, so every frame has its own trajectory),
 --trajectory PATH one on the (T, M, 2) positions of a file, --kspace PATH --trajectory PATH --sens_maps PATH reconstructs
 measured samples (n_coils, T, M).  The proximal is then L2PenaltyCG (--proximal_type L2PenaltyCG); trajectory.pt, ZF.pt and
-measurement.pt are written and no mask.pt.  Under torchrun the `--num_samples` posterior samples are block-partitioned over the ranks (Philox noise
+measurement.pt are written and no mask.pt.  --self_calibrate ([--virtual_coils N] [--noise_cov PATH] [--calib_max N]
+[--maps_method walsh|espirit]) takes the coil maps from the samples themselves, pooled over the frames, so that --kspace PATH
+--trajectory PATH --self_calibrate needs no --sens_maps (sens_maps.pt, calib_kspace.pt, coil_matrix.pt).  Under torchrun the `--num_samples` posterior samples are block-partitioned over the ranks (Philox noise
 keyed by the global sample id, the per-step random shift drawn from identically seeded host generators), rank 0 writes the
 artefacts and the posterior mean / std: the result does not depend on the number of ranks."""
 import argparse
@@ -71,16 +73,19 @@ if __name__ == '__main__':
                         help="--trajectory radial: samples per spoke (default: 2 x the larger image side)")
     from inverseproblemwithdiffusionmodel_amd.helpers import load_data
     load_data.add_cine_measurement_args(parser)
+    load_data.add_self_calibrate_args(parser)
     a = parser.parse_args()
     H, W = a.image_size, a.image_size if a.image_width is None else a.image_width
     from inverseproblemwithdiffusionmodel_amd import ops
-    trajectory, nc_kspace = None, None
+    trajectory, nc_kspace, self_cal = None, None, None
+    if not a.trajectory:
+        load_data.driver_self_calibrate(a, None, H, W, a.num_sens)          # the flags alone: they go with --trajectory
     if a.trajectory:                                  # every refusal before a network is built
         if a.proximal_type != "L2PenaltyCG":
             sys.exit(f"--trajectory: non-Cartesian SENSE takes --proximal_type L2PenaltyCG, not {a.proximal_type}")
         for flag, given in (("mask", a.mask), ("mask_2d", a.mask_2d), ("estimate_maps", a.estimate_maps),
-                            ("coil_compress", a.coil_compress is not None), ("noise_cov", a.noise_cov),
-                            ("maps_method", a.maps_method != "walsh")):
+                            ("coil_compress", a.coil_compress is not None), ("noise_cov", a.noise_cov and not a.self_calibrate),
+                            ("maps_method", a.maps_method != "walsh" and not a.self_calibrate)):
             if given:
                 sys.exit(f"--trajectory does not go with --{flag}: non-Cartesian SENSE takes given coil maps and no sampling mask")
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -103,18 +108,20 @@ if __name__ == '__main__':
             trajectory = check_trajectory(trajectory, H, W, "--trajectory")
             a.T = int(trajectory.shape[0])
             if a.kspace:
-                if not a.sens_maps or a.sens_phase:
-                    sys.exit("--kspace PATH --trajectory PATH needs --sens_maps PATH (maps are not estimated from non-Cartesian data)")
+                if not a.self_calibrate and (not a.sens_maps or a.sens_phase):
+                    sys.exit("--kspace PATH --trajectory PATH needs --sens_maps PATH, or --self_calibrate to estimate the maps "
+                             "from the samples")
                 nc_kspace = load_data.load_kspace(a.kspace, noncartesian=True, cine=True)
                 if tuple(nc_kspace.shape[1:]) != tuple(trajectory.shape[:2]):
                     sys.exit(f"--kspace holds {tuple(nc_kspace.shape)}; (n_coils, {trajectory.shape[0]}, {trajectory.shape[1]}) "
                              "expected for this trajectory")
                 a.num_sens = int(nc_kspace.shape[0])
-                maps_shape = tuple(load_data.load_sens_maps(a.sens_maps).shape)
-                if maps_shape != (a.num_sens, H, W):
+                maps_shape = tuple(load_data.load_sens_maps(a.sens_maps).shape) if a.sens_maps else None
+                if a.sens_maps and maps_shape != (a.num_sens, H, W):
                     sys.exit(f"--sens_maps holds {maps_shape}; ({a.num_sens}, {H}, {W}) expected for this measurement")
         except (ValueError, TypeError) as e:
             sys.exit(str(e))
+        self_cal = load_data.driver_self_calibrate(a, trajectory, H, W, a.num_sens)     # the pooled window, before any network
     elif a.spokes is not None or a.readout is not None:
         sys.exit("--spokes / --readout go with --trajectory radial")
     checked = None
@@ -155,7 +162,7 @@ if __name__ == '__main__':
             sens_maps = complex_coil_maps(a.num_sens, H, W, a.seed)
         op = NonCartesianSENSE(trajectory, (1, H, W), sens_maps=sens_maps)
         M = op.n_samples
-        frames, kspace_scale = None, None
+        frames, kspace_scale, cal = None, None, None
         if nc_kspace is None:
             base = phantom_image(H, W, seed=a.seed).to(device)
             beat = torch.cos(torch.arange(a.T, device=device) * (2 * torch.pi / a.T)).view(a.T, 1, 1, 1)
@@ -163,6 +170,14 @@ if __name__ == '__main__':
             y = op(frames.to(torch.complex64))                             # (n, T, 1, M): frame t on trajectory t
         else:
             y = nc_kspace.to(device).reshape(a.num_sens, a.T, 1, M)
+        if self_cal is not None:               # simulated with the true maps (or measured), reconstructed with the estimated ones
+            cal = NonCartesianSENSE.from_measurement(y.reshape(a.num_sens, a.T, M), trajectory, (1, H, W),
+                                                     n_virtual=self_cal.virtual_coils, noise_cov=self_cal.noise_cov,
+                                                     method=self_cal.maps_method, calib_max=self_cal.calib_max,
+                                                     **self_cal.maps_kwargs)
+            op, a.num_sens = cal.op, cal.op.num_sens
+            y = cal.measurement.reshape(a.num_sens, a.T, 1, M)
+        if nc_kspace is not None:
             kspace_scale = float(a.kspace_scale) if a.kspace_scale != "auto" else None
             if kspace_scale is None:                                       # 1 / peak |zero_filled(y)| over all frames
                 peak = float(op.zero_filled(y).abs().max())
@@ -191,6 +206,12 @@ if __name__ == '__main__':
         torch.save(zf.cpu(), os.path.join(a.save_dir, "ZF.pt"))
         torch.save(y.cpu(), os.path.join(a.save_dir, "measurement.pt"))
         torch.save(op.sens_maps, os.path.join(a.save_dir, "sens_maps.pt"))
+        if cal is not None:
+            torch.save(cal.calib_kspace.cpu(), os.path.join(a.save_dir, "calib_kspace.pt"))
+            if cal.coil_matrix is not None:
+                torch.save(cal.coil_matrix, os.path.join(a.save_dir, "coil_matrix.pt"))
+            if cal.eigval is not None:
+                torch.save(cal.eigval, os.path.join(a.save_dir, "espirit_eigval.pt"))
         if a.num_samples > 1:
             flat = out.to(device).reshape(out.shape[0], -1, H, W)
             torch.save({k: v.cpu() for k, v in sharding.all_reduce_posterior(flat, a.num_samples).items()},
