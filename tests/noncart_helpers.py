@@ -5,6 +5,8 @@ conjugate-gradient proximal.  Inputs are whatever the GPU gets (float32 images /
 Conventions: trajectory k (M, 2) = (k_y, k_x) in cycles per field of view; images [..., H, W]; samples [..., M];
 maps S [n, H, W]; coil axis first, as in the package ([n, B, ...]).
 """
+from argparse import Namespace
+
 import numpy as np
 
 
@@ -185,3 +187,101 @@ def relerr(got, ref):
     """max |err| / max |ref|"""
     ref = np.asarray(ref)
     return float(np.abs(np.asarray(got) - ref).max() / np.abs(ref).max())
+
+
+# ---- the edge cases of tests/test_noncart_edges_{gpu,host}.py: shapes past one sample stage, column tile and grid round -----
+NC_STAGE = 256                                   # samples per LDS stage and columns per tile of ndft_adjoint_kernel (NC_THREADS)
+NC_FORWARD_TILE = 64                             # samples per workgroup of ndft_forward_kernel (NC_TILE)
+NC_GRID_ROUND = 2048 * 256                       # table entries per grid round of nc_phasor_kernel (ipdm_ew_grid's cap x 256)
+
+# name -> (H, W, B, coils, spokes, readout) with nh.edge_trajectory(spokes, readout, H, W)
+EDGE_CASES = {"wide": (16, 320, 2, 3, 27, 64), "tall": (320, 16, 2, 3, 27, 64), "widest": (8, 1024, 1, 2, 9, 64),
+              "smallest_wide": (2, 64, 3, 4, 5, 64), "smallest_tall": (64, 2, 3, 4, 5, 64)}
+EDGE_WEIGHTS = ("none", "ramp", "blocky")
+# (H, W, T, B, coils); frame_trajectory(T, H, W, 27, 33): 897 = 3 * 256 + 129 samples per frame
+EDGE_FRAME_CASES = {"wide": (16, 320, 2, 4, 2), "tall": (320, 16, 3, 6, 1)}
+
+
+def blocky_weights(k, H, W):
+    """ramp weights, exactly zero on the samples [256, 512) and on the whole last partial stage of 256"""
+    w = ramp_weights(k, H, W).astype(np.float32)
+    w[NC_STAGE:2 * NC_STAGE] = 0
+    w[len(k) // NC_STAGE * NC_STAGE:] = 0
+    return w
+
+
+def edge_weights(kind, k, H, W):
+    """float32 weights [M] as the GPU gets them; None for "none\""""
+    return {"none": lambda: None, "ramp": lambda: ramp_weights(k, H, W).astype(np.float32),
+            "blocky": lambda: blocky_weights(k, H, W)}[kind]()
+
+
+def frame_trajectory(T, H, W, spokes, readout):
+    """(T, M, 2): frame t = `spokes` consecutive golden-angle spokes of radial(spokes * T, ...) plus the six bound points of
+    edge_trajectory (tests/test_noncart_frames_gpu.py's frame_trajectory, restated here for the host file)"""
+    whole = radial(spokes * T, readout, H, W).reshape(T, spokes * readout, 2)
+    extra = edge_trajectory(1, 1, H, W)[1:]
+    return np.ascontiguousarray(np.stack([np.concatenate([whole[t], extra]) for t in range(T)]))
+
+
+_EDGE_INPUTS, _EDGE_REFS = {}, {}
+
+
+def edge_inputs(name):
+    """the inputs of one edge case, made once: the float32 / complex64 values the GPU gets, the float64 trajectory, and the
+    weight-free float64 references (forward with maps, forward of coil images)"""
+    if name not in _EDGE_INPUTS:
+        H, W, B, n, spokes, readout = EDGE_CASES[name]
+        rng = np.random.default_rng(H * 131 + W + 7 * n)
+        k = edge_trajectory(spokes, readout, H, W)
+        S = smooth_maps(n, H, W, seed=n)
+        x = (rng.standard_normal((B, H, W)) + 1j * rng.standard_normal((B, H, W))).astype(np.complex64)
+        y = (rng.standard_normal((n, B, len(k))) + 1j * rng.standard_normal((n, B, len(k)))).astype(np.complex64)
+        imgs = (S[:, None] * x[None]).astype(np.complex64)
+        _EDGE_INPUTS[name] = Namespace(name=name, H=H, W=W, B=B, n=n, M=len(k), k=k, S=S, x=x, y=y, imgs=imgs,
+                                       Ax=sense_forward(x, S, k), Aimgs=ndft_forward(imgs, k))
+    return _EDGE_INPUTS[name]
+
+
+def edge_refs(name, kind):
+    """the float64 references of one edge case that depend on the weights (kind in EDGE_WEIGHTS), made once and never
+    written to: A^H W y combined and per coil, the spectrum P, T x with and without maps"""
+    if (name, kind) not in _EDGE_REFS:
+        c = edge_inputs(name)
+        w = edge_weights(kind, c.k, c.H, c.W)
+        coil_imgs = ndft_adjoint(c.y, c.k, c.H, c.W, w)
+        AHy = (np.asarray(c.S, dtype=np.complex128).conj()[:, None] * coil_imgs).sum(0)
+        P = toeplitz_psf(c.k, c.H, c.W, w)
+        r = Namespace(w=w, coil_imgs=coil_imgs, AHy=AHy, P=P, Tx=toeplitz_normal(c.x, c.S, P),
+                      Tx_nomaps=toeplitz_normal(c.x, None, P))
+        for a in (coil_imgs, AHy, P, r.Tx, r.Tx_nomaps):
+            a.setflags(write=False)
+        _EDGE_REFS[name, kind] = r
+    return _EDGE_REFS[name, kind]
+
+
+def prox_problem(H, W, spokes, readout, B=3, n=4):
+    """the proximal problem of tests/test_noncart_gpu.py's _prox_problem, host arrays only: seed H + W, radial trajectory,
+    measurements of a random-phase image through the float64 forward transform"""
+    rng = np.random.default_rng(H + W)
+    k = radial(spokes, readout, H, W)
+    S = smooth_maps(n, H, W, seed=1)
+    z = (rng.standard_normal((B, H, W)) + 1j * rng.standard_normal((B, H, W))).astype(np.complex64)
+    img = (rng.random((B, H, W)) * np.exp(1j * rng.standard_normal((B, H, W)))).astype(np.complex64)
+    y = sense_forward(img, S, k).astype(np.complex64)
+    return Namespace(H=H, W=W, B=B, n=n, k=k, S=S, z=z, y=y)
+
+
+_PROX_REFS = {}
+
+
+def prox_reference(H, W, spokes, readout, B, n, a, max_iter, tol):
+    """-> (problem, A^H y, float64 CG solution, its iteration counts), made once per argument list"""
+    key = (H, W, spokes, readout, B, n, a, max_iter, tol)
+    if key not in _PROX_REFS:
+        p = prox_problem(H, W, spokes, readout, B, n)
+        ahy = sense_adjoint(p.y, p.S, p.k, H, W)
+        P = toeplitz_psf(p.k, H, W)
+        ref, it = cg_prox(p.z, ahy, lambda v: toeplitz_normal(v, p.S, P), a, max_iter, tol)
+        _PROX_REFS[key] = (p, ahy, ref, it)
+    return _PROX_REFS[key]
