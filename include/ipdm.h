@@ -887,6 +887,13 @@ int ipdm_conv2d_wino_hx2_form(int Cin, int Cout, int H, int W, int dilation);
 int64_t ipdm_conv_wino1d_weight_bytes(int Cout, int Cin);
 int ipdm_conv_wino1d_pack_weight(const float* w /* [Cout][Cin][3][3] */, void* U, int Cout, int Cin, void* stream);
 int ipdm_conv2d_wino1d_supported(int Cin, int Cout, int H, int W);
+/* The folded ConvMeanPool blob of the same kernel: the 2x2 mean's two rows summed (in fp32) into a 4-row filter g'[0] = g[0],
+ * g'[1] = g[0] + g[1], g'[2] = g[1] + g[2], g'[3] = g[2] -- 16 positions, the same layout and scale table.  A pooled row is then
+ * one contraction over four input rows: 16 instead of 24 multiply-adds per pooling window and (co, ci).  Only for
+ * ipdm_conv2d_wino1d_f32 / _stats_f32 with pool2 = 2 and coef = NULL (a fused input: IPDM_EUNSUPPORTED); results agree with
+ * the pool2 = 1 launch of the 12-position blob to fp32 rounding, not bit for bit. */
+int64_t ipdm_conv_wino1d_pool_weight_bytes(int Cout, int Cin);
+int ipdm_conv_wino1d_pack_weight_pool(const float* w /* [Cout][Cin][3][3] */, void* U, int Cout, int Cin, void* stream);
 /* 3x3x3 convolution of volumes [B][C][D][H][W] on the same kernel: the depth taps are further K chunks (36 weight positions; blob
  * from ipdm_conv_wino1d_pack_weight3d, w [Cout][Cin][3][3][3]); planes of 12 pixels or less go two depth slices per row block.
  * Undilated, Cin % 32 == 0, Cout % 128 == 0, W % 4 == 0 and (W <= 12 or W >= 16): ipdm_conv3d_wino1d_supported. */
@@ -897,7 +904,9 @@ int ipdm_conv3d_wino1d_f32(const float* x, const void* U, const float* bias, con
                            float* out_act, int act_out, int B, int Cin, int Cout, int D, int H, int W,
                            const ipdm_conv_ext_t* ext, void* stream);
 /* coef != NULL: the input is act(InstanceNorm++(x)) -- coef [B][Cin][3] from ipdm_instnorm_plus_coef_f32, act = IPDM_ACT_ELU --
- * applied inside the kernel (as ipdm_conv2d_hx2_f32's fused input); ext->in_amax is then the coefficient kernel's bound. */
+ * applied inside the kernel (as ipdm_conv2d_hx2_f32's fused input); ext->in_amax is then the coefficient kernel's bound.
+ * pool2: 0 = the convolution, 1 = its 2x2 mean [B][Cout][H/2][W/2] from the 12-position blob, 2 = the same mean from the folded
+ * blob of ipdm_conv_wino1d_pack_weight_pool (U must be that blob). */
 int ipdm_conv2d_wino1d_f32(const float* x, const void* U, const float* bias, const float* coef, int act,
                            const float* residual, float* out, float* out_act, int act_out, int B, int Cin, int Cout, int H,
                            int W, int pool2, const ipdm_conv_ext_t* ext, void* stream);

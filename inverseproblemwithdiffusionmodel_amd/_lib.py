@@ -195,6 +195,8 @@ SIGNATURES = {
     "ipdm_conv_wino_hx2_weight_bytes": [c_int, c_int],
     "ipdm_conv_wino1d_weight_bytes": [c_int, c_int],
     "ipdm_conv_wino1d_pack_weight": [P, P, c_int, c_int, P],
+    "ipdm_conv_wino1d_pool_weight_bytes": [c_int, c_int],
+    "ipdm_conv_wino1d_pack_weight_pool": [P, P, c_int, c_int, P],
     "ipdm_conv2d_wino1d_supported": [c_int, c_int, c_int, c_int],
     "ipdm_conv_wino1d_weight_bytes3d": [c_int, c_int],
     "ipdm_conv_wino1d_pack_weight3d": [P, P, c_int, c_int, P],
@@ -237,6 +239,7 @@ _RESTYPES = {"ipdm_build_arch": c_char_p, "ipdm_debug_lds_optin_count": c_int64,
              "ipdm_conv_bx3_weight_bytes": c_int64,
              "ipdm_conv_wino_bx3_weight_bytes": c_int64, "ipdm_conv_hx2_weight_bytes": c_int64,
              "ipdm_conv_wino_hx2_weight_bytes": c_int64, "ipdm_conv_wino1d_weight_bytes": c_int64, "ipdm_conv_wino1d_weight_bytes3d": c_int64,
+             "ipdm_conv_wino1d_pool_weight_bytes": c_int64,
              "ipdm_conv1d_hx2_weight_bytes": c_int64, "ipdm_csm_workspace_bytes": ctypes.c_size_t,
              "ipdm_coilcomp_workspace_bytes": ctypes.c_size_t, "ipdm_gcc_workspace_bytes": ctypes.c_size_t,
              "ipdm_espirit_workspace_bytes": ctypes.c_size_t, "ipdm_nc_coil_gram_workspace_bytes": ctypes.c_size_t}

@@ -41,23 +41,35 @@ static_assert(Y_STAGE <= 2 * Y_M && Y_LDS_BYTES <= 160 * 1024, "LDS budget");
 constexpr float HX1_PRESCALE = 0.5f;                 // the 1-D input transform at most doubles a value
 constexpr int Y_QC = 10, Y_RC4 = 40, Y_QN = 100;     // quads / floats per raw row, quads per channel
 
-__device__ __forceinline__ float wino1d_U(const float* g, int p) {       // p = (kz*3 + ky)*4 + xi; g: the filter's 9 (or 27) taps
-  g += (p / 12) * 9;
-  p %= 12;
+// fold (npos = 16, the ConvMeanPool blob): p = r*4 + xi over the FOUR rows g'[0] = g[0], g'[1] = g[0] + g[1], g'[2] = g[1] + g[2],
+// g'[3] = g[2] of the filter that yields the sum of a pooling window's two output rows -- added in fp32, before the G transform
+__device__ __forceinline__ float wino1d_U(const float* g, int p, bool fold) {   // p = (kz*3 + ky)*4 + xi; g: the filter's 9 (or 27) taps
   const float G[4][3] = {{1.f, 0.f, 0.f}, {0.5f, 0.5f, 0.5f}, {0.5f, -0.5f, 0.5f}, {0.f, 0.f, 1.f}};
-  const int ky = p >> 2, xi = p & 3;
-  return G[xi][0] * g[ky * 3 + 0] + G[xi][1] * g[ky * 3 + 1] + G[xi][2] * g[ky * 3 + 2];
+  float t[3];
+  const int xi = p & 3;
+  if (fold) {
+    const int r = p >> 2;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) t[k] = (r < 3 ? g[r * 3 + k] : 0.f) + (r > 0 ? g[(r - 1) * 3 + k] : 0.f);
+  } else {
+    g += (p / 12) * 9;
+    p %= 12;
+    const int ky = p >> 2;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) t[k] = g[ky * 3 + k];
+  }
+  return G[xi][0] * t[0] + G[xi][1] * t[1] + G[xi][2] * t[2];
 }
 
 // one workgroup per output channel: inv_scale[co] = 2^-k with max |U| * 2^k in [2^13, 2^14), times 1 / HX1_PRESCALE
 __global__ __launch_bounds__(256) void wino1d_scale_kernel(const float* __restrict__ w, float* __restrict__ inv_scale, int Cout,
-                                                           int Cin, int n_co_pad, int npos) {
+                                                           int Cin, int n_co_pad, int npos, bool fold) {
   __shared__ float red[256];
   const int co = blockIdx.x;
   float m = 0.f;
   if (co < Cout)
     for (int i = threadIdx.x; i < Cin * npos; i += 256)
-      m = fmaxf(m, fabsf(wino1d_U(w + ((size_t)co * Cin + i / npos) * (npos / 12 * 9), i % npos)));
+      m = fmaxf(m, fabsf(wino1d_U(w + ((size_t)co * Cin + i / npos) * (npos / 12 * 9), i % npos, fold)));
   red[threadIdx.x] = m;
   __syncthreads();
   for (int st = 128; st > 0; st >>= 1) {
@@ -74,7 +86,7 @@ __global__ __launch_bounds__(256) void wino1d_scale_kernel(const float* __restri
 
 __global__ __launch_bounds__(256) void wino1d_weight_kernel(const float* __restrict__ w, unsigned short* __restrict__ out,
                                                             const float* __restrict__ inv_scale, int Cout, int Cin, int n_cc,
-                                                            int n_ct, int npos) {
+                                                            int n_ct, int npos, bool fold) {
   const int64_t total = (int64_t)npos * n_cc * n_ct * 512;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
     const int q = (int)(i & 7), r = (int)((i >> 3) & 31), h = (int)((i >> 8) & 1);
@@ -84,7 +96,7 @@ __global__ __launch_bounds__(256) void wino1d_weight_kernel(const float* __restr
     const int p = (int)(rest / ((int64_t)n_ct * n_cc));
     const int co = ct * 32 + r, ci = cc * 16 + 8 * h + q;
     float v = 0.f;
-    if (co < Cout && ci < Cin) v = wino1d_U(w + ((size_t)co * Cin + ci) * (npos / 12 * 9), p) * (1.f / (inv_scale[co] * HX1_PRESCALE));
+    if (co < Cout && ci < Cin) v = wino1d_U(w + ((size_t)co * Cin + ci) * (npos / 12 * 9), p, fold) * (1.f / (inv_scale[co] * HX1_PRESCALE));
     const _Float16 hi = (_Float16)v;
     const _Float16 lo = (_Float16)(v - (float)hi);
     const int64_t base = rest * 2 * 512 + h * 256 + r * 8 + q;
@@ -107,8 +119,16 @@ __global__ __launch_bounds__(256) void wino1d_weight_kernel(const float* __restr
 // NBU = 3 (VOL, rows of exactly 12 used pixel pairs -- 24-pixel planes or two 12-pixel slices -- and 8-row blocks): the block's 8 x 12
 // used columns are numbered row * 12 + pair and fill THREE 32-column blocks completely, instead of 12 of 16 pairs in each of four:
 // a quarter of the MFMAs, operand reads and epilogue rounds gone
-template <int OUTS, bool STATS = false, bool POOL = false, bool FIN = false, bool VOL = false, int NBU = 4>
+// FOLD (POOL, the 16-position blob of wino1d_U's fold mode): the 2x2 mean's VERTICAL half lives in the filter -- a pooled row is one
+// contraction over FOUR staged rows (K = 4 Cin once instead of K = 3 Cin for each of its two convolution rows).  The block's 4 x 16
+// pooled pixels are 64 columns in TWO column blocks: block nb holds pooled rows 2nb + (j >> 4), its B operand for filter row r is
+// staged row 4nb + 2(j >> 4) + r.  Eight sub-steps (4 rows x 2 blocks) of 6 MFMAs per chunk instead of twelve, 64 accumulator
+// registers instead of 128, four epilogue rounds instead of eight and no cross-row exchange: each thread sums its pixel pair
+template <int OUTS, bool STATS = false, bool POOL = false, bool FIN = false, bool VOL = false, int NBU = 4, bool FOLD = false>
 __global__ __launch_bounds__(512) void conv_wino1d_kernel(ConvArgs a, int total_tiles) {
+  static_assert(!FOLD || (POOL && !VOL && !FIN && NBU == 4), "FOLD: the pooled form, plain input, images");
+  constexpr int NBA = FOLD ? 2 : NBU;                          // column blocks (accumulators, epilogue rounds per channel tile)
+  constexpr int NKY = FOLD ? 4 : 3;                            // filter rows
   extern __shared__ __align__(16) float lds[];
   unsigned* const ldsw = reinterpret_cast<unsigned*>(lds);
   const int tid = threadIdx.x;
@@ -332,7 +352,7 @@ __global__ __launch_bounds__(512) void conv_wino1d_kernel(ConvArgs a, int total_
 #pragma unroll
       for (int s = 0; s < 2; ++s) fr[c][s] = base[c * 128 + s * 64];
   };
-  const int b_lane = (j >> 4) * Y_RS + xi * 256 + h * 32 + (j & 15);
+  const int b_lane = (j >> 4) * (FOLD ? 2 : 1) * Y_RS + xi * 256 + h * 32 + (j & 15);
   [[maybe_unused]] int b_cmp[3] = {0, 0, 0};                    // NBU == 3: this lane's (row, pair) of column 32 nb + j, as a word offset
   if constexpr (NBU == 3) {
 #pragma unroll
@@ -343,16 +363,16 @@ __global__ __launch_bounds__(512) void conv_wino1d_kernel(ConvArgs a, int total_
   }
   auto load_B = [&](uint4 (&fr)[2], const unsigned* cur, auto kyc, auto nbc) {
     constexpr int ky = decltype(kyc)::value, nb = decltype(nbc)::value;
-    const unsigned* bp = NBU == 3 ? cur + ky * Y_RS + b_cmp[nb < 3 ? nb : 0] : cur + (2 * nb + ky) * Y_RS + b_lane;
+    const unsigned* bp = NBU == 3 ? cur + ky * Y_RS + b_cmp[nb < 3 ? nb : 0] : cur + ((FOLD ? 4 : 2) * nb + ky) * Y_RS + b_lane;
 #pragma unroll
     for (int s = 0; s < 2; ++s) fr[s] = make_uint4(bp[s * 128], bp[s * 128 + 16], bp[s * 128 + 64], bp[s * 128 + 80]);
   };
 
-  f32x16 acc[2][NBU];
+  f32x16 acc[2][NBA];
 #pragma unroll
-  for (int i = 0; i < 2 * NBU; ++i)
+  for (int i = 0; i < 2 * NBA; ++i)
 #pragma unroll
-    for (int rr = 0; rr < 16; ++rr) acc[i / NBU][i % NBU][rr] = 0.f;
+    for (int rr = 0; rr < 16; ++rr) acc[i / NBA][i % NBA][rr] = 0.f;
 
   auto lds_barrier = [&]() {
     __builtin_amdgcn_sched_barrier(0);
@@ -421,7 +441,8 @@ __global__ __launch_bounds__(512) void conv_wino1d_kernel(ConvArgs a, int total_
         }
         uint4 bsh[2][2];
         // the wave's DMA of chunk ch+1 (issued a chunk ago) has landed: three fragment groups are younger, two of them still wanted
-        __builtin_amdgcn_s_waitcnt(0x0F78);                     // vmcnt(8)
+        // (FOLD: four groups younger, three still wanted)
+        __builtin_amdgcn_s_waitcnt(FOLD ? 0x0F7C : 0x0F78);     // vmcnt(8) / vmcnt(12)
         read_items();
         load_B(bsh[0], cur, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
         __builtin_amdgcn_sched_barrier(0);
@@ -429,17 +450,21 @@ __global__ __launch_bounds__(512) void conv_wino1d_kernel(ConvArgs a, int total_
         issue_dma(dma_chunk);
         __builtin_amdgcn_sched_barrier(0);
         float va[4], vb[4];
-        static_for<3 * NBU>([&](auto ssc) {
+        constexpr int NSS = NKY * NBA;
+        static_for<NSS>([&](auto ssc) {
           constexpr int ss = decltype(ssc)::value;
-          constexpr int ky = ss / NBU, nb = ss % NBU;
-          constexpr int aslot = (cpar * 3 + ky) & 1;
-          if constexpr (ss < 3 * NBU - 1)
-            load_B(bsh[(ss + 1) & 1], cur, std::integral_constant<int, (ss + 1) / NBU>{}, std::integral_constant<int, (ss + 1) % NBU>{});
-          // producer work of item ky, dealt over the sub-steps of a filter row
-          constexpr int it = ky;
-          if constexpr (nb == 0) xform_item(std::integral_constant<int, it>{}, va, vb);
-          if constexpr (nb == 1) store_item(nxt, std::integral_constant<int, it>{}, va, vb, std::integral_constant<int, 0>{}, std::integral_constant<int, 2>{});
-          if constexpr (nb == 2) store_item(nxt, std::integral_constant<int, it>{}, va, vb, std::integral_constant<int, 2>{}, std::integral_constant<int, 4>{});
+          constexpr int ky = ss / NBA, nb = ss % NBA;
+          constexpr int aslot = FOLD ? (ky & 1) : ((cpar * 3 + ky) & 1);
+          if constexpr (ss < NSS - 1)
+            load_B(bsh[(ss + 1) & 1], cur, std::integral_constant<int, (ss + 1) / NBA>{}, std::integral_constant<int, (ss + 1) % NBA>{});
+          // producer work of item ky, dealt over the sub-steps of a filter row; FOLD: the three items' nine pieces over the
+          // chunk's eight sub-steps (transform | store half | store half, the last item's transform sharing its first store's)
+          constexpr int it = FOLD ? (ss < 6 ? ss / 3 : 2) : ky;
+          constexpr int ph = FOLD ? (ss < 6 ? ss % 3 : ss - 5) : nb;
+          constexpr bool stores = ph == 1 || ph == 2;
+          if constexpr (ph == 0 || (FOLD && ss == 6)) xform_item(std::integral_constant<int, it>{}, va, vb);
+          if constexpr (ph == 1) store_item(nxt, std::integral_constant<int, it>{}, va, vb, std::integral_constant<int, 0>{}, std::integral_constant<int, 2>{});
+          if constexpr (ph == 2) store_item(nxt, std::integral_constant<int, it>{}, va, vb, std::integral_constant<int, 2>{}, std::integral_constant<int, 4>{});
           const f16x8 bh = __builtin_bit_cast(f16x8, bsh[ss & 1][0]), bl = __builtin_bit_cast(f16x8, bsh[ss & 1][1]);
 #pragma unroll
           for (int c = 0; c < 2; ++c) {
@@ -449,18 +474,23 @@ __global__ __launch_bounds__(512) void conv_wino1d_kernel(ConvArgs a, int total_
             v = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, afr[aslot][c][0]), bh, v, 0, 0, 0);
             acc[c][nb] = v;
           }
-          if constexpr (nb == NBU - 1) {
+          if constexpr (nb == NBA - 1) {
             // this filter row's fragments are free: request the row after next (same slot)
-            if constexpr (ky == 0) load_A(afr[aslot], 2, ch, cur_g.cob);
-            if constexpr (ky == 1) load_A(afr[aslot], 0, a_chunk, a_cob);
-            if constexpr (ky == 2) load_A(afr[aslot], 1, a_chunk, a_cob);
+            if constexpr (FOLD) {
+              if constexpr (ky < 2) load_A(afr[aslot], ky + 2, ch, cur_g.cob);
+              else load_A(afr[aslot], ky - 2, a_chunk, a_cob);
+            } else {
+              if constexpr (ky == 0) load_A(afr[aslot], 2, ch, cur_g.cob);
+              if constexpr (ky == 1) load_A(afr[aslot], 0, a_chunk, a_cob);
+              if constexpr (ky == 2) load_A(afr[aslot], 1, a_chunk, a_cob);
+            }
           }
-          if constexpr (ss < 3 * NBU - 1) __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);   // next sub-step's operand reads first
+          if constexpr (ss < NSS - 1) __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);   // next sub-step's operand reads first
 #pragma unroll
           for (int i = 0; i < 6; ++i) {
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x006, 4, 0);
-            if constexpr (nb == 1 || nb == 2) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x006, (FOLD && ss == 6) ? 8 : 4, 0);   // (transform and store in one sub-step)
+            if constexpr (stores) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
           }
           __builtin_amdgcn_sched_barrier(0);
         });
@@ -473,19 +503,21 @@ __global__ __launch_bounds__(512) void conv_wino1d_kernel(ConvArgs a, int total_
       t_loop += t - tq;
       tq = t;
     }
-    // ---- epilogue: eight rounds (channel tile c, column block nb) through M[rnd & 1][xi][co 64][col 32] ----
+    // ---- epilogue: eight rounds (FOLD: four) (channel tile c, column block nb) through M[rnd & 1][xi][co 64][col 32] ----
     constexpr bool W_OUT = (OUTS & 1) != 0, W_ACT = (OUTS & 2) != 0;
     float* const ms = lds + Y_S1;
     const int ecol = tid & 31, ecg = tid >> 5;                  // this thread: column, channels k*16 + ecg of the round's 64
     const int co0 = cur_g.cob * Y_CO;
-    const float* const scale_p = reinterpret_cast<const float*>(wq + (VOL ? 36 : 12) * pos_stride);
+    const float* const scale_p = reinterpret_cast<const float*>(wq + (VOL ? 36 : FOLD ? 16 : 12) * pos_stride);
     const int oHW = POOL ? HW >> 2 : (VOL ? CS : HW), oW = POOL ? a.W >> 1 : a.W;     // the written tensor's channel stride / row
     const size_t tile_base = (((size_t)cur_g.b * a.Cout + co0) * oHW + (size_t)cur_g.z * HW + (size_t)(POOL ? cur_g.y0 >> 1 : cur_g.y0) * oW +
                               (POOL ? cur_g.x0 >> 1 : cur_g.x0)) * 4;
     // pack: pixel pairs seam .. 2 seam - 1 are the second slice's pairs 0 .. seam - 1
     const bool e_isb = pack && (ecol & 15) >= seam;
     const int e_pair = e_isb ? (ecol & 15) - seam : (ecol & 15);
-    unsigned eoff4 = 4u * (unsigned)(ecg * oHW + (POOL ? (ecol & 15) : (ecol >> 4) * oW + 2 * e_pair + (e_isb ? HW : 0)));
+    // (FOLD: column ecol is pooled row 2nb + (ecol >> 4), pooled pixel ecol & 15 -- every lane stores)
+    unsigned eoff4 = 4u * (unsigned)(ecg * oHW + (FOLD ? (ecol >> 4) * oW + (ecol & 15) : POOL ? (ecol & 15)
+                                                        : (ecol >> 4) * oW + 2 * e_pair + (e_isb ? HW : 0)));
     asm volatile("" : "+v"(eoff4));
     // NBU == 3: column 32 nb + ecol is (row, pair) = divmod(., 12); pairs 6 .. 11 of a two-slice block are the second slice's 0 .. 5
     [[maybe_unused]] auto cmp_off = [&](int nb) -> unsigned {
@@ -495,11 +527,11 @@ __global__ __launch_bounds__(512) void conv_wino1d_kernel(ConvArgs a, int total_
     };
     auto boff = [&](int c, int nb, int k) -> unsigned {
       if constexpr (NBU == 3) return 4u * (unsigned)((((k >> 1) * 2 + c) * 32 + (k & 1) * 16) * oHW) + cmp_off(nb);
-      return 4u * (unsigned)((((k >> 1) * 2 + c) * 32 + (k & 1) * 16) * oHW + (POOL ? nb : 2 * nb) * oW) + eoff4;
+      return 4u * (unsigned)((((k >> 1) * 2 + c) * 32 + (k & 1) * 16) * oHW + (POOL && !FOLD ? nb : 2 * nb) * oW) + eoff4;
     };
     auto in_range = [&](int nb) {
       if constexpr (NBU == 3) return !(pack && (32 * nb + ecol) % 12 >= 6) || cur_g.z + 1 < a.D;     // (8 full rows, 12 used pairs)
-      const bool row_ok = cur_g.y0 + 2 * nb + (ecol >> 4) < a.H;
+      const bool row_ok = FOLD ? cur_g.y0 + 4 * nb + 2 * (ecol >> 4) < a.H : cur_g.y0 + 2 * nb + (ecol >> 4) < a.H;
       if constexpr (VOL) {
         if (pack) return row_ok && (ecol & 15) < 2 * seam && (!e_isb || cur_g.z + 1 < a.D);
       }
@@ -518,8 +550,8 @@ __global__ __launch_bounds__(512) void conv_wino1d_kernel(ConvArgs a, int total_
     // (unconditional loads -- an absent operand or an out-of-range column reads the weight blob -- so that hipcc can count them)
     auto prefetch = [&](auto rc) {
       constexpr int rnd = decltype(rc)::value;
-      constexpr int c = rnd / NBU, nb = rnd % NBU, bf = rnd & 1;
-      const bool res_ok = has_res && in_range(nb) && (!POOL || (ecol >> 4) == 0);
+      constexpr int c = rnd / NBA, nb = rnd % NBA, bf = rnd & 1;
+      const bool res_ok = has_res && in_range(nb) && (!POOL || FOLD || (ecol >> 4) == 0);
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const unsigned ob = res_ok ? boff(c, nb, k) : 0u;
@@ -548,9 +580,9 @@ __global__ __launch_bounds__(512) void conv_wino1d_kernel(ConvArgs a, int total_
 #else
 #define W1D_TE(k)
 #endif
-    static_for<2 * NBU>([&](auto rc) {
+    static_for<2 * NBA>([&](auto rc) {
       constexpr int rnd = decltype(rc)::value;
-      constexpr int c = rnd / NBU, nb = rnd % NBU, bf = rnd & 1;
+      constexpr int c = rnd / NBA, nb = rnd % NBA, bf = rnd & 1;
       float* const mw = ms + (rnd & 1) * Y_M;
 #pragma unroll
       for (int rr = 0; rr < 16; ++rr) {
@@ -561,8 +593,8 @@ __global__ __launch_bounds__(512) void conv_wino1d_kernel(ConvArgs a, int total_
       W1D_TE(0);
       __syncthreads();
       W1D_TE(1);
-      if constexpr (rnd < 2 * NBU - 1) prefetch(std::integral_constant<int, rnd + 1>{});
-      const bool inr = in_range(nb) && (!POOL || (ecol >> 4) == 0);   // this thread stores (POOL: the windows' upper rows do)
+      if constexpr (rnd < 2 * NBA - 1) prefetch(std::integral_constant<int, rnd + 1>{});
+      const bool inr = in_range(nb) && (!POOL || FOLD || (ecol >> 4) == 0);   // this thread stores (POOL: the windows' upper rows do)
 #pragma unroll
       for (int half = 0; half < 2; ++half) {
         float m[2][4], sc[2], bi[2];
@@ -580,9 +612,16 @@ __global__ __launch_bounds__(512) void conv_wino1d_kernel(ConvArgs a, int total_
         for (int kk = 0; kk < 2; ++kk) {
           const int k = half * 2 + kk;
           float yv[2];
-          yv[0] = __builtin_fmaf(m[kk][0] + m[kk][1] + m[kk][2], sc[kk], bi[kk]);
-          yv[1] = __builtin_fmaf(m[kk][1] - m[kk][2] - m[kk][3], sc[kk], bi[kk]);
-          if constexpr (POOL) {
+          if constexpr (FOLD) {
+            // the filter summed the window's rows: its two columns are this thread's pixel pair
+            // (m0 + m1 + m2) + (m1 - m2 - m3) with position 2 cancelled on paper: two roundings instead of five, one LDS read less
+            yv[0] = __builtin_fmaf(__builtin_fmaf(2.f, m[kk][1], m[kk][0]) - m[kk][3], 0.25f * sc[kk], bi[kk]);
+            yv[1] = 0.f;
+          } else {
+            yv[0] = __builtin_fmaf(m[kk][0] + m[kk][1] + m[kk][2], sc[kk], bi[kk]);
+            yv[1] = __builtin_fmaf(m[kk][1] - m[kk][2] - m[kk][3], sc[kk], bi[kk]);
+          }
+          if constexpr (POOL && !FOLD) {
             // (y[::2,::2] + y[1::2,::2] + y[::2,1::2] + y[1::2,1::2]) / 4 in the reference's order (layers.py:291-313)
             const float p0 = __shfl_xor(yv[0], 16, 64), p1 = __shfl_xor(yv[1], 16, 64);
             yv[0] = (((yv[0] + p0) + yv[1]) + p1) * 0.25f;
@@ -645,7 +684,7 @@ __global__ __launch_bounds__(512) void conv_wino1d_kernel(ConvArgs a, int total_
         if constexpr (nb == 0) st_c0 = st_c1 = 0;
         st_c0 += NV * __popcll(bal & 0xffffffffull);
         st_c1 += NV * __popcll(bal >> 32);
-        if constexpr (nb == NBU - 1) {
+        if constexpr (nb == NBA - 1) {
           const float cnt = (float)(h ? st_c1 : st_c0);
           const int tb = (cur_g.y0 / Y_ROWS) * a.tiles_x + cur_g.x0 / (2 * Y_TX);
           const int n_tb = a.tiles_x * a.tiles_y;
@@ -733,7 +772,14 @@ int conv_wino1d_launch(ConvArgs a, hipStream_t s) {
 #define W1D_LAUNCH(O, S_, P_)                                                                                            \
   return a.coef ? ipdm_launch_lds(conv_wino1d_kernel<O, S_, P_, true>, grid, dim3(512), Y_LDS_BYTES, s, a, (int)nblk)   \
                 : ipdm_launch_lds(conv_wino1d_kernel<O, S_, P_, false>, grid, dim3(512), Y_LDS_BYTES, s, a, (int)nblk)
-  if (a.pool2) {
+#define W1D_LAUNCH_FOLD(O, S_) \
+  return ipdm_launch_lds(conv_wino1d_kernel<O, S_, true, false, false, 4, true>, grid, dim3(512), Y_LDS_BYTES, s, a, (int)nblk)
+  if (a.pool2 == 2) {                                          // the folded pool blob (no fused input: the entry refused it)
+    if (a.stats) { if (outs == 3) W1D_LAUNCH_FOLD(3, true); else W1D_LAUNCH_FOLD(1, true); }
+    else if (outs == 3) W1D_LAUNCH_FOLD(3, false);
+    else if (outs == 1) W1D_LAUNCH_FOLD(1, false);
+    else W1D_LAUNCH_FOLD(2, false);
+  } else if (a.pool2) {
     if (a.stats) { if (outs == 3) W1D_LAUNCH(3, true, true); else W1D_LAUNCH(1, true, true); }
     else if (outs == 3) W1D_LAUNCH(3, false, true);
     else if (outs == 1) W1D_LAUNCH(1, false, true);
@@ -743,16 +789,18 @@ int conv_wino1d_launch(ConvArgs a, hipStream_t s) {
   } else if (outs == 3) W1D_LAUNCH(3, false, false);
   else if (outs == 1) W1D_LAUNCH(1, false, false);
   else W1D_LAUNCH(2, false, false);
+#undef W1D_LAUNCH_FOLD
 #undef W1D_LAUNCH
 }
 
-int conv_wino1d_weights(const float* w, void* U, int Cout, int Cin, int npos, hipStream_t s) {
+int conv_wino1d_weights(const float* w, void* U, int Cout, int Cin, int npos, hipStream_t s) {       // npos 16: the folded pool blob
+  const bool fold = npos == 16;
   const int n_cc = (Cin + 15) / 16, n_ct = (Cout + 31) / 32;
   const int64_t total = (int64_t)npos * n_cc * n_ct * 512;
   float* inv_scale = reinterpret_cast<float*>(static_cast<char*>(U) + total * 2 * 2);
-  hipLaunchKernelGGL(wino1d_scale_kernel, dim3(n_ct * 32), dim3(256), 0, s, w, inv_scale, Cout, Cin, n_ct * 32, npos);
+  hipLaunchKernelGGL(wino1d_scale_kernel, dim3(n_ct * 32), dim3(256), 0, s, w, inv_scale, Cout, Cin, n_ct * 32, npos, fold);
   hipLaunchKernelGGL(wino1d_weight_kernel, dim3(ipdm_ew_grid(total, 256)), dim3(256), 0, s, w, (unsigned short*)U, inv_scale, Cout,
-                     Cin, n_cc, n_ct, npos);
+                     Cin, n_cc, n_ct, npos, fold);
   return ipdm_launch_status();
 }
 
@@ -770,6 +818,16 @@ extern "C" int ipdm_conv_wino1d_pack_weight(const float* w, void* U, int Cout, i
   return conv_wino1d_weights(w, U, Cout, Cin, 12, ipdm_stream(stream));
 }
 
+extern "C" int64_t ipdm_conv_wino1d_pool_weight_bytes(int Cout, int Cin) {
+  if (Cout <= 0 || Cin <= 0) return -1;
+  return (int64_t)16 * ((Cin + 15) / 16) * ((Cout + 31) / 32) * 2048 + (int64_t)((Cout + 31) / 32) * 32 * 4;
+}
+
+extern "C" int ipdm_conv_wino1d_pack_weight_pool(const float* w, void* U, int Cout, int Cin, void* stream) {
+  IPDM_REQUIRE(w && U && Cout > 0 && Cin > 0);
+  return conv_wino1d_weights(w, U, Cout, Cin, 16, ipdm_stream(stream));
+}
+
 extern "C" int ipdm_conv2d_wino1d_supported(int Cin, int Cout, int H, int W) {
   return wino1d_ok(conv_query_args(Cin, Cout, 1, H, W, 1)) ? 1 : 0;
 }
@@ -783,8 +841,8 @@ static int wino1d_entry(const float* x, const void* U, const float* bias, const 
   ConvArgs a = conv_launch_args(x, U, bias, residual, out, out_act, act_out, B, Cin, Cout, 1, H, W, 3, 1, 1, ext, conv_debug_stamps());
   a.coef = coef; a.act = coef ? act : IPDM_ACT_NONE;
   a.stats = stats;
-  a.pool2 = pool2 ? 1 : 0;
-  if (!wino1d_ok(a) || !wino_pairs_aligned(a)) return IPDM_EUNSUPPORTED;
+  a.pool2 = pool2 == 2 ? 2 : pool2 ? 1 : 0;                    // 2: U is the folded pool blob (ipdm_conv_wino1d_pack_weight_pool)
+  if (!wino1d_ok(a) || !wino_pairs_aligned(a) || (a.pool2 == 2 && coef)) return IPDM_EUNSUPPORTED;
   return conv_wino1d_launch(a, ipdm_stream(stream));
 }
 

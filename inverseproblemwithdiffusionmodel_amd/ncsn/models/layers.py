@@ -86,6 +86,10 @@ class Conv2d(ops.PackedWeightMixin, nn.Module):
     def packed_wino1d(self):
         return self._cached("wino1d", ops.conv_wino1d_weight)
 
+    def packed_wino1d_pool(self):
+        """the 1-D kernel's folded ConvMeanPool blob (ops.conv_wino1d_pool_weight)"""
+        return self._cached("wino1d_pool", ops.conv_wino1d_pool_weight)
+
     def route(self, x, site="ncsn", coef=None, **call):
         """ops.conv_route's answer for this layer reading x (`call`: the options of the call that the route looks at)"""
         return ops.conv_route(site, self.ndim, self.kernel_size, self.dilation, self.in_planes, self.out_planes, tuple(x.shape[2:]),
@@ -233,9 +237,12 @@ class ConvMeanPool(nn.Module):
                                            act_out=act_out, pool2=True, want_stats=True,
                                            in_amax=getattr(coef, "_ipdm_amax_bound", None) if dyn else None,
                                            want_amax=dyn and feeds_conv, coef=coef, act=act)
-            return ops.conv2d_wino_bx3(inputs, c.packed_wino1d() if route == ops.ROUTE_WINO1D else c.packed_wino_bx3(), bias, residual,
-                                       act_out=act_out, pool2=True, want_stats=True,     # a block's result: normalised next
-                                       in_amax=ops.in_amax_for(inputs), want_amax=dyn and feeds_conv)
+            # the 1-D kernel with the mean's rows folded into the filter (IPDM_W1D_POOLFOLD=0: four outputs averaged)
+            fold = c.packed_wino1d_pool if route == ops.ROUTE_WINO1D and ops.W1D_POOLFOLD else None
+            with ops.offer_pool_form(fold):
+                return ops.conv2d_wino_bx3(inputs, c.packed_wino1d() if route == ops.ROUTE_WINO1D else c.packed_wino_bx3(), bias, residual,
+                                           act_out=act_out, pool2=True, want_stats=True,     # a block's result: normalised next
+                                           in_amax=ops.in_amax_for(inputs), want_amax=dyn and feeds_conv)
         except _lib.IpdmUnsupported:
             return None
 

@@ -3,6 +3,7 @@ PyTorch-ROCm (plumbing), all arithmetic happens in the hand-written HIP kernels 
 
 Every function requires GPU tensors and raises otherwise -- there is no CPU path.
 """
+import contextlib
 import ctypes
 import os
 
@@ -2571,6 +2572,18 @@ def conv_wino1d_weight(w):
     return PackedBx3(blob, Cout, Cin, 12, "hx2")
 
 
+def conv_wino1d_pool_weight(w):
+    """[Cout, Cin, 3, 3] -> weights of the 1-D Winograd kernel's folded ConvMeanPool form: the 2x2 mean's two rows summed into a
+    4-row filter (16 positions; PackedBx3, kk=16, fmt "w1dp") -- for conv2d_wino_bx3(pool2=True) only"""
+    w = _gpu(w, torch.float32, "weight")
+    Cout, Cin = w.shape[:2]
+    if tuple(w.shape[2:]) != (3, 3):
+        raise ValueError(f"conv_wino1d_pool_weight: weight {tuple(w.shape)}")
+    blob = torch.empty(_lib.lib.ipdm_conv_wino1d_pool_weight_bytes(Cout, Cin), dtype=torch.uint8, device=w.device)
+    call("ipdm_conv_wino1d_pack_weight_pool", _ptr(w), _ptr(blob), Cout, Cin, _stream())
+    return PackedBx3(blob, Cout, Cin, 16, "w1dp")
+
+
 def conv_wino1d_weight3d(w):
     """[Cout, Cin, 3, 3, 3] -> weights of the 1-D Winograd kernel's volume form (36 positions: depth tap x filter row x position)"""
     w = _gpu(w, torch.float32, "weight")
@@ -2621,6 +2634,24 @@ WINO1D_STATS = os.environ.get("IPDM_WINO1D_STATS", "1") != "0"      # the launch
 # measured SLOWER on MI355X (17.24 -> 17.68 ms per iteration, same box: +1.1 ms of convolution for 0.8 ms of passes removed -- the
 # exponentials and selects in a 256-register kernel cost more than 8 bytes per element at the HBM roof), so off by default
 WINO1D_FIN = os.environ.get("IPDM_WINO1D_FIN", "0") != "0"
+# ConvMeanPool on the 1-D kernel: the 2x2 mean's rows folded into a 4-row filter (conv_wino1d_pool_weight: 16 of the direct form's
+# 36 multiply-adds instead of 24); 0: the 12-position blob and the epilogue that averages four convolution outputs
+W1D_POOLFOLD = os.environ.get("IPDM_W1D_POOLFOLD", "1") != "0"
+_POOL_FORM_OFFER = None
+
+
+@contextlib.contextmanager
+def offer_pool_form(get):
+    """ConvMeanPool.fused's choice of the folded form: inside the block, a conv2d_wino_bx3(pool2=True) of a 12-position blob with a
+    plain input launches the folded form on get()'s blob (Conv2d.packed_wino1d_pool) instead.  The offer travels beside the call,
+    not in it: what the layer modules hand to this module, and what a 12-position blob hands to the native entry, are pinned
+    (tests/golden/g39, g40) and stay as they are.  get = None: no offer."""
+    global _POOL_FORM_OFFER
+    prev, _POOL_FORM_OFFER = _POOL_FORM_OFFER, get
+    try:
+        yield
+    finally:
+        _POOL_FORM_OFFER = prev
 
 
 def wino1d_pays(Cin, Cout, H, W, dilation=1):
@@ -2645,30 +2676,40 @@ def conv2d_wino_bx3(x, U, bias=None, residual=None, act_out=ACT_NONE, raw=True, 
     """3x3 convolution through the split-bf16 Winograd kernel (same output options as conv2d).
     res_second (needs residual, act_out (ACT_COPY = none) and raw): -> (conv + bias, act_out(conv + bias + residual)).
     pool2: the ConvMeanPool form -- outputs (and the residual) are [B, Cout, H/2, W/2] 2x2 means of the convolution;
-    raises IpdmUnsupported where the pooled epilogue is not built (small / odd images).
+    raises IpdmUnsupported where the pooled epilogue is not built (small / odd images).  A conv_wino1d_pool_weight blob
+    (fmt "w1dp") runs the 1-D kernel's folded pooled form and serves nothing else (ValueError without pool2 or with coef).
     want_stats: the result feeds an InstanceNorm++ -- where the statistics epilogue exists for this shape, its partials
     [B, Cout, P, 3] are hung on the raw result as `_ipdm_partials` (instnorm_plus_coef picks them up).
     x may be any contiguous tensor (off a 16-byte boundary: the dword-staged forms, no statistics epilogue, no split-K).
     A residual that does not start on an 8-byte boundary is copied first (_wino_residual: the epilogue fetches pairs)."""
     x = _gpu(x, torch.float32, "x")
     B, Cin, H, W = x.shape
+    if _POOL_FORM_OFFER is not None and pool2 and U.kk == 12 and U.fmt == "hx2" and coef is None and act == ACT_NONE:
+        offered = _POOL_FORM_OFFER()
+        if (offered.fmt, offered.Cout, offered.Cin) != ("w1dp", U.Cout, U.Cin):
+            raise ValueError("conv2d_wino_bx3: the offered pool form does not match the weight blob")
+        U = offered
+    fold = U.fmt == "w1dp"               # conv_wino1d_pool_weight: the 1-D kernel's folded pooled form, an f16x2 launch
+    if fold and (not pool2 or U.kk != 16):
+        raise ValueError("conv2d_wino_bx3: the folded pool blob (conv_wino1d_pool_weight) serves pool2=True launches only")
+    fmt = "hx2" if fold else U.fmt
     amax_t = None
-    if U.fmt == "hx2" and in_amax is not None:
+    if fmt == "hx2" and in_amax is not None:
         if in_amax is True and coef is not None:
             raise ValueError("conv2d_wino_bx3: with a fused input the maxima are the coefficient kernel's bound, not max |x|")
         amax_t = absmax_per_image(x) if in_amax is True else in_amax
     bias_per_image = bias is not None and bias.dim() == 2
     if bias_per_image and (tuple(bias.shape) != (B, U.Cout) or bias.stride(1) != 1):
         raise ValueError(f"conv2d_wino_bx3: per-image bias {tuple(bias.shape)} != {(B, U.Cout)} (rows may be strided, not columns)")
-    one_d = U.kk == 12                   # conv_wino1d_weight: 1-D Winograd along x (conv_wino1d.hip), plain epilogues only
+    one_d = U.kk == 12 or fold           # conv_wino1d_weight: 1-D Winograd along x (conv_wino1d.hip), plain epilogues only
     if U.kk not in (12, 16) or U.Cin != Cin:
         raise ValueError("conv2d_wino_bx3: weight blob does not match the input")
-    if one_d and (dilation != 1 or U.fmt != "hx2"):
+    if one_d and (dilation != 1 or fmt != "hx2"):
         raise ValueError("conv2d_wino_bx3: the 1-D Winograd blob serves undilated f16x2 launches only")
     if coef is not None or act != ACT_NONE:
         # fused input act(InstanceNorm++(x)) (coef from instnorm_plus_coef): the 1-D kernel's producer applies it to the raw rows
-        if not one_d or coef is None or act != ACT_ELU:
-            raise ValueError("conv2d_wino_bx3: a fused input (coef + ACT_ELU) is the 1-D Winograd kernel's only")
+        if not one_d or fold or coef is None or act != ACT_ELU:
+            raise ValueError("conv2d_wino_bx3: a fused input (coef + ACT_ELU) is the 1-D Winograd kernel's only (12-position blob)")
         coef = _gpu(coef, torch.float32, "coef")
         if tuple(coef.shape) != (B, Cin, 3):
             raise ValueError(f"conv2d_wino_bx3: coef {tuple(coef.shape)} != {(B, Cin, 3)}")
@@ -2682,7 +2723,7 @@ def conv2d_wino_bx3(x, U, bias=None, residual=None, act_out=ACT_NONE, raw=True, 
     e0 = _trace_open()
     nb = wino_bx3_max_batch(Cin, H, W, dilation)
     # 16-pixel layers with few channel tiles: two K halves + a fixed-order reduction
-    ksplit = 1 if one_d or pool2 or x.data_ptr() % 16 or (WBX3_CO32 and U.fmt == "hx2") else wino_bx3_splitk(Cin, Cout, H, W, dilation)
+    ksplit = 1 if one_d or pool2 or x.data_ptr() % 16 or (WBX3_CO32 and fmt == "hx2") else wino_bx3_splitk(Cin, Cout, H, W, dilation)
     part = None
     if ksplit == 1 and want_stats and raw and USE_STATS_EPILOGUE and x.data_ptr() % 16 == 0:
         P = (int(_lib.lib.ipdm_conv2d_wino1d_stats_partials(Cin, Cout, H, W)) if one_d else
@@ -2692,7 +2733,7 @@ def conv2d_wino_bx3(x, U, bias=None, residual=None, act_out=ACT_NONE, raw=True, 
     for n, cut in _chunks(B, nb):        # one launch unless the batch outgrows the kernel's 32-bit buffer offsets
         head = (_ptr(cut(x)), _ptr(U.blob), _ptr(cut(bias) if bias_per_image else bias))
         outs = (_ptr(cut(residual)), _ptr(cut(out)), _ptr(cut(out_act)), act_out, n, Cin, Cout, H, W)
-        ext = _conv_ext(U.fmt, cut(amax_t), cut(x), False, bias_per_image, out_scale, bias.stride(0) if bias_per_image else 0,
+        ext = _conv_ext(fmt, cut(amax_t), cut(x), False, bias_per_image, out_scale, bias.stride(0) if bias_per_image else 0,
                         cut(slot_o), cut(slot_a), res_second)
         if ksplit > 1:
             work = torch.empty((ksplit, n, Cout, H, W), dtype=torch.float32, device=x.device)
@@ -2700,7 +2741,7 @@ def conv2d_wino_bx3(x, U, bias=None, residual=None, act_out=ACT_NONE, raw=True, 
         elif one_d:                      # (+ fused input, no dilation)
             stats = () if part is None else (_ptr(cut(part)),)
             call("ipdm_conv2d_wino1d_f32" if part is None else "ipdm_conv2d_wino1d_stats_f32", *head, _ptr(cut(coef)), act, *outs,
-                 int(bool(pool2)), *stats, ext, _stream())
+                 2 if fold else int(bool(pool2)), *stats, ext, _stream())
         else:
             args = head + outs + (dilation, int(bool(pool2)))
             if part is not None:
@@ -2712,9 +2753,12 @@ def conv2d_wino_bx3(x, U, bias=None, residual=None, act_out=ACT_NONE, raw=True, 
             call(f"ipdm_conv2d_wino_{U.fmt}_f32", *args, ext, _stream())
     if part is not None:
         out._ipdm_partials = (part, (out._version, out.data_ptr()))
-    form = dict(pool2=False, ksplit=ksplit) if ksplit > 1 else dict(pool2=bool(pool2), wino1d=one_d, stats=part is not None)
+    # (the folded form executes 16 / 36 of the direct multiply-adds, the 2-D Winograd factor: counted as `wino`, not `wino1d`)
+    form = dict(pool2=False, ksplit=ksplit) if ksplit > 1 else dict(pool2=bool(pool2), wino1d=one_d and not fold, stats=part is not None)
+    if fold:
+        form["w1d_fold"] = True
     return _conv_done(e0, out, out_act, slot_o, slot_a, B=B, Cin=Cin, Cout=Cout, H=H, W=W, k=3, dil=dilation, wino=True, bx3=True,
-                      fmt=U.fmt, res=residual is not None, **form)
+                      fmt=fmt, res=residual is not None, **form)
 
 
 # f16x2 family: the 16-pixel layers whose split-K rule says "two K halves" run as ONE launch of 32-channel workgroups instead
